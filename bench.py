@@ -3,7 +3,7 @@
 semantics) on the project_gadget workload -- 10^7 particles, ONE 1024^2 orthographic image
 (BASELINE.json configs[3], the configuration the metric is quoted on; it fits one GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One process per GPU (torch.distributed / RCCL when N > 1): every rank builds the same BVH
 from the same seeded particles (the tree is replicated), traces its own contiguous shard of
@@ -55,6 +55,7 @@ VALU_PEAK_GINST = N_SIMDS * MAX_CLOCK_GHZ / 2.0   # v_fma_f32 wave64: 2 cycles p
 MIN_VALU_PER_HIT = 10   # sub sub mul fma | sqrt mul cvt shl | LDS | fma fma (csrc/trace_kernel.hpp, test-free rounds of fat spheres)
 PMC_FILE = os.path.join(ROOT, "profiles", "r03_pmc_trace.json")
 TRACE_SRC = os.path.join(ROOT, "grace-devel_amd", "csrc", "trace_kernel.hpp")   # the kernel's source
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most this much in all
 
 
 def make_particles(n, device, seed=42):
@@ -66,6 +67,20 @@ def make_particles(n, device, seed=42):
     s[:, :3] = torch.rand((n, 3), generator=g, device=device, dtype=torch.float32)
     s[:, 3] = float((3.0 * 48.0 / (4.0 * math.pi * n)) ** (1.0 / 3.0))
     return s
+
+
+def dump_outputs(out_dir, column_densities):
+    """Write the step's result (float32, one value per ray) as out_dir/column_densities.npy.
+    Above DUMP_MAX_BYTES, one ray per stride of the batch at a seeded position inside it: the
+    same rays for the same arguments, so two builds compare value for value."""
+    vals = column_densities.detach().to(torch.float32).cpu().numpy().reshape(-1)
+    n = len(vals)
+    k = DUMP_MAX_BYTES // vals.itemsize
+    if n > k:
+        stride = n // k
+        vals = vals[np.arange(k) * stride + np.random.default_rng(0).integers(0, stride, k)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "column_densities.npy"), np.ascontiguousarray(vals))
 
 
 def _cores():
@@ -185,7 +200,13 @@ def main():
     ap.add_argument("--trusted", action="store_true",
                     help="grace_trace_set_cache_validation(0) + grace_trace_prepare_*: cached records "
                          "are used on the caller's promise, no signature pass (round 2's prepared call)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (the column "
+                         "densities of every ray, in ray order) to DIR/column_densities.npy, float32; "
+                         "above %d MB a fixed seeded sample of rays" % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -337,6 +358,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image)     # the last timed step's result, all rays
 
     # ---- kernel and call durations: HIP events, after the timed region ----------------------
     # In-library events sit directly around the traversal kernel on its stream
