@@ -185,21 +185,23 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     // 2-4x the waves, each with a tighter beam, on a chip that would otherwise sit idle.
     int width = 64;
     if (ts.width > 0) width = ts.width;
-    else if ((MODE == MODE_HITS && !hits_split) || MODE == MODE_TRI || MODE == MODE_HITS_D4)
+    else if ((MODE == MODE_HITS && !hits_split) || MODE == MODE_TRI || MODE == MODE_HITS_D4
+             || MODE == MODE_HITS_F4D)
         while (width > 16 && ceil_div(n_rays, size_t(width)) < 4096) width /= 2;
     // Hit counts and column densities split packets eight ways at most; a batch too small to fill
     // the chip even then (< 512 packets) also gets narrower packets (10^7 particles, 12288 HEALPix
     // rays: 3.5 -> 2.0 ms at 16 rays per packet; from 49152 rays on it loses: config 3 0.87 -> 0.95 ms).
-    else if ((MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4)
-             && ts.split <= 0)
+    else if ((MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4
+              || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D) && ts.split <= 0)
         while (width > 16 && ceil_div(n_rays, size_t(width)) * SUM_CLASSES < 4096) width /= 2;
     a.width = width;
     const int n_packets = ceil_div(n_rays, size_t(width));
     // Waves per packet: two resident sets of waves (2 x 8192) for small ray batches.
     int split = 1;
-    // (double4 hit counts and column densities split the same way: the same classes, summed in double)
+    // (double4 and mixed-precision hit counts and column densities split the same way: the same
+    // classes, summed in double)
     constexpr bool CLASS_SPLIT = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4
-                                  || MODE == MODE_CUM_D4);
+                                  || MODE == MODE_CUM_D4 || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D);
     if (CLASS_SPLIT) {
         // (column densities: a batch of exactly 16384 packets -- the 1024^2 frame -- still gets a
         // second wave per packet, 32768 waves; see choose_split.  Larger batches run one.)
@@ -224,6 +226,10 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         const bool fast_b = MODE == MODE_CUMULATIVE && !ts.exact_integrals;
         const bool reorder = ts.ray_reorder && n_rays > 64;
         constexpr bool D4 = (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4);
+        // Mixed precision: records of its own (kind 3, inflated for the fp64 test), derived per call
+        // like the double4 ones -- the scene cache, which holds kind 0 records, is neither read nor
+        // filled nor counted as seen, so float calls on the same arrays cache exactly as before.
+        constexpr bool F4D = (MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D || MODE == MODE_HITS_F4D);
         // ---- which cached records does this call use?  (see trace_state.hpp) -------------------
         // NONE: derive into the workspace (a scene / batch seen for the first time);  FILL: the
         // same arrays as the previous call -- derive into the cache;  CHECK: cached -- validate by
@@ -239,7 +245,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         skey.kind = MODE == MODE_TRI ? 1 : 0;
         skey.prims = a.spheres; skey.nodes = a.nodes; skey.leaves = a.leaves;
         skey.n_prims = n_spheres; skey.n_nodes = n_nodes;
-        if (!D4 && MODE != MODE_STATS) {
+        if (!D4 && !F4D && MODE != MODE_STATS) {
             scene_use = decide(ts.scene.valid && ts.scene.key == skey, ts.scene.valid && ts.scene.pinned,
                                ts.scene.seen == skey);
             ts.scene.seen = skey;
@@ -267,7 +273,8 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
                                                    + 4 * Workspace::aligned(hit_packets * 4 + 64)
                                                    + Workspace::aligned(n_rays * 4) : 0)
                                    + (MODE == MODE_CUMULATIVE ? Workspace::aligned(n_rays * SUM_CLASSES * 4) : 0)
-                                   + (MODE == MODE_CUM_D4 ? Workspace::aligned(n_rays * SUM_CLASSES * 8) : 0)
+                                   + ((MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D)
+                                      ? Workspace::aligned(n_rays * SUM_CLASSES * 8) : 0)
                                    + (reorder ? 2 * Workspace::aligned(n_rays * 4)
                                                 + sort_ws_bytes(n_rays, 4, 0) : 0)
                                    + (any_sig ? Workspace::aligned(sig_partial_words() * 8) : 0) + 1024, stream));
@@ -304,13 +311,14 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
             double* T64 = (MODE == MODE_TRI) ? Workspace::take<double>(9 * (n_spheres + 4)) : nullptr;
             int2* node_prims = Workspace::take<int2>(n_nodes);
             float4* C = Workspace::take<float4>(cluster_record_count(n_spheres));
-            GRACE_TRY(scene_fill(MODE == MODE_TRI ? 1 : D4 ? 2 : 0,
+            GRACE_TRY(scene_fill(MODE == MODE_TRI ? 1 : D4 ? 2 : F4D ? 3 : 0,
                                  D4 ? static_cast<const void*>(a.spheres_d) : a.spheres, n_spheres, a.nodes, n_nodes, a.leaves, A,
                                  fast_b ? nullptr : B, fast_b ? B : nullptr, T64, node_prims, C, stream));
             a.A = A; a.B = B; a.T64 = T64; a.node_prims = node_prims; a.C = C;
         }
         a.partial = (MODE == MODE_CUMULATIVE) ? Workspace::take<float>(n_rays * SUM_CLASSES) : nullptr;
-        a.partial_d = (MODE == MODE_CUM_D4) ? Workspace::take<double>(n_rays * SUM_CLASSES) : nullptr;
+        a.partial_d = (MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D)
+            ? Workspace::take<double>(n_rays * SUM_CLASSES) : nullptr;
         if (hits_split) {
             chunk_counts = Workspace::take<int>(n_rays * size_t(hit_chunks));
             chunk_off = Workspace::take<int>(n_rays * size_t(hit_chunks));
@@ -387,7 +395,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     a.chunk_off = chunk_off;
     a.wave_map = wave_map;
     a.n_wave_map = n_wave_map;
-    if (split > 1 && (MODE == MODE_COUNT || MODE == MODE_COUNT_D4))
+    if (split > 1 && (MODE == MODE_COUNT || MODE == MODE_COUNT_D4 || MODE == MODE_COUNT_F4D))
         GRACE_TRY_HIP(hipMemsetAsync(a.out_counts, 0, n_rays * sizeof(int), stream));
     if (keep_chunks && split > 1) {
         a.chunk_counts = ts.hits.chunk_counts;
@@ -504,7 +512,8 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         if (split > 1) both(M_(), T(), F(), a);
         else if (lat_split) GRACE_TRY(one_or_split(F()));
         else both(M_(), F(), F(), a);
-    } else if constexpr (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4) {
+    } else if constexpr (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4 || MODE == MODE_COUNT_F4D
+                         || MODE == MODE_CUM_F4D) {
         if (split > 1) trace_kernel<MODE, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);
         else trace_kernel<MODE, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
     } else {
@@ -512,7 +521,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     }
     GRACE_CHECK_LAUNCH();
     GRACE_TRY(stamps_report(MODE));
-    if (MODE == MODE_CUM_D4 && split > 1) {
+    if ((MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D) && split > 1) {
         combine_classes_kernel<double><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial_d, int(n_rays), split,
                                                                                    nullptr, a.out_sums_d);
         GRACE_CHECK_LAUNCH();
@@ -709,6 +718,60 @@ grace_status grace_trace_hits_d4(const void* d_rays, size_t n_rays, const double
 }
 
 grace_status grace_trace_status_d4(grace_stream stream) { return grace_trace_status(stream); }
+
+// ---- float4 spheres, double outputs (Real4 = float4, Real = double) ---------------------------
+static TraceArgs f4d_args(const void* d_rays, const float* d_spheres, const int* d_nodes,
+                          const int* d_leaves, const int* d_root)
+{
+    TraceArgs a = {};
+    a.rays = static_cast<const float*>(d_rays);
+    a.spheres = reinterpret_cast<const float4*>(d_spheres);
+    a.nodes = reinterpret_cast<const float4*>(d_nodes);
+    a.leaves = reinterpret_cast<const int4*>(d_leaves);
+    a.root = d_root;
+    return a;
+}
+
+grace_status grace_trace_hitcounts_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                          size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                          const int* d_leaves, const int* d_root, int* d_hit_counts,
+                                          grace_stream stream)
+{
+    if (n_rays == 0) return GRACE_OK;
+    GRACE_REQUIRE(d_hit_counts, "trace_hitcounts (float4, double): null output");
+    TraceArgs a = f4d_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.out_counts = d_hit_counts;
+    return launch_trace<MODE_COUNT_F4D>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
+}
+
+grace_status grace_trace_cumulative_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                           size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                           const int* d_leaves, const int* d_root, double* d_sums,
+                                           grace_stream stream)
+{
+    if (n_rays == 0) return GRACE_OK;
+    GRACE_REQUIRE(d_sums, "trace_cumulative (float4, double): null output");
+    TraceArgs a = f4d_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.out_sums_d = d_sums;
+    return launch_trace<MODE_CUM_F4D>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
+}
+
+grace_status grace_trace_hits_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                     size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                     const int* d_leaves, const int* d_root, const int* d_ray_offsets,
+                                     int* d_hit_indices, double* d_hit_integrals,
+                                     double* d_hit_distances, grace_stream stream)
+{
+    if (n_rays == 0) return GRACE_OK;
+    GRACE_REQUIRE(d_ray_offsets && d_hit_indices && d_hit_integrals && d_hit_distances,
+                  "trace_hits (float4, double): null output");
+    TraceArgs a = f4d_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.offsets = d_ray_offsets;
+    a.hit_idx = d_hit_indices;
+    a.hit_integral_d = d_hit_integrals;
+    a.hit_dist_d = d_hit_distances;
+    return launch_trace<MODE_HITS_F4D>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
+}
 
 grace_status grace_trace_stats_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
                                   size_t n_spheres, const int* d_nodes, size_t n_nodes,

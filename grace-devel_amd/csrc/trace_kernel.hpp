@@ -367,7 +367,8 @@ void trace_kernel(const TraceArgs a)
     // Per-wave tile of the candidates of the current culling round (MODE_TRI keeps its
     // fp64 triangles on the scalar path).
     constexpr bool D4 = (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4);
-    constexpr bool LDS_TILE = (MODE != MODE_TRI && !D4);
+    constexpr bool F4D = (MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D || MODE == MODE_HITS_F4D);
+    constexpr bool LDS_TILE = (MODE != MODE_TRI && !D4 && !F4D);
     // Three 8-byte planes per wave -- (x, y), (z, h^2), (1/h terms) -- so that one address
     // (plane base + 8 j) serves all of a survivor's reads through immediate offsets.
     // (66 slots: the survivor loop reads up to two slots past the round's last survivor)
@@ -375,9 +376,13 @@ void trace_kernel(const TraceArgs a)
     // *_D4 modes: the round's candidates as doubles, lane-indexed: {x, y, z, w w, 1/w, (1/w)^2}
     // (the division is done once per candidate by its lane, not once per survivor by the wave).
     __shared__ double s_tile_d[D4 ? TRACE_BLOCK / 64 : 1][D4 ? 64 : 1][D4 ? 6 : 1];
+    // *_F4D modes: the same, from the caller's float4 record, as floats: {x, y, z, fl(w w)},
+    // {fl(1/w), fl(fl(1/w)^2), -, -} -- every value the reference forms in float before widening.
+    __shared__ float4 s_tile_f[F4D ? TRACE_BLOCK / 64 : 1][F4D ? 64 : 1][F4D ? 2 : 1];
     const int lane = threadIdx.x & 63;
     constexpr bool SPLITTABLE = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_HITS
-                                 || MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4);
+                                 || MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4
+                                 || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D);
     static_assert(!SPLIT || SPLITTABLE, "triangle and stats walks do not split");
     // Hit counts and column densities split a packet by summation class (interleaved granules);
     // the per-hit trace, whose output is ordered, by contiguous chunk ranges chosen per packet.
@@ -395,7 +400,8 @@ void trace_kernel(const TraceArgs a)
     const int vblock = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + slot;
     const int wave_id = __builtin_amdgcn_readfirstlane(vblock * (TRACE_BLOCK / 64)
                                                        + (threadIdx.x >> 6));
-    if (MODE == MODE_CUMULATIVE || MODE == MODE_HITS || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4) {
+    if (MODE == MODE_CUMULATIVE || MODE == MODE_HITS || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4
+        || MODE == MODE_CUM_F4D || MODE == MODE_HITS_F4D) {
         if (FAST) {
             static_assert(TRACE_BLOCK >= 256, "one table entry per thread");
             float2 e = make_float2(0.f, 0.f);
@@ -461,7 +467,7 @@ void trace_kernel(const TraceArgs a)
 
     // Axis-aligned packet?  (wave-uniform; tail lanes replicate a valid ray)
     int axis = -1;
-    if (MODE != MODE_HITS && MODE != MODE_TRI && MODE != MODE_HITS_D4) {
+    if (MODE != MODE_HITS && MODE != MODE_TRI && MODE != MODE_HITS_D4 && MODE != MODE_HITS_F4D) {
         const unsigned long long all = ~0ull;
         const bool zx = dx == 0.f, zy = dy == 0.f, zz = dz == 0.f;
         if (__builtin_amdgcn_ballot_w64(zy && zz && fabsf(dx) == 1.f) == all) axis = 0;
@@ -612,8 +618,8 @@ void trace_kernel(const TraceArgs a)
     int count_at_chunk = 0;
     float sum = 0.f;        // accumulator of the current granule's class (MODE_CUMULATIVE)
     // Class accumulators of this wave's lanes (one wave = one row of the workgroup's array).
-    // (MODE_CUM_D4: the same classes, accumulated and combined in double)
-    constexpr bool CLASSES_F = (MODE == MODE_CUMULATIVE), CLASSES_D = (MODE == MODE_CUM_D4);
+    // (MODE_CUM_D4, MODE_CUM_F4D: the same classes, accumulated and combined in double)
+    constexpr bool CLASSES_F = (MODE == MODE_CUMULATIVE), CLASSES_D = (MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D);
     constexpr bool CLASSES = CLASSES_F || CLASSES_D;
     __shared__ float s_class[CLASSES_F ? TRACE_BLOCK / 64 : 1][CLASSES_F ? SUM_CLASSES : 1][CLASSES_F ? 64 : 1];
     __shared__ double s_class_d[CLASSES_D ? TRACE_BLOCK / 64 : 1][CLASSES_D ? SUM_CLASSES : 1][CLASSES_D ? 64 : 1];
@@ -626,7 +632,7 @@ void trace_kernel(const TraceArgs a)
 #pragma unroll
         for (int c = 0; c < SUM_CLASSES; ++c) s_class_d[wv_acc][c][lane] = 0.0;
     }
-    double sum_d = 0.0;     // MODE_CUM_D4: accumulator of the current granule's class
+    double sum_d = 0.0;     // MODE_CUM_D4 / _F4D: accumulator of the current granule's class
     int cur_granule = -1;            // wave-uniform
     int cur_granule_end = 0;         // first primitive past the current granule
     bool cur_owned = true;
@@ -652,7 +658,7 @@ void trace_kernel(const TraceArgs a)
     int tri_data = -1;
     float tri_tmin = len * (1.f + 0.000001f);
     const double ddx = dx, ddy = dy, ddz = dz;
-    if (MODE == MODE_HITS || MODE == MODE_HITS_D4) write_at = a.offsets[ray_index];
+    if (MODE == MODE_HITS || MODE == MODE_HITS_D4 || MODE == MODE_HITS_F4D) write_at = a.offsets[ray_index];
     const double rdx = dx, rdy = dy, rdz = dz;
     // MODE_HITS: every ray owns a contiguous output segment, so lanes writing hit by hit
     // touch 64 different cache lines per store and the partial lines thrash L2 (measured:
@@ -737,7 +743,7 @@ void trace_kernel(const TraceArgs a)
     // like the walk and the cluster tests: a group is dropped only if no ray of the packet can
     // hit any member, so the per-ray hit sets, and with them every sum, are unchanged.
     constexpr bool FLAT_OK = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4
-                              || MODE == MODE_CUM_D4);
+                              || MODE == MODE_CUM_D4 || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D);
     // Only packets whose group test is sharp: axis-aligned ones (origin rectangle) and pencils
     // (one origin: the bundle's side planes).  A GENERAL packet's beam -- boxes around its origins
     // and directions -- keeps nearly every group, where the walk's per-ray slab tests prune
@@ -941,7 +947,8 @@ void trace_kernel(const TraceArgs a)
             const int c_first = r_lo >> 6, c_last = (r_hi - 1) >> 6;
             // Lane j's candidate of cluster c: primitive 64 c + j, clamped into the range (idle
             // lanes then hold a valid candidate and the tests need no control flow).
-            double4 mined_next = make_double4(0., 0., 0., 0.);   // *_D4: the candidate's double4 record
+            // *_D4: the candidate's double4 record; *_F4D: the caller's float4 record, widened (exact)
+            double4 mined_next = make_double4(0., 0., 0., 0.);
             // (Round 3, measured and rejected: buffer loads for the candidates -- a resource based at
             // the range's first cluster, the cluster as scalar offset, the lane as constant vector
             // offset: no per-round address arithmetic (six vector instructions) and no clamps, the
@@ -952,6 +959,10 @@ void trace_kernel(const TraceArgs a)
                 m4 = a.A[pj];
                 if (LDS_TILE && NEED_B) m2 = a.B[pj];
                 if (D4) mined_next = reinterpret_cast<const double4*>(a.spheres_d)[pj];
+                if (F4D) {
+                    const float4 f = a.spheres[pj];
+                    mined_next = make_double4(f.x, f.y, f.z, f.w);
+                }
             };
             // The range's clusters, 64 at a time: lane j decides for cluster cg + j whether ANY ray
             // of the packet can hit ANY of its members (cluster_may_hit); culling rounds then run
@@ -1103,6 +1114,12 @@ void trace_kernel(const TraceArgs a)
                     t[3] = mined.w * mined.w;                         // generic/intersect.h:37
                     t[4] = ir; t[5] = ir * ir;
                 }
+                if (F4D) {
+                    const float4 f = make_float4(float(mined.x), float(mined.y), float(mined.z), float(mined.w));
+                    const float ir = 1.f / f.w;                       // functors/trace.cuh:181, in float
+                    s_tile_f[wv][lane][0] = make_float4(f.x, f.y, f.z, f.w * f.w);   // intersect.h:37, in float
+                    s_tile_f[wv][lane][F4D ? 1 : 0] = make_float4(ir, ir * ir, 0.f, 0.f);
+                }
                 const unsigned long long todo = rest;
                 STAMP_ADD(st_cull, st_t2);
                 const unsigned long long st_t3 = STAMP_NOW(); (void)st_t3;
@@ -1159,6 +1176,64 @@ void trace_kernel(const TraceArgs a)
                                 a.hit_dist_d[write_at] = dot_p;
                                 ++write_at;
                             }
+                        }
+                    } else if constexpr (F4D) {
+                        // sphere_hit<float4, double> (generic/intersect.h:16-54): p = s - o is a FLOAT
+                        // subtraction, widened; r widened; dot_p, b and b2 in double; the radius test
+                        // against the float product w * w, widened.
+                        const float4 r0 = s_tile_f[wv][jj - pbase][0], r1 = s_tile_f[wv][jj - pbase][F4D ? 1 : 0];
+                        double dot_p, b2;
+                        if (AX >= 0) {
+                            // Axis-aligned packet (d = +-e_AX exactly, no per-hit outputs): the general
+                            // form below collapses in double as it does for double4 spheres -- the
+                            // products with a zero direction component are +-0 and leave the sums
+                            // unchanged, dot = p_a d_a exactly, b_a = p_a - (p_a d_a) d_a = 0, and b2
+                            // adds the two perpendicular squares with a zero in the same place --, where
+                            // p is the same fl32(s - o) in each form.
+                            const float sa = AX == 0 ? r0.x : AX == 1 ? r0.y : r0.z;
+                            const float s1 = AX == 0 ? r0.y : r0.x;
+                            const float s2 = AX == 2 ? r0.y : r0.z;
+                            const double q1 = s1 - o1, q2 = s2 - o2;
+                            dot_p = double(sa - oa) * double(da);
+                            b2 = q1 * q1 + q2 * q2;
+                        } else {
+                            const double px = r0.x - ox, py = r0.y - oy, pz = r0.z - oz;
+                            dot_p = px * rdx + py * rdy + pz * rdz;
+                            const double bx = px - dot_p * rdx, by = py - dot_p * rdy, bz = pz - dot_p * rdz;
+                            b2 = bx * bx + by * by + bz * bz;
+                        }
+                        const bool hit = !(b2 >= double(r0.w)) && !(dot_p < 0.0f) && !(dot_p >= len);
+                        if (MODE == MODE_COUNT_F4D) {
+                            count += hit ? 1 : 0;
+                        } else if (hit && MODE == MODE_CUM_F4D) {
+                            // OnHit_sphere_cumulate with Real4 = float4 (functors/trace.cuh:164-186): Real
+                            // is float -- b = float(50 (sqrt(b2) ir)), lerp<float> over the double table
+                            // (its fma in double, narrowed), integral *= ir ir in float -- and the
+                            // accumulator is the double RayData (data += integral).
+                            const float b = float((N_TABLE - 1) * (sqrt(b2) * double(r1.x)));
+                            int x_idx = static_cast<int>(b);
+                            // t = double(b) - x_idx, formed exactly in float (b < 64) and widened, as
+                            // in hit_integral
+                            float t = b - static_cast<float>(x_idx);
+                            if (x_idx >= N_TABLE - 1) { t = 1.0f; x_idx = N_TABLE - 2; }
+                            const double2 y = s_lut[x_idx];
+                            float integral = static_cast<float>(__builtin_fma(double(t), y.y, y.x));
+                            integral *= r1.y;
+                            sum_d += integral;
+                        } else if (hit && valid) {
+                            // OnHit_sphere_individual<int, double> (functors/trace.cuh:196-235):
+                            // ir = 1.f / w divided in float, everything after it in double.
+                            const double ir = r1.x;
+                            double x = (N_TABLE - 1) * (sqrt(b2) * ir);
+                            int x_idx = static_cast<int>(x);
+                            if (x_idx >= N_TABLE - 1) { x = double(N_TABLE - 1); x_idx = N_TABLE - 2; }
+                            const double2 y = s_lut[x_idx];
+                            double integral = __builtin_fma(x - x_idx, y.y, y.x);
+                            integral *= ir * ir;
+                            a.hit_idx[write_at] = jj;
+                            a.hit_integral_d[write_at] = integral;
+                            a.hit_dist_d[write_at] = dot_p;
+                            ++write_at;
                         }
                     } else if (MODE == MODE_TRI) {
                         // RayIntersect_tri + OnHit_tri (tris_trace.cuh:24-61)
@@ -1258,7 +1333,7 @@ void trace_kernel(const TraceArgs a)
                         // Keep the reads here -- ahead of the survivors in between -- instead of
                         // letting the scheduler sink them next to their use.
                         __builtin_amdgcn_sched_barrier(0);
-                    } else if (!D4) {
+                    } else if (!D4 && !F4D) {
                         c = a.A[jj];
                     }
                 };
@@ -1378,11 +1453,11 @@ void trace_kernel(const TraceArgs a)
         else if (count) atomicAdd(&a.out_counts[ray_index], count); // output zeroed by the host
     }
     if (MODE == MODE_TRI) a.out_counts[ray_index] = tri_data;
-    if (MODE == MODE_COUNT_D4) {
+    if (MODE == MODE_COUNT_D4 || MODE == MODE_COUNT_F4D) {
         if (!SPLIT) a.out_counts[ray_index] = count;
         else if (count) atomicAdd(&a.out_counts[ray_index], count); // output zeroed by the host
     }
-    if (MODE == MODE_CUM_D4) {
+    if (MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D) {
         // the float path's class-ordered sum, in double: pairwise over the 8 classes (this wave's
         // subtree of it when the packet is split)
         if (cur_granule >= 0) s_class_d[wv_acc][cur_granule & (SUM_CLASSES - 1)][lane] = sum_d;

@@ -124,6 +124,37 @@ __global__ __launch_bounds__(256) void trace_prepass_d4_kernel(const double* __r
     }
 }
 
+// float4 spheres under the fp64 test (mixed precision, sphere_hit<float4, double>): the survivor
+// test forms q = fl32(s - o) exactly as the float test does, then b2 in double, against fl32(w w).
+// It accepts near-tangent pairs the float test rejects (its b2 is not rounded up past fl32(w w)),
+// so the culls must run on a record whose r^2 exceeds fl32(w w) by more than the float culls' own
+// rounding of the same q: r^2 = w^2 (1 + 2^-16), widened, squared and narrowed (fl32(w w) <= w^2
+// (1 + 2^-24); the narrowing rounds by 2^-24).  Then
+//   * the exact culls of axis-aligned packets (rectangle, lattice: the rays' own q and the float
+//     expression fl(fl(q1^2) + fl(q2^2)) <= (q1^2 + q2^2)(1 + 3 * 2^-24) at the nearest origin)
+//     keep every sphere whose double q1^2 + q2^2 < fl32(w w): r^2 / fl32(w w) >= 1 + 2^-16 - 2^-23,
+//     against rounding below 2^-22;
+//   * the general and pencil culls bound the EXACT impact parameter with margins (2^-18 |p|^2,
+//     1e-5 relative) that already cover the float test's error in b2, which includes the same
+//     fl32(s - o) as here; the fp64 b2 of that q carries strictly less error;
+//   * cluster and group boxes contain [c - r, c + r] of these records: a hit needs |s - o| <=
+//     |q| (1 + 2^-24) < r in each perpendicular co-ordinate.
+// Centres are the caller's floats, not narrowed: no co-ordinate term (cf. the double4 records).
+__global__ __launch_bounds__(256) void trace_prepass_f4d_kernel(const float4* __restrict__ spheres,
+                                                                size_t n, float4* __restrict__ A)
+{
+    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n + 4;
+         i += size_t(gridDim.x) * blockDim.x) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < n) {
+            const float4 s = spheres[i];
+            const double w = s.w;
+            a = make_float4(s.x, s.y, s.z, float(w * w * (1.0 + 1.52587890625e-05 /* 2^-16 */)));
+        }
+        A[i] = a;
+    }
+}
+
 // ---- cluster boxes ---------------------------------------------------------------------------
 // Primitives are Morton-sorted, so 64 consecutive ones (a CLUSTER: indices [64 c, 64 c + 64)) are
 // a compact clump about as wide as a smoothing length.  One box per cluster -- the union of
@@ -311,6 +342,10 @@ grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float
     } else if (kind == 2) {
         trace_prepass_d4_kernel<<<stream_grid(n_prims + 4, 256), 256, 0, stream>>>(
             static_cast<const double*>(prims), n_prims, A);
+        GRACE_CHECK_LAUNCH();
+    } else if (kind == 3) {
+        trace_prepass_f4d_kernel<<<stream_grid(n_prims + 4, 256), 256, 0, stream>>>(
+            static_cast<const float4*>(prims), n_prims, A);
         GRACE_CHECK_LAUNCH();
     } else {
         // (+ the cluster boxes: fused)

@@ -45,7 +45,12 @@ enum { MODE_COUNT = 0, MODE_CUMULATIVE = 1, MODE_HITS = 2, MODE_STATS = 3, MODE_
        // Real4 = double4, Real = double (trace_sph.cuh:57-241 instantiated in double): the walk and
        // every cull run on float records that CONTAIN the double spheres; each survivor is then
        // tested and integrated in double against the caller's double4 record.
-       MODE_COUNT_D4 = 5, MODE_CUM_D4 = 6, MODE_HITS_D4 = 7 };
+       MODE_COUNT_D4 = 5, MODE_CUM_D4 = 6, MODE_HITS_D4 = 7,
+       // Real4 = float4, Real = double (mixed precision): the same walk on float records that
+       // contain every sphere the fp64 test can accept (trace_prepass_f4d_kernel); each survivor is
+       // tested in double from the caller's float4 record, its per-hit terms follow the reference's
+       // promotions for that pair, and column densities are the class-ordered double sum.
+       MODE_COUNT_F4D = 8, MODE_CUM_F4D = 9, MODE_HITS_F4D = 10 };
 
 struct TraceArgs {
     const float* rays;      // 7 floats per ray
@@ -62,8 +67,8 @@ struct TraceArgs {
                             // the box of the member spheres, slightly inflated (cluster_boxes_kernel)
     const double* T64;      // MODE_TRI pre-pass: {v, e1, e2} widened to fp64, 9 per triangle
     const double* spheres_d; // *_D4 modes: the caller's double4 spheres
-    double* out_sums_d;      // MODE_CUM_D4
-    double* hit_integral_d;  // MODE_HITS_D4
+    double* out_sums_d;      // MODE_CUM_D4, MODE_CUM_F4D
+    double* hit_integral_d;  // MODE_HITS_D4, MODE_HITS_F4D
     double* hit_dist_d;
     int split;              // waves per packet (1, 2, 4, 8); each owns SUM_CLASSES / split classes
     int n_prims;
@@ -228,7 +233,7 @@ grace_status scene_release(TraceState& ts);
 // Buffers of the scene cache for `key` (replaces whatever is cached).
 grace_status scene_cache_alloc(TraceState& ts, const SceneKey& key);
 // Fills the scene-constant arrays (any of B1 / B50 / T64 may be null).  kind: 0 float4 spheres,
-// 1 triangles, 2 double4 spheres.  run_if (device, optional): every kernel returns at once if
+// 1 triangles, 2 double4 spheres, 3 float4 spheres under the fp64 test (mixed precision).  run_if (device, optional): every kernel returns at once if
 // *run_if == 0.
 grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float4* nodes,
                         size_t n_nodes, const int4* leaves, float4* A, float2* B1, float2* B50,

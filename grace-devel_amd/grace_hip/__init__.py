@@ -424,12 +424,29 @@ def trace_release():
     _prepared.pop("scene", None)
 
 
-def _trace_hitcounts_keep(rays, spheres, tree, hit_counts):
+def _trace_hitcounts_keep(rays, spheres, tree, hit_counts, real=torch.float32):
     """The hit-count pass of trace_sph / trace_with_sentinels_sph: for small batches the library
-    keeps the hits per (ray, primitive chunk) for the per-hit pass that follows."""
+    keeps the hits per (ray, primitive chunk) for the per-hit pass that follows.  real=float64:
+    the mixed-precision pass, counted with the fp64 test its per-hit pass applies."""
     _check_rays(rays)
-    _check(_lib.grace_trace_hitcounts_keep_f4(*_trace_args(rays, spheres, tree), _ptr(hit_counts),
-                                              _stream()))
+    fn = _lib.grace_trace_hitcounts_f4_f64 if real == torch.float64 else _lib.grace_trace_hitcounts_keep_f4
+    _check(fn(*_trace_args(rays, spheres, tree), _ptr(hit_counts), _stream()))
+    return hit_counts
+
+
+def _real_of(real):
+    assert real in (torch.float32, torch.float64), "real: torch.float32 or torch.float64"
+    return real
+
+
+def trace_hitcounts_f4_f64(rays, spheres, tree, hit_counts, check=False):
+    """Hit counts under sphere_hit<float4, double> (the fp64 test on float spheres): the counts
+    of the mixed-precision trace_sph.  trace_hitcounts_sph keeps the float test."""
+    _check_rays(rays)
+    assert hit_counts.dtype == torch.int32 and len(hit_counts) == len(rays)
+    _check(_lib.grace_trace_hitcounts_f4_f64(*_trace_args(rays, spheres, tree), _ptr(hit_counts), _stream()))
+    if check:
+        trace_status()
     return hit_counts
 
 
@@ -448,11 +465,13 @@ def trace_hitcounts_sph(rays, spheres, tree, hit_counts, check=False):
 
 def trace_cumulative_sph(rays, spheres, tree, cumulated, check=False):
     """trace_sph.cuh:82-110.  Asynchronous by default (the bench's timed loop relies on it);
-    check=True reads the status word after the launch, as the C++ mirrors do."""
+    check=True reads the status word after the launch, as the C++ mirrors do.  cumulated.dtype
+    picks Real: float32 (Real4 = float4, Real = float) or float64 (the mixed-precision
+    trace_cumulative_sph<float4, double>: fp64 sphere test, double class-ordered sums)."""
     _check_rays(rays)
-    assert cumulated.dtype == torch.float32 and len(cumulated) == len(rays)
-    _check(_lib.grace_trace_cumulative_f4(*_trace_args(rays, spheres, tree), _ptr(cumulated),
-                                          _stream()))
+    assert cumulated.dtype in (torch.float32, torch.float64) and len(cumulated) == len(rays)
+    fn = _lib.grace_trace_cumulative_f4_f64 if cumulated.dtype == torch.float64 else _lib.grace_trace_cumulative_f4
+    _check(fn(*_trace_args(rays, spheres, tree), _ptr(cumulated), _stream()))
     if check:
         trace_status()
     return cumulated
@@ -472,44 +491,56 @@ def _offsets_from_counts(offsets, extra=0):
     return total
 
 
-def trace_sph(rays, spheres, tree):
+def trace_sph(rays, spheres, tree, real=torch.float32):
     """trace_sph.cuh:112-168: returns (ray_offsets, hit_indices, hit_integrals,
-    hit_distances); the reference resizes the three per-hit vectors to the total."""
+    hit_distances); the reference resizes the three per-hit vectors to the total.  real is the
+    Real of the integrals and distances: float32, or float64 for trace_sph<float4, int, double>."""
     _check_rays(rays)
+    real = _real_of(real)
     n = len(rays)
     offsets = torch.empty(n, dtype=torch.int32, device=rays.device)
-    _trace_hitcounts_keep(rays, spheres, tree, offsets)
+    _trace_hitcounts_keep(rays, spheres, tree, offsets, real)
     total = _offsets_from_counts(offsets)
     idx = torch.empty(total, dtype=torch.int32, device=rays.device)
-    integrals = torch.empty(total, dtype=torch.float32, device=rays.device)
-    dists = torch.empty(total, dtype=torch.float32, device=rays.device)
+    integrals = torch.empty(total, dtype=real, device=rays.device)
+    dists = torch.empty(total, dtype=real, device=rays.device)
     if total == 0:             # no ray hits anything: empty outputs, like the reference's resize(0)
         return offsets, idx, integrals, dists
-    _check(_lib.grace_trace_hits_f4(*_trace_args(rays, spheres, tree), _ptr(offsets), _ptr(idx),
-                                    _ptr(integrals), _ptr(dists), _stream()))
+    fn = _lib.grace_trace_hits_f4_f64 if real == torch.float64 else _lib.grace_trace_hits_f4
+    _check(fn(*_trace_args(rays, spheres, tree), _ptr(offsets), _ptr(idx), _ptr(integrals), _ptr(dists),
+              _stream()))
     trace_status()
     return offsets, idx, integrals, dists
 
 
 def trace_with_sentinels_sph(rays, spheres, tree, index_sentinel, integral_sentinel,
-                             distance_sentinel):
+                             distance_sentinel, real=torch.float32):
     """trace_sph.cuh:171-241: like trace_sph, but every ray's segment ends with one sentinel
-    slot; returns (ray_offsets, hit_indices, hit_integrals, hit_distances)."""
+    slot; returns (ray_offsets, hit_indices, hit_integrals, hit_distances).  real as for
+    trace_sph."""
     _check_rays(rays)
+    real = _real_of(real)
     n = len(rays)
     offsets = torch.empty(n, dtype=torch.int32, device=rays.device)
-    _trace_hitcounts_keep(rays, spheres, tree, offsets)
+    _trace_hitcounts_keep(rays, spheres, tree, offsets, real)
     total = _offsets_from_counts(offsets, extra=n) + n
     _check(_lib.grace_add_iota_i32(_ptr(offsets), C.c_size_t(n), _stream()))
     idx = torch.empty(total, dtype=torch.int32, device=rays.device)
-    integrals = torch.empty(total, dtype=torch.float32, device=rays.device)
-    dists = torch.empty(total, dtype=torch.float32, device=rays.device)
-    bits = lambda f: int(np.float32(f).view(np.uint32))
     _check(_lib.grace_fill_u32(_ptr(idx), C.c_size_t(total), C.c_uint32(index_sentinel & 0xFFFFFFFF), _stream()))
-    _check(_lib.grace_fill_u32(_ptr(integrals), C.c_size_t(total), C.c_uint32(bits(integral_sentinel)), _stream()))
-    _check(_lib.grace_fill_u32(_ptr(dists), C.c_size_t(total), C.c_uint32(bits(distance_sentinel)), _stream()))
-    _check(_lib.grace_trace_hits_f4(*_trace_args(rays, spheres, tree), _ptr(offsets), _ptr(idx),
-                                    _ptr(integrals), _ptr(dists), _stream()))
+    if real == torch.float64:
+        # (64-bit sentinels: a tensor fill)
+        integrals = torch.full((total,), float(integral_sentinel), dtype=real, device=rays.device)
+        dists = torch.full((total,), float(distance_sentinel), dtype=real, device=rays.device)
+        fn = _lib.grace_trace_hits_f4_f64
+    else:
+        integrals = torch.empty(total, dtype=torch.float32, device=rays.device)
+        dists = torch.empty(total, dtype=torch.float32, device=rays.device)
+        bits = lambda f: int(np.float32(f).view(np.uint32))
+        _check(_lib.grace_fill_u32(_ptr(integrals), C.c_size_t(total), C.c_uint32(bits(integral_sentinel)), _stream()))
+        _check(_lib.grace_fill_u32(_ptr(dists), C.c_size_t(total), C.c_uint32(bits(distance_sentinel)), _stream()))
+        fn = _lib.grace_trace_hits_f4
+    _check(fn(*_trace_args(rays, spheres, tree), _ptr(offsets), _ptr(idx), _ptr(integrals), _ptr(dists),
+              _stream()))
     trace_status()
     return offsets, idx, integrals, dists
 

@@ -10,7 +10,9 @@
 //                            RayEntry_from_array + OnHit_sphere_individual       -> grace_trace_hits_*
 //   trace_with_sentinels_sph the same with one sentinel slot per ray
 //
-// (Real4, Real) is (float4, float) or (double4, double); IndexType is a 32-bit integer.  Per-ray
+// (Real4, Real) is (float4, float), (double4, double) or (float4, double) -- float spheres under the
+// fp64 test with double sums and per-hit outputs, the reference's promotions for that pair --;
+// (double4, float) is refused at compile time.  IndexType is a 32-bit integer.  Per-ray
 // results equal the brute-force loop over all spheres (the reference's own criterion,
 // tests/tree_traversal); column densities are the class-ordered fp32 sum documented in
 // grace_hip.h (within 1e-6 of the reference's single running sum).  As in the reference the
@@ -22,6 +24,7 @@
 #include "grace/ray.h"
 
 #include <limits>
+#include <type_traits>
 
 namespace grace {
 
@@ -77,15 +80,25 @@ inline void hitcounts_dispatch(const Ray* r, size_t nr, const double4* s, size_t
 { GRACE_STATUS_CHECK(grace_trace_hitcounts_d4(r, nr, reinterpret_cast<const double*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, out, NULL)); }
 
 // The hit-count pass of trace_sph: the library keeps what the per-hit pass can reuse.
-inline void hitcounts_keep_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t, int* out)
+// The last argument names Real: the counts must come from the test the per-hit pass applies.
+inline void hitcounts_keep_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t, int* out,
+                                    const float*)
 { GRACE_STATUS_CHECK(grace_trace_hitcounts_keep_f4(r, nr, reinterpret_cast<const float*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, out, NULL)); }
-inline void hitcounts_keep_dispatch(const Ray* r, size_t nr, const double4* s, size_t n, const TreeArgs& t, int* out)
+inline void hitcounts_keep_dispatch(const Ray* r, size_t nr, const double4* s, size_t n, const TreeArgs& t, int* out,
+                                    const double*)
 { hitcounts_dispatch(r, nr, s, n, t, out); }
+// (float4, double): the fp64 test in both passes, so offsets and written hits always agree (the
+// reference sizes with the float test here)
+inline void hitcounts_keep_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t, int* out,
+                                    const double*)
+{ GRACE_STATUS_CHECK(grace_trace_hitcounts_f4_f64(r, nr, reinterpret_cast<const float*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, out, NULL)); }
 
 inline void cumulative_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t, float* out)
 { GRACE_STATUS_CHECK(grace_trace_cumulative_f4(r, nr, reinterpret_cast<const float*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, out, NULL)); }
 inline void cumulative_dispatch(const Ray* r, size_t nr, const double4* s, size_t n, const TreeArgs& t, double* out)
 { GRACE_STATUS_CHECK(grace_trace_cumulative_d4(r, nr, reinterpret_cast<const double*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, out, NULL)); }
+inline void cumulative_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t, double* out)
+{ GRACE_STATUS_CHECK(grace_trace_cumulative_f4_f64(r, nr, reinterpret_cast<const float*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, out, NULL)); }
 
 inline void hits_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t,
                           const int* off, int* idx, float* integrals, float* dists)
@@ -93,6 +106,20 @@ inline void hits_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, co
 inline void hits_dispatch(const Ray* r, size_t nr, const double4* s, size_t n, const TreeArgs& t,
                           const int* off, int* idx, double* integrals, double* dists)
 { GRACE_STATUS_CHECK(grace_trace_hits_d4(r, nr, reinterpret_cast<const double*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, off, idx, integrals, dists, NULL)); }
+inline void hits_dispatch(const Ray* r, size_t nr, const float4* s, size_t n, const TreeArgs& t,
+                          const int* off, int* idx, double* integrals, double* dists)
+{ GRACE_STATUS_CHECK(grace_trace_hits_f4_f64(r, nr, reinterpret_cast<const float*>(s), n, t.nodes, t.n_nodes, t.leaves, t.root, off, idx, integrals, dists, NULL)); }
+
+// double4 spheres with float outputs: the reference compiles them (fp64 test, fp32 sums); this
+// library does not provide that pairing -- a clear refusal instead of an overload-resolution error.
+template <typename Real4, typename Real>
+struct sph_precision_check
+{
+    static_assert(!(std::is_same<Real4, double4>::value && std::is_same<Real, float>::value),
+                  "grace: double4 spheres with float outputs are not supported; use double outputs "
+                  "(or float4 spheres with float or double outputs)");
+    static const bool ok = true;
+};
 
 // The traversal's status word: the reference asserts on stack exhaustion in GRACE_DEBUG builds
 // (bintree_trace.cuh:164); here it is an error in every build.
@@ -148,6 +175,7 @@ GRACE_HOST void trace_cumulative_sph(
     const Tree& d_tree,
     thrust::device_vector<Real>& d_cumulated)
 {
+    static_assert(detail::sph_precision_check<Real4, Real>::ok, "");
     detail::check_ray_count(d_rays.size());
     detail::cumulative_dispatch(detail::raw(d_rays), d_rays.size(), detail::raw(d_spheres),
                                 d_spheres.size(), detail::tree_args(d_tree), detail::raw(d_cumulated));
@@ -166,10 +194,12 @@ GRACE_HOST void trace_sph(
     thrust::device_vector<Real>& d_hit_distances)
 {
     static_assert(sizeof(IndexType) == sizeof(int), "IndexType must be a 32-bit integer");
+    static_assert(detail::sph_precision_check<Real4, Real>::ok, "");
     // Initially, d_ray_offsets is actually per-ray *hit counts*.
     detail::check_ray_count(d_rays.size());
     detail::hitcounts_keep_dispatch(detail::raw(d_rays), d_rays.size(), detail::raw(d_spheres),
-                                    d_spheres.size(), detail::tree_args(d_tree), detail::raw(d_ray_offsets));
+                                    d_spheres.size(), detail::tree_args(d_tree), detail::raw(d_ray_offsets),
+                                    static_cast<const Real*>(NULL));
     const size_t total_hits = detail::counts_to_offsets(d_ray_offsets, 0);
 
     d_hit_integrals.resize(total_hits);
@@ -198,10 +228,12 @@ GRACE_HOST void trace_with_sentinels_sph(
     const Real distance_sentinel)
 {
     static_assert(sizeof(IndexType) == sizeof(int), "IndexType must be a 32-bit integer");
+    static_assert(detail::sph_precision_check<Real4, Real>::ok, "");
     const size_t n_rays = d_rays.size();
     detail::check_ray_count(n_rays);
     detail::hitcounts_keep_dispatch(detail::raw(d_rays), n_rays, detail::raw(d_spheres),
-                                    d_spheres.size(), detail::tree_args(d_tree), detail::raw(d_ray_offsets));
+                                    d_spheres.size(), detail::tree_args(d_tree), detail::raw(d_ray_offsets),
+                                    static_cast<const Real*>(NULL));
     // Each ray segment in the output arrays ends with a sentinel value marking the end of the
     // ray; increase offsets accordingly (trace_sph.cuh:199-208).
     const size_t allocate_size = detail::counts_to_offsets(d_ray_offsets, n_rays) + n_rays;

@@ -410,6 +410,16 @@ inline void sort_by_distance(device_vector<float>& d_hit_distances,
                                              d_hit_indices.data(), d_hit_data.data(), nullptr));
 }
 
+// sort.cuh:100-131 with Real = double (the outputs of the double-precision trace_sph forms)
+inline void sort_by_distance(device_vector<double>& d_hit_distances,
+                             const device_vector<int>& d_ray_offsets,
+                             device_vector<int>& d_hit_indices, device_vector<double>& d_hit_data)
+{
+    detail::check(grace_sort_by_distance_f64(d_hit_distances.data(), d_ray_offsets.data(),
+                                             d_ray_offsets.size(), d_hit_distances.size(),
+                                             d_hit_indices.data(), d_hit_data.data(), nullptr));
+}
+
 // ---- ray generators, include/grace/cuda/gen_rays.cuh (vector overloads: d_rays is grown when
 // too small, never shrunk).  Random generators use this library's own counter-based streams;
 // the reference's cuRAND streams are device-specific by its own account (gen_rays.cuh:21-24).
@@ -595,6 +605,85 @@ inline void trace_cumulative_sph(const device_vector<Ray>& d_rays,
                                             d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
                                             d_tree.root_index_ptr, d_cumulated.data(), nullptr));
     detail::check(grace_trace_status_d4(nullptr));
+}
+
+// trace_sph.cuh:81-241 with Real4 = float4, Real = double (mixed precision: the fp64 sphere test
+// on float spheres, double sums and per-hit outputs; grace_hip.h).  The hit-count pass of
+// trace_sph uses the same fp64 test as the per-hit pass.
+inline void trace_cumulative_sph(const device_vector<Ray>& d_rays,
+                                 const device_vector<float4>& d_spheres, const Tree& d_tree,
+                                 device_vector<double>& d_cumulated)
+{
+    detail::check_ray_count(d_rays.size());
+    detail::check(grace_trace_cumulative_f4_f64(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                                d_spheres.size(), &d_tree.nodes.data()->x,
+                                                d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                                d_tree.root_index_ptr, d_cumulated.data(), nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
+inline void trace_sph(const device_vector<Ray>& d_rays, const device_vector<float4>& d_spheres,
+                      const Tree& d_tree, device_vector<int>& d_ray_offsets,
+                      device_vector<int>& d_hit_indices, device_vector<double>& d_hit_integrals,
+                      device_vector<double>& d_hit_distances)
+{
+    detail::check_ray_count(d_rays.size());
+    detail::check(grace_trace_hitcounts_f4_f64(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                               d_spheres.size(), &d_tree.nodes.data()->x,
+                                               d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                               d_tree.root_index_ptr, d_ray_offsets.data(), nullptr));
+    long long total = 0;
+    detail::check(grace_scan_exclusive_i32(d_ray_offsets.data(), d_ray_offsets.size(),
+                                           d_ray_offsets.data(), &total, nullptr));
+    if (total > 2147483647LL)
+        throw std::invalid_argument("trace_sph: more than INT_MAX hits; trace fewer rays per call.");
+    d_hit_integrals.resize(size_t(total));
+    d_hit_indices.resize(size_t(total));
+    d_hit_distances.resize(size_t(total));
+    if (total == 0) return;
+    detail::check(grace_trace_hits_f4_f64(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                          d_spheres.size(), &d_tree.nodes.data()->x,
+                                          d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                          d_tree.root_index_ptr, d_ray_offsets.data(),
+                                          d_hit_indices.data(), d_hit_integrals.data(),
+                                          d_hit_distances.data(), nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
+inline void trace_with_sentinels_sph(const device_vector<Ray>& d_rays,
+                                     const device_vector<float4>& d_spheres, const Tree& d_tree,
+                                     device_vector<int>& d_ray_offsets,
+                                     device_vector<int>& d_hit_indices, const int index_sentinel,
+                                     device_vector<double>& d_hit_integrals,
+                                     const double integral_sentinel,
+                                     device_vector<double>& d_hit_distances,
+                                     const double distance_sentinel)
+{
+    const size_t n_rays = d_rays.size();
+    detail::check_ray_count(n_rays);
+    detail::check(grace_trace_hitcounts_f4_f64(d_rays.data(), n_rays, &d_spheres.data()->x,
+                                               d_spheres.size(), &d_tree.nodes.data()->x,
+                                               d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                               d_tree.root_index_ptr, d_ray_offsets.data(), nullptr));
+    long long total = 0;
+    detail::check(grace_scan_exclusive_i32(d_ray_offsets.data(), n_rays, d_ray_offsets.data(),
+                                           &total, nullptr));
+    if (total + (long long)n_rays > 2147483647LL)
+        throw std::invalid_argument("trace_with_sentinels_sph: more than INT_MAX output slots; "
+                                    "trace fewer rays per call.");
+    const size_t allocate_size = size_t(total) + n_rays;
+    detail::check(grace_add_iota_i32(d_ray_offsets.data(), n_rays, nullptr));
+    d_hit_indices.resize(allocate_size);
+    detail::check(grace_fill_u32(d_hit_indices.data(), allocate_size, uint32_t(index_sentinel), nullptr));
+    // (64-bit sentinels: filled from the host, as a container fill)
+    d_hit_integrals = std::vector<double>(allocate_size, integral_sentinel);
+    d_hit_distances = std::vector<double>(allocate_size, distance_sentinel);
+    detail::check(grace_trace_hits_f4_f64(d_rays.data(), n_rays, &d_spheres.data()->x, d_spheres.size(),
+                                          &d_tree.nodes.data()->x, d_tree.leaves.size() - 1,
+                                          &d_tree.leaves.data()->x, d_tree.root_index_ptr,
+                                          d_ray_offsets.data(), d_hit_indices.data(),
+                                          d_hit_integrals.data(), d_hit_distances.data(), nullptr));
+    detail::check(grace_trace_status(nullptr));
 }
 
 // Extensions (not in the reference; see grace_hip.h): what every trace call otherwise recomputes

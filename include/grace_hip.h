@@ -528,6 +528,34 @@ grace_status grace_trace_hits_d4(const void* d_rays, size_t n_rays, const double
 /* Same status word as grace_trace_status (kept for callers of the round-1 interface). */
 grace_status grace_trace_status_d4(grace_stream stream);
 
+/* trace_hitcounts_sph / trace_cumulative_sph / trace_sph pass 2 <float4, (int,) double>, mixed
+ * precision (trace_sph.cuh:81-241 with RayData_sphere<double, double>): sphere_hit<float4, double>
+ * (generic/intersect.h:9-55) -- p = s - o subtracted in float then widened, dot_p and b2 in double,
+ * tested against the float product w * w --; per-hit terms as OnHit_sphere_cumulate /
+ * OnHit_sphere_individual<int, double> promote them (functors/trace.cuh:164-235,
+ * generic/interpolate.h:11-39): column-density terms are floats (ir, b, the lerp's result and
+ * the ir * ir scaling in float) added into the class-ordered double sum of
+ * grace_trace_cumulative_d4; per-hit integrals and distances are double, from ir = 1.f / w.
+ * grace_trace_hitcounts_f4_f64 counts with THIS test -- it is the hit-count pass of the mixed
+ * trace_sph (the reference sizes that pass with the float test, trace_sph.cuh:121-141;
+ * INTEGRATION.md) -- and grace_trace_hitcounts_f4 keeps the float test.  The walk runs on float
+ * records of their own, inflated so that every cull keeps what the fp64 test can accept; they
+ * are derived per call and never enter the scene cache.  grace_trace_set_exact_integrals does
+ * not apply.  Status word: grace_trace_status. */
+grace_status grace_trace_hitcounts_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                          size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                          const int* d_leaves, const int* d_root, int* d_hit_counts,
+                                          grace_stream stream);
+grace_status grace_trace_cumulative_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                           size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                           const int* d_leaves, const int* d_root, double* d_sums,
+                                           grace_stream stream);
+grace_status grace_trace_hits_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                     size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                     const int* d_leaves, const int* d_root, const int* d_ray_offsets,
+                                     int* d_hit_indices, double* d_hit_integrals,
+                                     double* d_hit_distances, grace_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
