@@ -169,7 +169,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     const bool reuse_chunks = MODE == MODE_HITS && hits_split && ts.hits.valid && ts.hits.rays == a.rays
         && ts.hits.n_rays == n_rays && ts.hits.prims == static_cast<const void*>(a.spheres)
         && ts.hits.n_prims == n_spheres && ts.hits.n_chunks == hit_chunks;
-    if (MODE == MODE_HITS || MODE == MODE_COUNT) ts.hits.valid = false;   // consumed, or stale from here on
+    if (chunked(MODE)) ts.hits.valid = false;   // consumed, or stale from here on
     if (keep_chunks) {
         const size_t need = n_rays * size_t(hit_chunks);
         if (ts.hits.capacity < need) {
@@ -185,24 +185,18 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     // 2-4x the waves, each with a tighter beam, on a chip that would otherwise sit idle.
     int width = 64;
     if (ts.width > 0) width = ts.width;
-    else if ((MODE == MODE_HITS && !hits_split) || MODE == MODE_TRI || MODE == MODE_HITS_D4
-             || MODE == MODE_HITS_F4D)
+    else if (ordered(MODE) && !hits_split)
         while (width > 16 && ceil_div(n_rays, size_t(width)) < 4096) width /= 2;
     // Hit counts and column densities split packets eight ways at most; a batch too small to fill
     // the chip even then (< 512 packets) also gets narrower packets (10^7 particles, 12288 HEALPix
     // rays: 3.5 -> 2.0 ms at 16 rays per packet; from 49152 rays on it loses: config 3 0.87 -> 0.95 ms).
-    else if ((MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4
-              || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D) && ts.split <= 0)
+    else if (class_split(MODE) && ts.split <= 0)
         while (width > 16 && ceil_div(n_rays, size_t(width)) * SUM_CLASSES < 4096) width /= 2;
     a.width = width;
     const int n_packets = ceil_div(n_rays, size_t(width));
     // Waves per packet: two resident sets of waves (2 x 8192) for small ray batches.
     int split = 1;
-    // (double4 and mixed-precision hit counts and column densities split the same way: the same
-    // classes, summed in double)
-    constexpr bool CLASS_SPLIT = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4
-                                  || MODE == MODE_CUM_D4 || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D);
-    if (CLASS_SPLIT) {
+    if (class_split(MODE)) {
         // (column densities: a batch of exactly 16384 packets -- the 1024^2 frame -- still gets a
         // second wave per packet, 32768 waves; see choose_split.  Larger batches run one.)
         const size_t wave_budget = (MODE == MODE_CUMULATIVE) ? 16385 : 16384;
@@ -220,16 +214,11 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     a.split = split;
     a.split_dev = nullptr;
     // (the working waves per packet are chosen on the device, by ray_keys_kernel)
-    const bool dev_split = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE) && split > 1 && ts.split <= 0;
+    const bool dev_split = f4_class_split(MODE) && split > 1 && ts.split <= 0;
     {
-        constexpr bool need_b = (MODE == MODE_CUMULATIVE || MODE == MODE_HITS);
+        constexpr bool need_b = f4_integrals(MODE);
         const bool fast_b = MODE == MODE_CUMULATIVE && !ts.exact_integrals;
         const bool reorder = ts.ray_reorder && n_rays > 64;
-        constexpr bool D4 = (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4);
-        // Mixed precision: records of its own (kind 3, inflated for the fp64 test), derived per call
-        // like the double4 ones -- the scene cache, which holds kind 0 records, is neither read nor
-        // filled nor counted as seen, so float calls on the same arrays cache exactly as before.
-        constexpr bool F4D = (MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D || MODE == MODE_HITS_F4D);
         // ---- which cached records does this call use?  (see trace_state.hpp) -------------------
         // NONE: derive into the workspace (a scene / batch seen for the first time);  FILL: the
         // same arrays as the previous call -- derive into the cache;  CHECK: cached -- validate by
@@ -242,10 +231,13 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         };
         int scene_use = USE_NONE, rays_use = USE_NONE;
         SceneKey skey;
-        skey.kind = MODE == MODE_TRI ? 1 : 0;
+        skey.kind = primitive(MODE);
         skey.prims = a.spheres; skey.nodes = a.nodes; skey.leaves = a.leaves;
         skey.n_prims = n_spheres; skey.n_nodes = n_nodes;
-        if (!D4 && !F4D && MODE != MODE_STATS) {
+        // The fp64 modes' records (inflated for the fp64 test) are derived per call: the scene cache
+        // is neither read nor filled nor counted as seen by them, so float calls on the same arrays
+        // cache exactly as they would without them.
+        if (!fp64(MODE) && MODE != MODE_STATS) {
             scene_use = decide(ts.scene.valid && ts.scene.key == skey, ts.scene.valid && ts.scene.pinned,
                                ts.scene.seen == skey);
             ts.scene.seen = skey;
@@ -273,8 +265,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
                                                    + 4 * Workspace::aligned(hit_packets * 4 + 64)
                                                    + Workspace::aligned(n_rays * 4) : 0)
                                    + (MODE == MODE_CUMULATIVE ? Workspace::aligned(n_rays * SUM_CLASSES * 4) : 0)
-                                   + ((MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D)
-                                      ? Workspace::aligned(n_rays * SUM_CLASSES * 8) : 0)
+                                   + (double_sums(MODE) ? Workspace::aligned(n_rays * SUM_CLASSES * 8) : 0)
                                    + (reorder ? 2 * Workspace::aligned(n_rays * 4)
                                                 + sort_ws_bytes(n_rays, 4, 0) : 0)
                                    + (any_sig ? Workspace::aligned(sig_partial_words() * 8) : 0) + 1024, stream));
@@ -311,14 +302,13 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
             double* T64 = (MODE == MODE_TRI) ? Workspace::take<double>(9 * (n_spheres + 4)) : nullptr;
             int2* node_prims = Workspace::take<int2>(n_nodes);
             float4* C = Workspace::take<float4>(cluster_record_count(n_spheres));
-            GRACE_TRY(scene_fill(MODE == MODE_TRI ? 1 : D4 ? 2 : F4D ? 3 : 0,
-                                 D4 ? static_cast<const void*>(a.spheres_d) : a.spheres, n_spheres, a.nodes, n_nodes, a.leaves, A,
-                                 fast_b ? nullptr : B, fast_b ? B : nullptr, T64, node_prims, C, stream));
+            GRACE_TRY(scene_fill(skey.kind, primitive(MODE) == PRIM_D4 ? static_cast<const void*>(a.spheres_d) : a.spheres,
+                                 n_spheres, a.nodes, n_nodes, a.leaves, A, fast_b ? nullptr : B, fast_b ? B : nullptr,
+                                 T64, node_prims, C, stream));
             a.A = A; a.B = B; a.T64 = T64; a.node_prims = node_prims; a.C = C;
         }
         a.partial = (MODE == MODE_CUMULATIVE) ? Workspace::take<float>(n_rays * SUM_CLASSES) : nullptr;
-        a.partial_d = (MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D)
-            ? Workspace::take<double>(n_rays * SUM_CLASSES) : nullptr;
+        a.partial_d = double_sums(MODE) ? Workspace::take<double>(n_rays * SUM_CLASSES) : nullptr;
         if (hits_split) {
             chunk_counts = Workspace::take<int>(n_rays * size_t(hit_chunks));
             chunk_off = Workspace::take<int>(n_rays * size_t(hit_chunks));
@@ -357,8 +347,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
             uint32_t* ext = Workspace::take<uint32_t>(16);
             uint32_t* keys = Workspace::take<uint32_t>(n_rays);
             uint32_t* perm = Workspace::take<uint32_t>(n_rays);
-            constexpr bool lat_mode = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_HITS);
-            uint32_t* lat_flag = lat_mode ? ext + 13 : nullptr;
+            uint32_t* lat_flag = has_lattice(MODE) ? ext + 13 : nullptr;
             int* split_dev = dev_split ? reinterpret_cast<int*>(ext + 12) : nullptr;
             const int split_flags = (MODE == MODE_CUMULATIVE) ? SPLIT_WIDE_BUDGET : 0;
             if (rays_cached) {
@@ -380,7 +369,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
                                     split | split_flags, split_dev, stream));
                 a.perm = perm;
             }
-            if (lat_mode) a.lat_dev = reinterpret_cast<const int*>(ext + 13);
+            if (has_lattice(MODE)) a.lat_dev = reinterpret_cast<const int*>(ext + 13);
             if (dev_split) a.split_dev = reinterpret_cast<const int*>(ext + 12);
         }
     }
@@ -395,7 +384,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     a.chunk_off = chunk_off;
     a.wave_map = wave_map;
     a.n_wave_map = n_wave_map;
-    if (split > 1 && (MODE == MODE_COUNT || MODE == MODE_COUNT_D4 || MODE == MODE_COUNT_F4D))
+    if (split > 1 && output(MODE) == OUT_COUNTS)
         GRACE_TRY_HIP(hipMemsetAsync(a.out_counts, 0, n_rays * sizeof(int), stream));
     if (keep_chunks && split > 1) {
         a.chunk_counts = ts.hits.chunk_counts;
@@ -430,17 +419,16 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     // with four waves per packet: the heaviest packets' work is spread over four SIMDs (measured
     // on two clustered scenes: K = 2 / 4 / 8 -> 3.62 / 3.47 / 4.24 ms and 4.24 / 3.42 / 3.71 ms;
     // one wave: 4.66 and 6.78 ms).  Same class sums, same bits.
-    const bool lat_split = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE) && split == 1 && a.lat_dev && width == 64
+    const bool lat_split = f4_class_split(MODE) && split == 1 && a.lat_dev && width == 64
         && ts.lat_split > 0 && ts.split <= 0;   // (an explicit grace_trace_set_packet_split is obeyed)
     auto one_or_split = [&](auto alt_tag) -> grace_status {
         constexpr bool A = decltype(alt_tag)::value;
-        constexpr int M = (MODE == MODE_COUNT) ? MODE_COUNT : MODE_CUMULATIVE;
         if (MODE == MODE_COUNT) GRACE_TRY_HIP(hipMemsetAsync(a.out_counts, 0, n_rays * sizeof(int), stream));
-        trace_kernel<M, false, A, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
+        trace_kernel<MODE, false, A, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
         GRACE_CHECK_LAUNCH();
         TraceArgs a8 = a;
         a8.split = ts.lat_split; a8.split_dev = nullptr;
-        trace_kernel<M, true, A, true><<<ceil_div(size_t(n_packets) * ts.lat_split, TRACE_BLOCK / 64), TRACE_BLOCK, 0, stream>>>(a8);
+        trace_kernel<MODE, true, A, true><<<ceil_div(size_t(n_packets) * ts.lat_split, TRACE_BLOCK / 64), TRACE_BLOCK, 0, stream>>>(a8);
         GRACE_CHECK_LAUNCH();
         if (MODE == MODE_CUMULATIVE) {
             combine_classes_kernel<float><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial, int(n_rays), ts.lat_split,
@@ -512,8 +500,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         if (split > 1) both(M_(), T(), F(), a);
         else if (lat_split) GRACE_TRY(one_or_split(F()));
         else both(M_(), F(), F(), a);
-    } else if constexpr (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4 || MODE == MODE_COUNT_F4D
-                         || MODE == MODE_CUM_F4D) {
+    } else if constexpr (class_split(MODE)) {
         if (split > 1) trace_kernel<MODE, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);
         else trace_kernel<MODE, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
     } else {
@@ -521,7 +508,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     }
     GRACE_CHECK_LAUNCH();
     GRACE_TRY(stamps_report(MODE));
-    if ((MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D) && split > 1) {
+    if (double_sums(MODE) && split > 1) {
         combine_classes_kernel<double><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial_d, int(n_rays), split,
                                                                                    nullptr, a.out_sums_d);
         GRACE_CHECK_LAUNCH();
@@ -536,6 +523,20 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         ts.ev_valid = true;
     }
     return GRACE_OK;
+}
+
+// What every trace entry point passes the same way (a double4 trace also sets spheres_d; its
+// `spheres` is checked for null only).
+TraceArgs trace_args(const void* d_rays, const void* d_prims, const int* d_nodes, const int* d_leaves,
+                     const int* d_root)
+{
+    TraceArgs a = {};
+    a.rays = static_cast<const float*>(d_rays);
+    a.spheres = static_cast<const float4*>(d_prims);
+    a.nodes = reinterpret_cast<const float4*>(d_nodes);
+    a.leaves = reinterpret_cast<const int4*>(d_leaves);
+    a.root = d_root;
+    return a;
 }
 
 } // namespace
@@ -577,12 +578,7 @@ grace_status grace_trace_hitcounts_f4(const void* d_rays, size_t n_rays, const f
 {
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_hit_counts, "trace_hitcounts: null output");
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.out_counts = d_hit_counts;
     return launch_trace<MODE_COUNT>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -594,12 +590,7 @@ grace_status grace_trace_hitcounts_keep_f4(const void* d_rays, size_t n_rays, co
 {
     if (n_rays == 0) return GRACE_OK;
     GRACE_REQUIRE(d_hit_counts, "trace_hitcounts: null output");
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.out_counts = d_hit_counts;
     a.keep_chunks = true;
     return launch_trace<MODE_COUNT>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
@@ -612,12 +603,7 @@ grace_status grace_trace_cumulative_f4(const void* d_rays, size_t n_rays, const 
 {
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_cumulated, "trace_cumulative: null output");
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.out_sums = d_cumulated;
     return launch_trace<MODE_CUMULATIVE>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -632,12 +618,7 @@ grace_status grace_trace_hits_f4(const void* d_rays, size_t n_rays, const float*
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_ray_offsets && d_hit_indices && d_hit_integrals && d_hit_distances,
                   "trace_hits: null output");
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.offsets = d_ray_offsets;
     a.hit_idx = d_hit_indices;
     a.hit_integral = d_hit_integrals;
@@ -652,30 +633,12 @@ grace_status grace_trace_closest_tri(const void* d_rays, size_t n_rays, const fl
 {
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_closest, "trace_closest_tri: null output");
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_tris); // 9 floats per triangle
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
+    TraceArgs a = trace_args(d_rays, d_tris, d_nodes, d_leaves, d_root);   // (9 floats per triangle)
     a.out_counts = d_closest;
     return launch_trace<MODE_TRI>(a, n_rays, n_tris, n_nodes, as_stream(stream));
 }
 
 // ---- double4 spheres (Real4 = double4, Real = double) ----------------------------------------
-static TraceArgs d4_args(const void* d_rays, const double* d_spheres, const int* d_nodes,
-                         const int* d_leaves, const int* d_root)
-{
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);   // (non-null check only)
-    a.spheres_d = d_spheres;
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
-    return a;
-}
-
 grace_status grace_trace_hitcounts_d4(const void* d_rays, size_t n_rays, const double* d_spheres,
                                       size_t n_spheres, const int* d_nodes, size_t n_nodes,
                                       const int* d_leaves, const int* d_root, int* d_hit_counts,
@@ -683,7 +646,8 @@ grace_status grace_trace_hitcounts_d4(const void* d_rays, size_t n_rays, const d
 {
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_hit_counts, "trace_hitcounts (double4): null output");
-    TraceArgs a = d4_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.spheres_d = d_spheres;
     a.out_counts = d_hit_counts;
     return launch_trace<MODE_COUNT_D4>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -695,7 +659,8 @@ grace_status grace_trace_cumulative_d4(const void* d_rays, size_t n_rays, const 
 {
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_sums, "trace_cumulative (double4): null output");
-    TraceArgs a = d4_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.spheres_d = d_spheres;
     a.out_sums_d = d_sums;
     return launch_trace<MODE_CUM_D4>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -709,7 +674,8 @@ grace_status grace_trace_hits_d4(const void* d_rays, size_t n_rays, const double
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_ray_offsets && d_hit_indices && d_hit_integrals && d_hit_distances,
                   "trace_hits (double4): null output");
-    TraceArgs a = d4_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.spheres_d = d_spheres;
     a.offsets = d_ray_offsets;
     a.hit_idx = d_hit_indices;
     a.hit_integral_d = d_hit_integrals;
@@ -720,18 +686,6 @@ grace_status grace_trace_hits_d4(const void* d_rays, size_t n_rays, const double
 grace_status grace_trace_status_d4(grace_stream stream) { return grace_trace_status(stream); }
 
 // ---- float4 spheres, double outputs (Real4 = float4, Real = double) ---------------------------
-static TraceArgs f4d_args(const void* d_rays, const float* d_spheres, const int* d_nodes,
-                          const int* d_leaves, const int* d_root)
-{
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
-    return a;
-}
-
 grace_status grace_trace_hitcounts_f4_f64(const void* d_rays, size_t n_rays, const float* d_spheres,
                                           size_t n_spheres, const int* d_nodes, size_t n_nodes,
                                           const int* d_leaves, const int* d_root, int* d_hit_counts,
@@ -739,7 +693,7 @@ grace_status grace_trace_hitcounts_f4_f64(const void* d_rays, size_t n_rays, con
 {
     if (n_rays == 0) return GRACE_OK;
     GRACE_REQUIRE(d_hit_counts, "trace_hitcounts (float4, double): null output");
-    TraceArgs a = f4d_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.out_counts = d_hit_counts;
     return launch_trace<MODE_COUNT_F4D>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -751,7 +705,7 @@ grace_status grace_trace_cumulative_f4_f64(const void* d_rays, size_t n_rays, co
 {
     if (n_rays == 0) return GRACE_OK;
     GRACE_REQUIRE(d_sums, "trace_cumulative (float4, double): null output");
-    TraceArgs a = f4d_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.out_sums_d = d_sums;
     return launch_trace<MODE_CUM_F4D>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -765,7 +719,7 @@ grace_status grace_trace_hits_f4_f64(const void* d_rays, size_t n_rays, const fl
     if (n_rays == 0) return GRACE_OK;
     GRACE_REQUIRE(d_ray_offsets && d_hit_indices && d_hit_integrals && d_hit_distances,
                   "trace_hits (float4, double): null output");
-    TraceArgs a = f4d_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.offsets = d_ray_offsets;
     a.hit_idx = d_hit_indices;
     a.hit_integral_d = d_hit_integrals;
@@ -780,12 +734,7 @@ grace_status grace_trace_stats_f4(const void* d_rays, size_t n_rays, const float
 {
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
     GRACE_REQUIRE(d_stats4, "trace_stats: null output");
-    TraceArgs a = {};
-    a.rays = static_cast<const float*>(d_rays);
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.stats = d_stats4;
     return launch_trace<MODE_STATS>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
 }
@@ -810,14 +759,14 @@ grace_status grace_trace_prepare_f4(const float* d_spheres, size_t n_spheres, co
                                     size_t n_nodes, const int* d_leaves, grace_stream stream)
 {
     GRACE_TRACE_STATE();
-    return scene_prepare(ts, false, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, as_stream(stream));
+    return scene_prepare(ts, PRIM_F4, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, as_stream(stream));
 }
 
 grace_status grace_trace_prepare_tri(const float* d_tris, size_t n_tris, const int* d_nodes,
                                      size_t n_nodes, const int* d_leaves, grace_stream stream)
 {
     GRACE_TRACE_STATE();
-    return scene_prepare(ts, true, d_tris, n_tris, d_nodes, n_nodes, d_leaves, as_stream(stream));
+    return scene_prepare(ts, PRIM_TRI, d_tris, n_tris, d_nodes, n_nodes, d_leaves, as_stream(stream));
 }
 
 grace_status grace_trace_prepare_rays(const void* d_rays, size_t n_rays, grace_stream stream)

@@ -347,12 +347,12 @@ template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false>
 // VGPRs): left to itself the register allocator drifts between 77 and 102 VGPRs from one edit of
 // this file to the next, and at 5 waves per SIMD the frame kernel loses 20 % (2.9 -> 3.55 ms,
 // measured when an unrelated change tipped it over).
-__global__ __launch_bounds__(TRACE_BLOCK, (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE) ? (SPLIT ? 8 : 6) : 1)
+__global__ __launch_bounds__(TRACE_BLOCK, f4_class_split(MODE) ? (SPLIT ? 8 : 6) : 1)
 void trace_kernel(const TraceArgs a)
 {
-    static_assert(!ALT || MODE == MODE_CUMULATIVE || MODE == MODE_HITS, "no alternative path for this mode");
-    static_assert(!LAT || MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_HITS, "no lattice cull for this mode");
-    if (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_HITS) {
+    static_assert(!ALT || f4_integrals(MODE), "no alternative path for this mode");
+    static_assert(!LAT || has_lattice(MODE), "no lattice cull for this mode");
+    if (has_lattice(MODE)) {
         if (a.lat_dev ? (*a.lat_dev != 0) != LAT : LAT) return;   // (workgroup-uniform)
         if (a.stage_dev && *a.stage_dev != a.stage_want) return;
     }
@@ -366,9 +366,8 @@ void trace_kernel(const TraceArgs a)
     __shared__ float2 s_lutf[FAST ? LUTF_N : 1];
     // Per-wave tile of the candidates of the current culling round (MODE_TRI keeps its
     // fp64 triangles on the scalar path).
-    constexpr bool D4 = (MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4);
-    constexpr bool F4D = (MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D || MODE == MODE_HITS_F4D);
-    constexpr bool LDS_TILE = (MODE != MODE_TRI && !D4 && !F4D);
+    constexpr bool D4 = primitive(MODE) == PRIM_D4, F4D = primitive(MODE) == PRIM_F4D;
+    constexpr bool LDS_TILE = primitive(MODE) == PRIM_F4;
     // Three 8-byte planes per wave -- (x, y), (z, h^2), (1/h terms) -- so that one address
     // (plane base + 8 j) serves all of a survivor's reads through immediate offsets.
     // (66 slots: the survivor loop reads up to two slots past the round's last survivor)
@@ -380,10 +379,7 @@ void trace_kernel(const TraceArgs a)
     // {fl(1/w), fl(fl(1/w)^2), -, -} -- every value the reference forms in float before widening.
     __shared__ float4 s_tile_f[F4D ? TRACE_BLOCK / 64 : 1][F4D ? 64 : 1][F4D ? 2 : 1];
     const int lane = threadIdx.x & 63;
-    constexpr bool SPLITTABLE = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_HITS
-                                 || MODE == MODE_COUNT_D4 || MODE == MODE_CUM_D4
-                                 || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D);
-    static_assert(!SPLIT || SPLITTABLE, "triangle and stats walks do not split");
+    static_assert(!SPLIT || class_split(MODE) || MODE == MODE_HITS, "triangle and stats walks do not split");
     // Hit counts and column densities split a packet by summation class (interleaved granules);
     // the per-hit trace, whose output is ordered, by contiguous chunk ranges chosen per packet.
     constexpr bool RANGE_SPLIT = SPLIT && MODE == MODE_HITS;
@@ -400,8 +396,7 @@ void trace_kernel(const TraceArgs a)
     const int vblock = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + slot;
     const int wave_id = __builtin_amdgcn_readfirstlane(vblock * (TRACE_BLOCK / 64)
                                                        + (threadIdx.x >> 6));
-    if (MODE == MODE_CUMULATIVE || MODE == MODE_HITS || MODE == MODE_CUM_D4 || MODE == MODE_HITS_D4
-        || MODE == MODE_CUM_F4D || MODE == MODE_HITS_F4D) {
+    if (integrates(MODE)) {
         if (FAST) {
             static_assert(TRACE_BLOCK >= 256, "one table entry per thread");
             float2 e = make_float2(0.f, 0.f);
@@ -467,7 +462,7 @@ void trace_kernel(const TraceArgs a)
 
     // Axis-aligned packet?  (wave-uniform; tail lanes replicate a valid ray)
     int axis = -1;
-    if (MODE != MODE_HITS && MODE != MODE_TRI && MODE != MODE_HITS_D4 && MODE != MODE_HITS_F4D) {
+    if (!ordered(MODE)) {
         const unsigned long long all = ~0ull;
         const bool zx = dx == 0.f, zy = dy == 0.f, zz = dz == 0.f;
         if (__builtin_amdgcn_ballot_w64(zy && zz && fabsf(dx) == 1.f) == all) axis = 0;
@@ -613,14 +608,13 @@ void trace_kernel(const TraceArgs a)
     // Chunk bookkeeping of the split per-hit trace (see TraceArgs): the counting pass adds each
     // lane's hits of a chunk to chunk_counts when the walk leaves the chunk; the per-hit pass
     // repositions each lane's output cursor when it enters one.
-    constexpr bool CHUNKED = (SPLIT && (MODE == MODE_COUNT || MODE == MODE_HITS));
+    constexpr bool CHUNKED = SPLIT && chunked(MODE);
     int cur_chunk = -1;        // wave-uniform
     int count_at_chunk = 0;
     float sum = 0.f;        // accumulator of the current granule's class (MODE_CUMULATIVE)
     // Class accumulators of this wave's lanes (one wave = one row of the workgroup's array).
-    // (MODE_CUM_D4, MODE_CUM_F4D: the same classes, accumulated and combined in double)
-    constexpr bool CLASSES_F = (MODE == MODE_CUMULATIVE), CLASSES_D = (MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D);
-    constexpr bool CLASSES = CLASSES_F || CLASSES_D;
+    constexpr bool CLASSES_F = MODE == MODE_CUMULATIVE, CLASSES_D = double_sums(MODE);
+    constexpr bool CLASSES = output(MODE) == OUT_SUMS;
     __shared__ float s_class[CLASSES_F ? TRACE_BLOCK / 64 : 1][CLASSES_F ? SUM_CLASSES : 1][CLASSES_F ? 64 : 1];
     __shared__ double s_class_d[CLASSES_D ? TRACE_BLOCK / 64 : 1][CLASSES_D ? SUM_CLASSES : 1][CLASSES_D ? 64 : 1];
     const int wv_acc = threadIdx.x >> 6;
@@ -632,7 +626,7 @@ void trace_kernel(const TraceArgs a)
 #pragma unroll
         for (int c = 0; c < SUM_CLASSES; ++c) s_class_d[wv_acc][c][lane] = 0.0;
     }
-    double sum_d = 0.0;     // MODE_CUM_D4 / _F4D: accumulator of the current granule's class
+    double sum_d = 0.0;     // the same, of double_sums
     int cur_granule = -1;            // wave-uniform
     int cur_granule_end = 0;         // first primitive past the current granule
     bool cur_owned = true;
@@ -658,7 +652,7 @@ void trace_kernel(const TraceArgs a)
     int tri_data = -1;
     float tri_tmin = len * (1.f + 0.000001f);
     const double ddx = dx, ddy = dy, ddz = dz;
-    if (MODE == MODE_HITS || MODE == MODE_HITS_D4 || MODE == MODE_HITS_F4D) write_at = a.offsets[ray_index];
+    if (output(MODE) == OUT_HITS) write_at = a.offsets[ray_index];
     const double rdx = dx, rdy = dy, rdz = dz;
     // MODE_HITS: every ray owns a contiguous output segment, so lanes writing hit by hit
     // touch 64 different cache lines per store and the partial lines thrash L2 (measured:
@@ -742,8 +736,7 @@ void trace_kernel(const TraceArgs a)
     // replaced by n / 2^18 independent, coalesced passes (39 at 10^7 primitives).  Conservative
     // like the walk and the cluster tests: a group is dropped only if no ray of the packet can
     // hit any member, so the per-ray hit sets, and with them every sum, are unchanged.
-    constexpr bool FLAT_OK = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE || MODE == MODE_COUNT_D4
-                              || MODE == MODE_CUM_D4 || MODE == MODE_COUNT_F4D || MODE == MODE_CUM_F4D);
+    constexpr bool FLAT_OK = class_split(MODE);
     // Only packets whose group test is sharp: axis-aligned ones (origin rectangle) and pencils
     // (one origin: the bundle's side planes).  A GENERAL packet's beam -- boxes around its origins
     // and directions -- keeps nearly every group, where the walk's per-ray slab tests prune
@@ -939,7 +932,7 @@ void trace_kernel(const TraceArgs a)
             // component selection of the axis path is resolved at compile time.
             auto sweep_range = [&](auto ax_tag) {
                 constexpr int AX = decltype(ax_tag)::value;
-            constexpr bool NEED_B = (MODE == MODE_CUMULATIVE || MODE == MODE_HITS);
+            constexpr bool NEED_B = f4_integrals(MODE);
             constexpr bool LEAN4 = FAST && AX >= 0;
             const int wv = threadIdx.x >> 6;
             float4* const tile4 = reinterpret_cast<float4*>(&s_tile[wv][0][0]);   // (the same bytes, as 16-byte records)
@@ -1032,7 +1025,7 @@ void trace_kernel(const TraceArgs a)
                 // along the axis -- decided per candidate with the same FMA the rays use, which
                 // is monotone in its addend -- the round's survivors skip the two range tests.
                 bool lean_round = false;
-                if constexpr (AX >= 0 && (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE)) {
+                if constexpr (AX >= 0 && f4_class_split(MODE)) {
                     const float sa = AX == 0 ? mine.x : AX == 1 ? mine.y : mine.z;
                     const unsigned long long inside =
                         __builtin_amdgcn_ballot_w64(__builtin_fmaf(sa, da0, noda_lo) >= 0.0f)
@@ -1074,7 +1067,7 @@ void trace_kernel(const TraceArgs a)
                 // survivors only, in ascending order (slot = number of kept lanes below), so the
                 // k-th survivor sits at slot k -- no bit scanning, and slot addresses that differ
                 // by immediates.  The per-hit and triangle modes keep lane-indexed tiles.
-                constexpr bool COMPACT = (MODE == MODE_COUNT || MODE == MODE_CUMULATIVE);
+                constexpr bool COMPACT = f4_class_split(MODE);
                 // The round's survivors belong to ONE granule (a cluster never straddles two), so
                 // the class accumulator switch and the ownership test of a split packet stay out
                 // of the per-survivor loop.
@@ -1158,7 +1151,7 @@ void trace_kernel(const TraceArgs a)
                             b2 = bx * bx + by * by + bz * bz;
                         }
                         const bool hit = !(b2 >= sw2) && !(dot_p < 0.0f) && !(dot_p >= len);
-                        if (MODE == MODE_COUNT_D4) {
+                        if (output(MODE) == OUT_COUNTS) {
                             count += hit ? 1 : 0;
                         } else if (hit) {
                             const double ir = sp[4];
@@ -1168,7 +1161,7 @@ void trace_kernel(const TraceArgs a)
                             const double2 y = s_lut[x_idx];
                             double integral = __builtin_fma(x - x_idx, y.y, y.x);
                             integral *= sp[5];
-                            if (MODE == MODE_CUM_D4) {
+                            if (output(MODE) == OUT_SUMS) {
                                 sum_d += integral;
                             } else if (valid) {
                                 a.hit_idx[write_at] = jj;
@@ -1203,9 +1196,9 @@ void trace_kernel(const TraceArgs a)
                             b2 = bx * bx + by * by + bz * bz;
                         }
                         const bool hit = !(b2 >= double(r0.w)) && !(dot_p < 0.0f) && !(dot_p >= len);
-                        if (MODE == MODE_COUNT_F4D) {
+                        if (output(MODE) == OUT_COUNTS) {
                             count += hit ? 1 : 0;
-                        } else if (hit && MODE == MODE_CUM_F4D) {
+                        } else if (hit && output(MODE) == OUT_SUMS) {
                             // OnHit_sphere_cumulate with Real4 = float4 (functors/trace.cuh:164-186): Real
                             // is float -- b = float(50 (sqrt(b2) ir)), lerp<float> over the double table
                             // (its fma in double, narrowed), integral *= ir ir in float -- and the
@@ -1283,7 +1276,7 @@ void trace_kernel(const TraceArgs a)
 #ifdef GRACE_PACKET_STATS
                         if (MODE == MODE_STATS && __builtin_amdgcn_ballot_w64(hit) != 0ull) ++st_nodes;
 #endif
-                        if (MODE == MODE_COUNT || MODE == MODE_STATS) {
+                        if (!integrates(MODE)) {
                             count += hit ? 1 : 0;
                         } else if (hit) {
                             const float w = FAST ? hit_integral_fast(b2, sb.x, s_lutf)
@@ -1333,7 +1326,7 @@ void trace_kernel(const TraceArgs a)
                         // Keep the reads here -- ahead of the survivors in between -- instead of
                         // letting the scheduler sink them next to their use.
                         __builtin_amdgcn_sched_barrier(0);
-                    } else if (!D4 && !F4D) {
+                    } else if (!fp64(MODE)) {
                         c = a.A[jj];
                     }
                 };
@@ -1448,16 +1441,12 @@ void trace_kernel(const TraceArgs a)
     if (CHUNKED && MODE == MODE_COUNT && a.chunk_counts) leave_chunk();
     if ((overflow || junk < 0) && lane == 0) *a.status = GRACE_STACK_OVERFLOW;
     if (!valid) return;
-    if (MODE == MODE_COUNT) {
+    if (output(MODE) == OUT_COUNTS) {
         if (!SPLIT) a.out_counts[ray_index] = count;
         else if (count) atomicAdd(&a.out_counts[ray_index], count); // output zeroed by the host
     }
     if (MODE == MODE_TRI) a.out_counts[ray_index] = tri_data;
-    if (MODE == MODE_COUNT_D4 || MODE == MODE_COUNT_F4D) {
-        if (!SPLIT) a.out_counts[ray_index] = count;
-        else if (count) atomicAdd(&a.out_counts[ray_index], count); // output zeroed by the host
-    }
-    if (MODE == MODE_CUM_D4 || MODE == MODE_CUM_F4D) {
+    if (double_sums(MODE)) {
         // the float path's class-ordered sum, in double: pairwise over the 8 classes (this wave's
         // subtree of it when the packet is split)
         if (cur_granule >= 0) s_class_d[wv_acc][cur_granule & (SUM_CLASSES - 1)][lane] = sum_d;

@@ -306,7 +306,7 @@ grace_status scene_cache_alloc(TraceState& ts, const SceneKey& key)
 {
     Scene& sc = ts.scene;
     GRACE_TRY(scene_free_buffers(sc));
-    const bool tri = key.kind == 1;
+    const bool tri = key.kind == PRIM_TRI;
     auto alloc = [&](void** ptr, size_t bytes) -> grace_status {
         hipError_t e = hipMalloc(ptr, bytes);
         if (e != hipSuccess)
@@ -326,7 +326,7 @@ grace_status scene_cache_alloc(TraceState& ts, const SceneKey& key)
     return GRACE_OK;
 }
 
-grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float4* nodes,
+grace_status scene_fill(Primitive kind, const void* prims, size_t n_prims, const float4* nodes,
                         size_t n_nodes, const int4* leaves, float4* A, float2* B1, float2* B50,
                         double* T64, int2* node_prims, float4* C, hipStream_t stream,
                         const uint32_t* run_if)
@@ -335,15 +335,15 @@ grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float
         reinterpret_cast<const int4*>(nodes), leaves, int(n_nodes), node_prims,
         reinterpret_cast<uint32_t*>(C + 2 * ((n_prims + 63) / 64)), run_if);
     GRACE_CHECK_LAUNCH();
-    if (kind == 1) {
+    if (kind == PRIM_TRI) {
         tri_prepass_kernel<<<stream_grid(n_prims + 4, 256), 256, 0, stream>>>(
             static_cast<const float*>(prims), n_prims, A, T64, run_if);
         GRACE_CHECK_LAUNCH();
-    } else if (kind == 2) {
+    } else if (kind == PRIM_D4) {
         trace_prepass_d4_kernel<<<stream_grid(n_prims + 4, 256), 256, 0, stream>>>(
             static_cast<const double*>(prims), n_prims, A);
         GRACE_CHECK_LAUNCH();
-    } else if (kind == 3) {
+    } else if (kind == PRIM_F4D) {
         trace_prepass_f4d_kernel<<<stream_grid(n_prims + 4, 256), 256, 0, stream>>>(
             static_cast<const float4*>(prims), n_prims, A);
         GRACE_CHECK_LAUNCH();
@@ -353,7 +353,7 @@ grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float
             static_cast<const float4*>(prims), n_prims, A, B1, B50, C, run_if);
         GRACE_CHECK_LAUNCH();
     }
-    if (kind != 0) {
+    if (kind != PRIM_F4) {
         cluster_boxes_kernel<<<stream_grid((n_prims + 63) / 64, 4), 256, 0, stream>>>(A, n_prims, C, run_if);
         GRACE_CHECK_LAUNCH();
     }
@@ -368,13 +368,13 @@ grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float
 
 // grace_trace_prepare_f4 / _tri: the cache filled NOW (and kept until released or replaced by
 // another prepare), instead of at the second call on the same arrays.
-grace_status scene_prepare(TraceState& ts, bool tri, const void* prims, size_t n_prims,
+grace_status scene_prepare(TraceState& ts, Primitive kind, const void* prims, size_t n_prims,
                            const int* d_nodes, size_t n_nodes, const int* d_leaves, hipStream_t stream)
 {
     GRACE_REQUIRE(prims && d_nodes && d_leaves, "trace_prepare: null pointer");
     GRACE_REQUIRE(n_prims > 0 && n_nodes >= 1, "trace_prepare: empty scene");
     SceneKey key;
-    key.kind = tri ? 1 : 0; key.prims = prims; key.nodes = d_nodes; key.leaves = d_leaves;
+    key.kind = kind; key.prims = prims; key.nodes = d_nodes; key.leaves = d_leaves;
     key.n_prims = n_prims; key.n_nodes = n_nodes;
     GRACE_TRY(scene_cache_alloc(ts, key));
     Scene& sc = ts.scene;
@@ -383,14 +383,14 @@ grace_status scene_prepare(TraceState& ts, bool tri, const void* prims, size_t n
     if (st == GRACE_OK) {
         unsigned long long* partial = Workspace::take<unsigned long long>(sig_partial_words());
         SigRequest rq;
-        rq.prims = prims; rq.prims_bytes = n_prims * (tri ? 36 : 16);
+        rq.prims = prims; rq.prims_bytes = n_prims * (kind == PRIM_TRI ? 36 : 16);
         rq.nodes = d_nodes; rq.nodes_bytes = n_nodes * 64;
         rq.leaves = d_leaves; rq.leaves_bytes = (n_nodes + 1) * 16;
         rq.scene_ctl = sc.ctl; rq.scene_force = true;
         st = launch_signatures(rq, partial, stream);
     }
     if (st == GRACE_OK)
-        st = scene_fill(tri ? 1 : 0, prims, n_prims, reinterpret_cast<const float4*>(d_nodes), n_nodes,
+        st = scene_fill(kind, prims, n_prims, reinterpret_cast<const float4*>(d_nodes), n_nodes,
                         reinterpret_cast<const int4*>(d_leaves), sc.A, sc.B1, sc.B50, sc.T64,
                         sc.node_prims, sc.C, stream);
     if (st != GRACE_OK) { (void)scene_release(ts); return st; }

@@ -52,6 +52,61 @@ enum { MODE_COUNT = 0, MODE_CUMULATIVE = 1, MODE_HITS = 2, MODE_STATS = 3, MODE_
        // promotions for that pair, and column densities are the class-ordered double sum.
        MODE_COUNT_F4D = 8, MODE_CUM_F4D = 9, MODE_HITS_F4D = 10 };
 
+// What a mode does is its primitive and its output; every choice that depends on the mode is made
+// from these two (or the properties below), never from a list of modes.
+// The primitive is also the kind of scene records the pre-pass derives (SceneKey, scene_fill).
+enum Primitive { PRIM_F4 = 0,    // float4 spheres
+                 PRIM_TRI = 1,   // triangles, 9 floats each
+                 PRIM_D4 = 2,    // double4 spheres
+                 PRIM_F4D = 3 }; // float4 spheres, double results
+enum Output { OUT_COUNTS, OUT_SUMS, OUT_HITS, OUT_STATS, OUT_CLOSEST };
+
+struct ModeParts { Primitive prim; Output out; };
+constexpr ModeParts mode_parts(const int mode)
+{
+    switch (mode) {
+    case MODE_COUNT:      return { PRIM_F4, OUT_COUNTS };
+    case MODE_CUMULATIVE: return { PRIM_F4, OUT_SUMS };
+    case MODE_HITS:       return { PRIM_F4, OUT_HITS };
+    case MODE_STATS:      return { PRIM_F4, OUT_STATS };
+    case MODE_TRI:        return { PRIM_TRI, OUT_CLOSEST };
+    case MODE_COUNT_D4:   return { PRIM_D4, OUT_COUNTS };
+    case MODE_CUM_D4:     return { PRIM_D4, OUT_SUMS };
+    case MODE_HITS_D4:    return { PRIM_D4, OUT_HITS };
+    case MODE_COUNT_F4D:  return { PRIM_F4D, OUT_COUNTS };
+    case MODE_CUM_F4D:    return { PRIM_F4D, OUT_SUMS };
+    case MODE_HITS_F4D:   return { PRIM_F4D, OUT_HITS };
+    }
+    __builtin_unreachable();   // (a mode missing above is no constant expression: trace_kernel fails to compile)
+}
+constexpr Primitive primitive(const int mode) { return mode_parts(mode).prim; }
+constexpr Output output(const int mode) { return mode_parts(mode).out; }
+
+// Each survivor is tested, and its results formed, in double from the caller's record (the walk
+// and every cull run on float records that contain those spheres).
+constexpr bool fp64(const int mode) { return primitive(mode) == PRIM_D4 || primitive(mode) == PRIM_F4D; }
+// Hit counts and column densities: summed by class, so a packet splits among waves by class.
+constexpr bool class_split(const int mode) { return output(mode) == OUT_COUNTS || output(mode) == OUT_SUMS; }
+// ... of float4 spheres: compacted survivor tiles, and the device-side choice of the working waves.
+constexpr bool f4_class_split(const int mode) { return class_split(mode) && primitive(mode) == PRIM_F4; }
+// Column densities whose class sums are kept in double.
+constexpr bool double_sums(const int mode) { return output(mode) == OUT_SUMS && fp64(mode); }
+// A ray's result depends on the order its hits are met in (per-hit lists, closest hit): the packet
+// walks the tree in one wave.
+constexpr bool ordered(const int mode) { return output(mode) == OUT_HITS || output(mode) == OUT_CLOSEST; }
+// Kernel line integrals (the kernel table).
+constexpr bool integrates(const int mode) { return output(mode) == OUT_SUMS || output(mode) == OUT_HITS; }
+// ... in fp32: the 1/h records B, and the alternative (ALT) instantiations.
+constexpr bool f4_integrals(const int mode) { return integrates(mode) && primitive(mode) == PRIM_F4; }
+// Modes with an origin-lattice (LAT) instantiation.
+constexpr bool has_lattice(const int mode) { return primitive(mode) == PRIM_F4 && output(mode) != OUT_STATS; }
+// Per-(ray, chunk) hit bookkeeping of the split per-hit trace: its own walk, and the hit-count walk
+// that counts for it (HitsCache).
+constexpr bool chunked(const int mode)
+{
+    return primitive(mode) == PRIM_F4 && (output(mode) == OUT_COUNTS || output(mode) == OUT_HITS);
+}
+
 struct TraceArgs {
     const float* rays;      // 7 floats per ray
     const uint32_t* perm;   // packet slot -> ray index (coherence order), or null
@@ -65,15 +120,15 @@ struct TraceArgs {
     int group_shift;        // primitives per group box = 2^group_shift (see cluster_record_count)
     const float4* C;        // pre-pass: per CLUSTER (64 consecutive primitives) {lo.xyz, -}, {hi.xyz, -}:
                             // the box of the member spheres, slightly inflated (cluster_boxes_kernel)
-    const double* T64;      // MODE_TRI pre-pass: {v, e1, e2} widened to fp64, 9 per triangle
-    const double* spheres_d; // *_D4 modes: the caller's double4 spheres
-    double* out_sums_d;      // MODE_CUM_D4, MODE_CUM_F4D
-    double* hit_integral_d;  // MODE_HITS_D4, MODE_HITS_F4D
+    const double* T64;      // PRIM_TRI pre-pass: {v, e1, e2} widened to fp64, 9 per triangle
+    const double* spheres_d; // PRIM_D4: the caller's double4 spheres
+    double* out_sums_d;      // double_sums
+    double* hit_integral_d;  // OUT_HITS, fp64
     double* hit_dist_d;
     int split;              // waves per packet (1, 2, 4, 8); each owns SUM_CLASSES / split classes
     int n_prims;
     float* partial;         // split > 1, cumulative: [n_rays][split] subtree sums
-    double* partial_d;      // ... of the double4 trace
+    double* partial_d;      // ... of double_sums
     // Class split only: the number of waves per packet that actually work (a power of two <=
     // split, chosen on the device from the batch's coherence); waves beyond it exit at once.
     const int* split_dev;
@@ -93,19 +148,19 @@ struct TraceArgs {
     const int* n_wave_map;
     bool keep_chunks;       // host only: a hit-count trace whose chunk counts the per-hit trace will reuse
     int chunk_shift, n_chunks;
-    int width;              // rays per packet: 64, or 32 / 16 for small batches of the modes that
-                            // cannot split a packet (lanes >= width re-trace the packet's last ray)
+    int width;              // rays per packet: 64, or 32 / 16 for small batches (lanes >= width
+                            // re-trace the packet's last ray)
     const float4* nodes;    // 4 x float4 per node
     int n_nodes;
     const int4* leaves;
     const int* root;
-    int* out_counts;        // MODE_COUNT
-    float* out_sums;        // MODE_CUMULATIVE
-    const int* offsets;     // MODE_HITS
+    int* out_counts;        // OUT_COUNTS; OUT_CLOSEST: the closest triangle's index (-1: none)
+    float* out_sums;        // OUT_SUMS, PRIM_F4
+    const int* offsets;     // OUT_HITS
     int* hit_idx;
-    float* hit_integral;
+    float* hit_integral;    // OUT_HITS, PRIM_F4
     float* hit_dist;
-    uint32_t* stats;        // MODE_STATS, 4 per ray
+    uint32_t* stats;        // OUT_STATS, 4 per ray
     int* status;            // set to GRACE_STACK_OVERFLOW on stack exhaustion
 };
 
@@ -129,7 +184,7 @@ struct CacheCtl {                 // device memory, one per cache
 };
 
 struct SceneKey {
-    int kind = -1;                // 0 float4 spheres, 1 triangles
+    Primitive kind = PRIM_F4;     // PRIM_F4 or PRIM_TRI (the fp64 modes' records are never cached)
     const void* prims = nullptr; const void* nodes = nullptr; const void* leaves = nullptr;
     size_t n_prims = 0, n_nodes = 0;
     bool operator==(const SceneKey& o) const
@@ -232,14 +287,14 @@ grace_status launch_signatures(const SigRequest& rq, unsigned long long* partial
 grace_status scene_release(TraceState& ts);
 // Buffers of the scene cache for `key` (replaces whatever is cached).
 grace_status scene_cache_alloc(TraceState& ts, const SceneKey& key);
-// Fills the scene-constant arrays (any of B1 / B50 / T64 may be null).  kind: 0 float4 spheres,
-// 1 triangles, 2 double4 spheres, 3 float4 spheres under the fp64 test (mixed precision).  run_if (device, optional): every kernel returns at once if
-// *run_if == 0.
-grace_status scene_fill(int kind, const void* prims, size_t n_prims, const float4* nodes,
+// Fills the scene-constant arrays (any of B1 / B50 / T64 may be null) for primitives of `kind`:
+// the double4 and mixed-precision records are float boxes that contain every sphere the fp64 test
+// can accept.  run_if (device, optional): every kernel returns at once if *run_if == 0.
+grace_status scene_fill(Primitive kind, const void* prims, size_t n_prims, const float4* nodes,
                         size_t n_nodes, const int4* leaves, float4* A, float2* B1, float2* B50,
                         double* T64, int2* node_prims, float4* C, hipStream_t stream,
                         const uint32_t* run_if = nullptr);
-grace_status scene_prepare(TraceState& ts, bool tri, const void* prims, size_t n_prims,
+grace_status scene_prepare(TraceState& ts, Primitive kind, const void* prims, size_t n_prims,
                            const int* d_nodes, size_t n_nodes, const int* d_leaves, hipStream_t stream);
 
 // trace_coherence.hip
