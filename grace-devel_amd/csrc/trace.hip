@@ -199,13 +199,13 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     if (class_split(MODE)) {
         // (column densities: a batch of exactly 16384 packets -- the 1024^2 frame -- still gets a
         // second wave per packet, 32768 waves; see choose_split.  Larger batches run one.)
-        const size_t wave_budget = (MODE == MODE_CUMULATIVE) ? 16385 : 16384;
+        const size_t wave_budget = f4_sums(MODE) ? 16385 : 16384;
         if (ts.split > 0) split = ts.split;
         else {
             while (split < SUM_CLASSES && size_t(n_packets) * split < wave_budget) split *= 2;
             // (the device picks the working waves per packet: scenes with spheres smaller than the ray
             // spacing want four -- see lat_split below --, one-direction batches two, others one)
-            if (MODE == MODE_CUMULATIVE && split > 1 && split < ts.lat_split && ts.ray_reorder && n_rays > 64
+            if (f4_sums(MODE) && split > 1 && split < ts.lat_split && ts.ray_reorder && n_rays > 64
                 && width == 64)
                 split = ts.lat_split;
         }
@@ -217,7 +217,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     const bool dev_split = f4_class_split(MODE) && split > 1 && ts.split <= 0;
     {
         constexpr bool need_b = f4_integrals(MODE);
-        const bool fast_b = MODE == MODE_CUMULATIVE && !ts.exact_integrals;
+        const bool fast_b = f4_sums(MODE) && !ts.exact_integrals;
         const bool reorder = ts.ray_reorder && n_rays > 64;
         // ---- which cached records does this call use?  (see trace_state.hpp) -------------------
         // NONE: derive into the workspace (a scene / batch seen for the first time);  FILL: the
@@ -264,7 +264,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
                                                    + Workspace::aligned(hit_packets * size_t(hit_chunks) * 4)
                                                    + 4 * Workspace::aligned(hit_packets * 4 + 64)
                                                    + Workspace::aligned(n_rays * 4) : 0)
-                                   + (MODE == MODE_CUMULATIVE ? Workspace::aligned(n_rays * SUM_CLASSES * 4) : 0)
+                                   + (f4_sums(MODE) ? Workspace::aligned(n_rays * SUM_CLASSES * channels(MODE) * 4) : 0)
                                    + (double_sums(MODE) ? Workspace::aligned(n_rays * SUM_CLASSES * 8) : 0)
                                    + (reorder ? 2 * Workspace::aligned(n_rays * 4)
                                                 + sort_ws_bytes(n_rays, 4, 0) : 0)
@@ -307,7 +307,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
                                  T64, node_prims, C, stream));
             a.A = A; a.B = B; a.T64 = T64; a.node_prims = node_prims; a.C = C;
         }
-        a.partial = (MODE == MODE_CUMULATIVE) ? Workspace::take<float>(n_rays * SUM_CLASSES) : nullptr;
+        a.partial = f4_sums(MODE) ? Workspace::take<float>(n_rays * SUM_CLASSES * channels(MODE)) : nullptr;
         a.partial_d = double_sums(MODE) ? Workspace::take<double>(n_rays * SUM_CLASSES) : nullptr;
         if (hits_split) {
             chunk_counts = Workspace::take<int>(n_rays * size_t(hit_chunks));
@@ -349,7 +349,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
             uint32_t* perm = Workspace::take<uint32_t>(n_rays);
             uint32_t* lat_flag = has_lattice(MODE) ? ext + 13 : nullptr;
             int* split_dev = dev_split ? reinterpret_cast<int*>(ext + 12) : nullptr;
-            const int split_flags = (MODE == MODE_CUMULATIVE) ? SPLIT_WIDE_BUDGET : 0;
+            const int split_flags = f4_sums(MODE) ? SPLIT_WIDE_BUDGET : 0;
             if (rays_cached) {
                 RayOrder& ro = ts.rays;
                 if (rays_use != USE_TRUST) {
@@ -435,9 +435,14 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
                                                                               nullptr, a.out_sums, a.lat_dev);
             GRACE_CHECK_LAUNCH();
         }
+        if (weighted(MODE)) {
+            combine_channel_classes_kernel<<<ceil_div(n_rays * channels(MODE), 256), 256, 0, stream>>>(
+                a.partial, int(n_rays), channels(MODE), ts.lat_split, nullptr, a.out_sums, a.out_stride, a.lat_dev);
+            GRACE_CHECK_LAUNCH();
+        }
         return GRACE_OK;
     };
-    if constexpr (MODE == MODE_CUMULATIVE) {
+    if constexpr (f4_sums(MODE)) {
         if (ts.exact_integrals) {
             if (split > 1) both(M_(), T(), F(), a);
             else if (lat_split) GRACE_TRY(one_or_split(F()));
@@ -516,6 +521,11 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     if (MODE == MODE_CUMULATIVE && split > 1) {
         combine_classes_kernel<float><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial, int(n_rays),
                                                                                  split, a.split_dev, a.out_sums);
+        GRACE_CHECK_LAUNCH();
+    }
+    if (weighted(MODE) && split > 1) {
+        combine_channel_classes_kernel<<<ceil_div(n_rays * channels(MODE), 256), 256, 0, stream>>>(
+            a.partial, int(n_rays), channels(MODE), split, a.split_dev, a.out_sums, a.out_stride);
         GRACE_CHECK_LAUNCH();
     }
     if (ts.timing) {
@@ -606,6 +616,36 @@ grace_status grace_trace_cumulative_f4(const void* d_rays, size_t n_rays, const 
     TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
     a.out_sums = d_cumulated;
     return launch_trace<MODE_CUMULATIVE>(a, n_rays, n_spheres, n_nodes, as_stream(stream));
+}
+
+// Weighted column densities (an extension): channels in groups of up to MAX_LAUNCH_CHANNELS, one
+// walk per group.
+grace_status grace_trace_cumulative_weighted_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                                size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                                const int* d_leaves, const int* d_root,
+                                                const float* d_weights, int n_channels, float* d_out,
+                                                grace_stream stream)
+{
+    GRACE_REQUIRE(n_channels >= 1 && n_channels <= 64, "trace_cumulative_weighted: channels must be 1..64");
+    if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
+    GRACE_REQUIRE(d_weights || n_spheres == 0, "trace_cumulative_weighted: null weights");
+    GRACE_REQUIRE(d_out, "trace_cumulative_weighted: null output");
+    GRACE_REQUIRE(n_rays * size_t(n_channels) < (size_t(1) << 31), "trace_cumulative_weighted: too many outputs");
+    for (int g = 0; g < n_channels; g += MAX_LAUNCH_CHANNELS) {
+        TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+        a.weights = d_weights + g;
+        a.w_stride = n_channels;
+        a.out_sums = d_out + g;
+        a.out_stride = n_channels;
+        const hipStream_t s = as_stream(stream);
+        switch (n_channels - g < MAX_LAUNCH_CHANNELS ? n_channels - g : MAX_LAUNCH_CHANNELS) {
+        case 1: GRACE_TRY(launch_trace<MODE_WCUM1>(a, n_rays, n_spheres, n_nodes, s)); break;
+        case 2: GRACE_TRY(launch_trace<MODE_WCUM2>(a, n_rays, n_spheres, n_nodes, s)); break;
+        case 3: GRACE_TRY(launch_trace<MODE_WCUM3>(a, n_rays, n_spheres, n_nodes, s)); break;
+        default: GRACE_TRY(launch_trace<MODE_WCUM4>(a, n_rays, n_spheres, n_nodes, s)); break;
+        }
+    }
+    return GRACE_OK;
 }
 
 grace_status grace_trace_hits_f4(const void* d_rays, size_t n_rays, const float* d_spheres,

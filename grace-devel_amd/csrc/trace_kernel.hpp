@@ -332,6 +332,14 @@ __device__ __forceinline__ bool cluster_may_hit(const float4 blo, const float4 b
     }
 }
 
+// A survivor's 1/h terms {x, y} with its staged weights (weighted sums; padded to even channels).
+template <int N>
+struct WeightedB {
+    float x, y;
+    float w[N + 1];
+    __device__ WeightedB(const float2 b) : x(b.x), y(b.y), w{} {}
+};
+
 // ALT selects the mode's alternative code path: the fast kernel integral of the column-density
 // trace, the LDS-staged outputs of the per-hit trace.
 // The class-split instantiations are held to 8 waves per SIMD (<= 64 VGPRs, <= 80 SGPRs: the
@@ -347,7 +355,12 @@ template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false>
 // VGPRs): left to itself the register allocator drifts between 77 and 102 VGPRs from one edit of
 // this file to the next, and at 5 waves per SIMD the frame kernel loses 20 % (2.9 -> 3.55 ms,
 // measured when an unrelated change tipped it over).
-__global__ __launch_bounds__(TRACE_BLOCK, f4_class_split(MODE) ? (SPLIT ? 8 : 6) : 1)
+// Weighted sums hold their class accumulators in LDS, 8 KB per channel per workgroup: with C
+// channels per launch the workgroups resident on a CU (160 KiB) allow 6, 5, 4, 3 waves per SIMD
+// for C = 1..4, and the bound asks for no more (a higher one would only cap the registers).
+__global__ __launch_bounds__(TRACE_BLOCK, !f4_class_split(MODE) ? 1
+                                          : weighted(MODE) ? (channels(MODE) == 1 ? 6 : 7 - channels(MODE))
+                                          : (SPLIT ? 8 : 6))
 void trace_kernel(const TraceArgs a)
 {
     static_assert(!ALT || f4_integrals(MODE), "no alternative path for this mode");
@@ -356,7 +369,13 @@ void trace_kernel(const TraceArgs a)
         if (a.lat_dev ? (*a.lat_dev != 0) != LAT : LAT) return;   // (workgroup-uniform)
         if (a.stage_dev && *a.stage_dev != a.stage_want) return;
     }
-    constexpr bool FAST = ALT && MODE == MODE_CUMULATIVE;
+    constexpr bool FAST = ALT && f4_sums(MODE);
+    // Weighted sums: NW channels per launch; each candidate's weights are fetched with its record
+    // and staged in WP extra planes of the tile (see the culling rounds).
+    constexpr bool WEIGHTED = weighted(MODE);
+    constexpr int NW = channels(MODE), WP = WEIGHTED ? (NW + 1) / 2 : 0;
+    // A survivor's 1/h terms -- and, weighted, its NW staged weights
+    using BRec = std::conditional_t<WEIGHTED, WeightedB<NW>, float2>;
     __shared__ double2 s_lut[FAST ? 1 : N_TABLE];
     // Fast integral: entry i = (y_i - i dy_i, dy_i), so that the lerp at table position b is ONE fma,
     // fma(dy_i, b, y_i - i dy_i) with i = int(b) -- no fractional part to extract.  Entries from
@@ -371,7 +390,8 @@ void trace_kernel(const TraceArgs a)
     // Three 8-byte planes per wave -- (x, y), (z, h^2), (1/h terms) -- so that one address
     // (plane base + 8 j) serves all of a survivor's reads through immediate offsets.
     // (66 slots: the survivor loop reads up to two slots past the round's last survivor)
-    __shared__ __align__(16) float2 s_tile[LDS_TILE ? TRACE_BLOCK / 64 : 1][LDS_TILE ? 3 : 1][LDS_TILE ? 66 : 1];
+    // Weighted sums add WP planes of staged weights (channels 2p, 2p + 1 in plane 3 + p).
+    __shared__ __align__(16) float2 s_tile[LDS_TILE ? TRACE_BLOCK / 64 : 1][LDS_TILE ? 3 + WP : 1][LDS_TILE ? 66 : 1];
     // *_D4 modes: the round's candidates as doubles, lane-indexed: {x, y, z, w w, 1/w, (1/w)^2}
     // (the division is done once per candidate by its lane, not once per survivor by the wave).
     __shared__ double s_tile_d[D4 ? TRACE_BLOCK / 64 : 1][D4 ? 64 : 1][D4 ? 6 : 1];
@@ -612,15 +632,17 @@ void trace_kernel(const TraceArgs a)
     int cur_chunk = -1;        // wave-uniform
     int count_at_chunk = 0;
     float sum = 0.f;        // accumulator of the current granule's class (MODE_CUMULATIVE)
-    // Class accumulators of this wave's lanes (one wave = one row of the workgroup's array).
-    constexpr bool CLASSES_F = MODE == MODE_CUMULATIVE, CLASSES_D = double_sums(MODE);
-    constexpr bool CLASSES = output(MODE) == OUT_SUMS;
-    __shared__ float s_class[CLASSES_F ? TRACE_BLOCK / 64 : 1][CLASSES_F ? SUM_CLASSES : 1][CLASSES_F ? 64 : 1];
+    float wsum[NW] = {};    // the same per channel (weighted sums)
+    // Class accumulators of this wave's lanes (one wave = one row of the workgroup's array);
+    // weighted sums: row class * NW + channel.
+    constexpr bool CLASSES_F = f4_sums(MODE), CLASSES_D = double_sums(MODE);
+    constexpr bool CLASSES = output(MODE) == OUT_SUMS || WEIGHTED;
+    __shared__ float s_class[CLASSES_F ? TRACE_BLOCK / 64 : 1][CLASSES_F ? SUM_CLASSES * NW : 1][CLASSES_F ? 64 : 1];
     __shared__ double s_class_d[CLASSES_D ? TRACE_BLOCK / 64 : 1][CLASSES_D ? SUM_CLASSES : 1][CLASSES_D ? 64 : 1];
     const int wv_acc = threadIdx.x >> 6;
     if (CLASSES_F) {
 #pragma unroll
-        for (int c = 0; c < SUM_CLASSES; ++c) s_class[wv_acc][c][lane] = 0.f;
+        for (int c = 0; c < SUM_CLASSES * NW; ++c) s_class[wv_acc][c][lane] = 0.f;
     }
     if (CLASSES_D) {
 #pragma unroll
@@ -632,14 +654,24 @@ void trace_kernel(const TraceArgs a)
     bool cur_owned = true;
     auto enter_granule = [&](const int prim) {
         if (cur_granule >= 0) {
+            if constexpr (WEIGHTED) {
+#pragma unroll
+                for (int c = 0; c < NW; ++c) s_class[wv_acc][(cur_granule & (SUM_CLASSES - 1)) * NW + c][lane] = wsum[c];
+            } else {
             if (CLASSES_D) s_class_d[wv_acc][cur_granule & (SUM_CLASSES - 1)][lane] = sum_d;
             else s_class[wv_acc][cur_granule & (SUM_CLASSES - 1)][lane] = sum;
+            }
         }
         cur_granule = prim >> GRANULE_SHIFT;
         cur_granule_end = (cur_granule + 1) << GRANULE_SHIFT;
         cur_owned = !SPLIT || owns_granule(cur_granule);
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int c = 0; c < NW; ++c) wsum[c] = s_class[wv_acc][(cur_granule & (SUM_CLASSES - 1)) * NW + c][lane];
+        } else {
         if (CLASSES_D) sum_d = s_class_d[wv_acc][cur_granule & (SUM_CLASSES - 1)][lane];
         else sum = s_class[wv_acc][cur_granule & (SUM_CLASSES - 1)][lane];
+        }
     };
     int write_at = 0;
     auto leave_chunk = [&]() {
@@ -942,6 +974,9 @@ void trace_kernel(const TraceArgs a)
             // lanes then hold a valid candidate and the tests need no control flow).
             // *_D4: the candidate's double4 record; *_F4D: the caller's float4 record, widened (exact)
             double4 mined_next = make_double4(0., 0., 0., 0.);
+            // Weighted sums: the candidate's weights, fetched lane-parallel with its record (the
+            // compacted survivor loop does not know a survivor's index).
+            float mw_next[NW] = {};
             // (Round 3, measured and rejected: buffer loads for the candidates -- a resource based at
             // the range's first cluster, the cluster as scalar offset, the lane as constant vector
             // offset: no per-round address arithmetic (six vector instructions) and no clamps, the
@@ -955,6 +990,10 @@ void trace_kernel(const TraceArgs a)
                 if (F4D) {
                     const float4 f = a.spheres[pj];
                     mined_next = make_double4(f.x, f.y, f.z, f.w);
+                }
+                if constexpr (WEIGHTED) {
+#pragma unroll
+                    for (int c = 0; c < NW; ++c) mw_next[c] = a.weights[size_t(pj) * a.w_stride + c];
                 }
             };
             // The range's clusters, 64 at a time: lane j decides for cluster cg + j whether ANY ray
@@ -1001,6 +1040,11 @@ void trace_kernel(const TraceArgs a)
                     const float4 mine = mine_next;
                     const float2 mineb = mineb_next;
                     const double4 mined = mined_next;
+                    float mw[NW];
+                    if constexpr (WEIGHTED) {
+#pragma unroll
+                        for (int c = 0; c < NW; ++c) mw[c] = mw_next[c];
+                    }
                     const bool more = cmask != 0ull;
                     if (more) {
                         cnext = cg + __builtin_ctzll(cmask);
@@ -1088,16 +1132,34 @@ void trace_kernel(const TraceArgs a)
                         ? int(__builtin_amdgcn_mbcnt_hi(uint32_t(rest >> 32),
                                                         __builtin_amdgcn_mbcnt_lo(uint32_t(rest), 0u)))
                         : lane;
+                    // Weighted sums stage per channel the weight (exact integral) or the weight folded
+                    // into 1/h^2, fl(w (1/h)^2) (fast integral: its terms then cost what the
+                    // unweighted ones do; fl(1 x) = x, so weights of one give the unweighted bits).
+                    float sw[NW + 3] = {};   // (zero padding: channels past NW of the second record)
+                    if constexpr (WEIGHTED) {
+#pragma unroll
+                        for (int c = 0; c < NW; ++c) sw[c] = FAST ? mw[c] * mineb.y : mw[c];
+                    }
                     if (LEAN4 && lean_round) {
                         // test-free round of an axis-aligned packet: all a survivor needs is the two
                         // perpendicular co-ordinates and the two 1/h terms -- ONE 16-byte record
+                        // (weighted: {.., w_0 / h^2}, channels 1.. in a second record 66 slots on)
                         const float s1 = AX == 0 ? mine.y : mine.x;
                         const float s2 = AX == 2 ? mine.y : mine.z;
+                        if constexpr (WEIGHTED) {
+                            if (keep) tile4[slot] = make_float4(s1, s2, mineb.x, sw[0]);
+                            if (NW > 1 && keep) tile4[66 + slot] = make_float4(sw[1], sw[2], sw[3], 0.f);
+                        } else {
                         if (keep) tile4[slot] = make_float4(s1, s2, mineb.x, mineb.y);
+                        }
                     } else if (!COMPACT || keep) {
                         s_tile[wv][0][slot] = make_float2(mine.x, mine.y);
                         s_tile[wv][LDS_TILE ? 1 : 0][slot] = make_float2(mine.z, mine.w);
                         if (NEED_B) s_tile[wv][LDS_TILE ? 2 : 0][slot] = mineb;
+                        if constexpr (WEIGHTED) {
+#pragma unroll
+                            for (int p = 0; p < WP; ++p) s_tile[wv][3 + p][slot] = make_float2(sw[2 * p], sw[2 * p + 1]);
+                        }
                     }
                 }
                 if (D4) {
@@ -1121,7 +1183,7 @@ void trace_kernel(const TraceArgs a)
 #endif
                 // One survivor: the packet's 64 rays against candidate jj (wave-uniform primitive
                 // index; 0 for the compacted tiles, which do not need it).
-                auto process = [&](auto lean_tag, const float4 s, const float2 sb, const int jj) {
+                auto process = [&](auto lean_tag, const float4 s, const BRec sb, const int jj) {
                     constexpr bool LEAN = decltype(lean_tag)::value;
                     if constexpr (D4) {
                         // sphere_hit<double4, double> (generic/intersect.h:16-54: ray members are
@@ -1268,7 +1330,13 @@ void trace_kernel(const TraceArgs a)
                             // round trip and the branch.
                             const float b = fminf(__builtin_amdgcn_sqrtf(b2) * sb.x, float(N_TABLE - 1));
                             const float2 y = s_lutf[static_cast<int>(b)];
-                            sum = __builtin_fmaf(__builtin_fmaf(y.y, b, y.x), sb.y, sum);
+                            if constexpr (WEIGHTED) {
+                                const float t = __builtin_fmaf(y.y, b, y.x);
+#pragma unroll
+                                for (int c = 0; c < NW; ++c) wsum[c] = __builtin_fmaf(t, sb.w[c], wsum[c]);
+                            } else {
+                                sum = __builtin_fmaf(__builtin_fmaf(y.y, b, y.x), sb.y, sum);
+                            }
                             return;
                         }
                         const bool hit = LEAN ? !(b2 >= s.w)
@@ -1281,6 +1349,13 @@ void trace_kernel(const TraceArgs a)
                         } else if (hit) {
                             const float w = FAST ? hit_integral_fast(b2, sb.x, s_lutf)
                                                  : hit_integral(b2, sb.x, sb.y, s_lut);
+                            if constexpr (WEIGHTED) {
+                                // fast: fma(I / (1/h^2), fl(w_c / h^2), sum); exact: the product
+                                // fl(w_c I) rounded on its own (no contraction), then added
+#pragma unroll
+                                for (int c = 0; c < NW; ++c)
+                                    wsum[c] = FAST ? __builtin_fmaf(w, sb.w[c], wsum[c]) : wsum[c] + sb.w[c] * w;
+                            } else {
                             if (FAST) {
                                 sum = __builtin_fmaf(w, sb.y, sum);
                             } else if (MODE == MODE_CUMULATIVE) {
@@ -1298,6 +1373,7 @@ void trace_kernel(const TraceArgs a)
                                 ++staged;
                                 ++write_at;
                             }
+                            }
                         }
                         if (STAGE_HITS && __builtin_amdgcn_ballot_w64(staged == HIT_CAP) != 0ull)
                             drain_hits();
@@ -1308,7 +1384,7 @@ void trace_kernel(const TraceArgs a)
                 // Issued UNCONDITIONALLY, up to two past the last survivor: lgkmcnt counts in
                 // order, so a fetch on only one of two merging paths makes the compiler wait for
                 // everything outstanding -- the just-issued reads included -- before each test.
-                auto fetch = [&](unsigned long long& td, int& k, float4& c, float2& cb, int& jj) {
+                auto fetch = [&](unsigned long long& td, int& k, float4& c, BRec& cb, int& jj) {
                     int at;
                     if (COMPACT) {
                         at = k++;
@@ -1322,7 +1398,18 @@ void trace_kernel(const TraceArgs a)
                         const float2 xy = s_tile[wv][0][at];
                         const float2 zw = s_tile[wv][LDS_TILE ? 1 : 0][at];
                         c = make_float4(xy.x, xy.y, zw.x, zw.y);
+                        if constexpr (WEIGHTED) {
+                            const float2 b = s_tile[wv][2][at];
+                            cb.x = b.x; cb.y = b.y;
+#pragma unroll
+                            for (int p = 0; p < WP; ++p) {
+                                const float2 wp = s_tile[wv][3 + p][at];
+                                cb.w[2 * p] = wp.x;
+                                cb.w[2 * p + 1] = wp.y;
+                            }
+                        } else {
                         if (NEED_B) cb = s_tile[wv][LDS_TILE ? 2 : 0][at];
+                        }
                         // Keep the reads here -- ahead of the survivors in between -- instead of
                         // letting the scheduler sink them next to their use.
                         __builtin_amdgcn_sched_barrier(0);
@@ -1334,7 +1421,7 @@ void trace_kernel(const TraceArgs a)
                     // Two survivors ahead, rotating through three register sets: each is loaded
                     // while the other two are being processed; no copies between survivors.
                     float4 c0, c1, c2;
-                    float2 b0 = make_float2(0.f, 0.f), b1 = b0, b2 = b0;
+                    BRec b0 = make_float2(0.f, 0.f), b1 = b0, b2 = b0;
                     int j0, j1 = 0, j2 = 0;
                     int left = __builtin_popcountll(todo);
                     unsigned long long td = todo | 0x8000000000000000ull;
@@ -1372,12 +1459,39 @@ void trace_kernel(const TraceArgs a)
                     float4 c0, c1, c2;
                     int left = __builtin_popcountll(todo);
                     const float4* t4 = tile4;
+                    if constexpr (WEIGHTED && NW > 1) {
+                        // weighted, several channels: the second record ({w_1, w_2, w_3} / h^2)
+                        // read beside the first, one survivor ahead
+                        float4 x0, x1;
+                        auto procw = [&](const float4 c, const float4 x) {
+                            const float q1 = c.x - o1, q2 = c.y - o2;
+                            float b = __builtin_amdgcn_sqrtf(__builtin_fmaf(q1, q1, q2 * q2)) * c.z;
+                            if (!FAT) b = fminf(b, float(N_TABLE - 1));
+                            const float2 y = s_lutf[static_cast<int>(b)];
+                            const float t = __builtin_fmaf(y.y, b, y.x);
+                            const float xw[4] = { c.w, x.x, x.y, x.z };
+#pragma unroll
+                            for (int ch = 0; ch < NW; ++ch) wsum[ch] = __builtin_fmaf(t, xw[ch], wsum[ch]);
+                        };
+                        c0 = t4[0]; x0 = t4[66]; __builtin_amdgcn_sched_barrier(0);
+                        for (;;) {
+                            c1 = t4[1]; x1 = t4[67]; __builtin_amdgcn_sched_barrier(0);
+                            procw(c0, x0);
+                            if (--left == 0) break;
+                            c0 = t4[2]; x0 = t4[68]; __builtin_amdgcn_sched_barrier(0);
+                            procw(c1, x1);
+                            if (--left == 0) break;
+                            t4 += 2;
+                        }
+                        return;
+                    }
                     auto proc = [&](const float4 c) {
                         const float q1 = c.x - o1, q2 = c.y - o2;
                         float b = __builtin_amdgcn_sqrtf(__builtin_fmaf(q1, q1, q2 * q2)) * c.z;
                         if (!FAT) b = fminf(b, float(N_TABLE - 1));
                         const float2 y = s_lutf[static_cast<int>(b)];
-                        sum = __builtin_fmaf(__builtin_fmaf(y.y, b, y.x), c.w, sum);
+                        if constexpr (WEIGHTED) wsum[0] = __builtin_fmaf(__builtin_fmaf(y.y, b, y.x), c.w, wsum[0]);
+                        else sum = __builtin_fmaf(__builtin_fmaf(y.y, b, y.x), c.w, sum);
                     };
                     c0 = t4[0]; __builtin_amdgcn_sched_barrier(0);
                     c1 = t4[1]; __builtin_amdgcn_sched_barrier(0);
@@ -1482,6 +1596,33 @@ void trace_kernel(const TraceArgs a)
                     s_class[wv_acc][c][lane] = x + y;
                 }
             a.partial[size_t(ray_index) * split + part] = s_class[wv_acc][own_lo][lane];
+        }
+    }
+    if constexpr (WEIGHTED) {
+        // per channel, the same class-ordered pairwise sum as MODE_CUMULATIVE's
+        if (cur_granule >= 0) {
+#pragma unroll
+            for (int c = 0; c < NW; ++c) s_class[wv_acc][(cur_granule & (SUM_CLASSES - 1)) * NW + c][lane] = wsum[c];
+        }
+#pragma unroll
+        for (int ch = 0; ch < NW; ++ch) {
+            if (!SPLIT) {
+                float t[SUM_CLASSES];
+#pragma unroll
+                for (int c = 0; c < SUM_CLASSES; ++c) t[c] = s_class[wv_acc][c * NW + ch][lane];
+#pragma unroll
+                for (int w = 1; w < SUM_CLASSES; w *= 2)
+#pragma unroll
+                    for (int c = 0; c < SUM_CLASSES; c += 2 * w) t[c] = t[c] + t[c + w];
+                a.out_sums[size_t(ray_index) * a.out_stride + ch] = t[0];
+            } else {
+                for (int w = 1; w < classes_per_part; w *= 2)
+                    for (int c = own_lo; c < own_hi; c += 2 * w) {
+                        const float x = s_class[wv_acc][c * NW + ch][lane], y = s_class[wv_acc][(c + w) * NW + ch][lane];
+                        s_class[wv_acc][c * NW + ch][lane] = x + y;
+                    }
+                a.partial[(size_t(ray_index) * NW + ch) * split + part] = s_class[wv_acc][own_lo * NW + ch][lane];
+            }
         }
     }
     if (MODE == MODE_STATS) {

@@ -27,6 +27,26 @@ __global__ __launch_bounds__(256) void combine_classes_kernel(const Real* __rest
     out[r] = t[0];
 }
 
+// The same for weighted sums: one thread per (ray, channel) of a launch's n_ch channels; partial is
+// [n_rays][n_ch][split], ray r's channel c goes to out[r out_stride + c].
+__global__ __launch_bounds__(256) void combine_channel_classes_kernel(const float* __restrict__ partial,
+                                                                      int n_rays, int n_ch, int split,
+                                                                      const int* __restrict__ split_dev,
+                                                                      float* __restrict__ out, int out_stride,
+                                                                      const int* __restrict__ run_if = nullptr)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rays * n_ch) return;
+    if (run_if && *run_if == 0) return;
+    if (split_dev) split = *split_dev;
+    const int r = i / n_ch, c = i - r * n_ch;
+    float t[SUM_CLASSES];
+    for (int k = 0; k < split; ++k) t[k] = partial[size_t(i) * split + k];
+    for (int w = 1; w < split; w *= 2)
+        for (int k = 0; k < split; k += 2 * w) t[k] = t[k] + t[k + w];
+    out[size_t(r) * out_stride + c] = t[0];
+}
+
 // Plan of the split per-hit trace.
 // (1) hits_offsets_kernel / hits_plan_kernel: each ray's chunk counts become output offsets
 //     (exclusive scan along the chunks, starting at the ray's own offset); the packet's running

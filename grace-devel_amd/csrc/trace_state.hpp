@@ -50,7 +50,10 @@ enum { MODE_COUNT = 0, MODE_CUMULATIVE = 1, MODE_HITS = 2, MODE_STATS = 3, MODE_
        // contain every sphere the fp64 test can accept (trace_prepass_f4d_kernel); each survivor is
        // tested in double from the caller's float4 record, its per-hit terms follow the reference's
        // promotions for that pair, and column densities are the class-ordered double sum.
-       MODE_COUNT_F4D = 8, MODE_CUM_F4D = 9, MODE_HITS_F4D = 10 };
+       MODE_COUNT_F4D = 8, MODE_CUM_F4D = 9, MODE_HITS_F4D = 10,
+       // Weighted column densities (an extension the reference lacks): float4 spheres, 1 to 4
+       // channels per launch, channel c of a ray = the class-ordered fp32 sum of fl(w[i][c] I_i).
+       MODE_WCUM1 = 11, MODE_WCUM2 = 12, MODE_WCUM3 = 13, MODE_WCUM4 = 14 };
 
 // What a mode does is its primitive and its output; every choice that depends on the mode is made
 // from these two (or the properties below), never from a list of modes.
@@ -59,9 +62,10 @@ enum Primitive { PRIM_F4 = 0,    // float4 spheres
                  PRIM_TRI = 1,   // triangles, 9 floats each
                  PRIM_D4 = 2,    // double4 spheres
                  PRIM_F4D = 3 }; // float4 spheres, double results
-enum Output { OUT_COUNTS, OUT_SUMS, OUT_HITS, OUT_STATS, OUT_CLOSEST };
+enum Output { OUT_COUNTS, OUT_SUMS, OUT_HITS, OUT_STATS, OUT_CLOSEST,
+              OUT_WSUMS };   // per-channel sums of weighted terms (TraceArgs::weights)
 
-struct ModeParts { Primitive prim; Output out; };
+struct ModeParts { Primitive prim; Output out; int channels = 1; };
 constexpr ModeParts mode_parts(const int mode)
 {
     switch (mode) {
@@ -76,26 +80,46 @@ constexpr ModeParts mode_parts(const int mode)
     case MODE_COUNT_F4D:  return { PRIM_F4D, OUT_COUNTS };
     case MODE_CUM_F4D:    return { PRIM_F4D, OUT_SUMS };
     case MODE_HITS_F4D:   return { PRIM_F4D, OUT_HITS };
+    case MODE_WCUM1:      return { PRIM_F4, OUT_WSUMS, 1 };
+    case MODE_WCUM2:      return { PRIM_F4, OUT_WSUMS, 2 };
+    case MODE_WCUM3:      return { PRIM_F4, OUT_WSUMS, 3 };
+    case MODE_WCUM4:      return { PRIM_F4, OUT_WSUMS, 4 };
     }
     __builtin_unreachable();   // (a mode missing above is no constant expression: trace_kernel fails to compile)
 }
 constexpr Primitive primitive(const int mode) { return mode_parts(mode).prim; }
 constexpr Output output(const int mode) { return mode_parts(mode).out; }
+// Output channels of a launch (weighted sums: 1 to 4; every other output: 1).
+constexpr int channels(const int mode) { return mode_parts(mode).channels; }
+constexpr int MAX_LAUNCH_CHANNELS = 4;
+constexpr bool weighted(const int mode) { return output(mode) == OUT_WSUMS; }
 
 // Each survivor is tested, and its results formed, in double from the caller's record (the walk
 // and every cull run on float records that contain those spheres).
 constexpr bool fp64(const int mode) { return primitive(mode) == PRIM_D4 || primitive(mode) == PRIM_F4D; }
 // Hit counts and column densities: summed by class, so a packet splits among waves by class.
-constexpr bool class_split(const int mode) { return output(mode) == OUT_COUNTS || output(mode) == OUT_SUMS; }
+constexpr bool class_split(const int mode)
+{
+    return output(mode) == OUT_COUNTS || output(mode) == OUT_SUMS || output(mode) == OUT_WSUMS;
+}
 // ... of float4 spheres: compacted survivor tiles, and the device-side choice of the working waves.
 constexpr bool f4_class_split(const int mode) { return class_split(mode) && primitive(mode) == PRIM_F4; }
+// Column densities (weighted or not) of float4 spheres: fp32 class sums (the fast integral, split
+// partials in float).
+constexpr bool f4_sums(const int mode)
+{
+    return primitive(mode) == PRIM_F4 && (output(mode) == OUT_SUMS || output(mode) == OUT_WSUMS);
+}
 // Column densities whose class sums are kept in double.
 constexpr bool double_sums(const int mode) { return output(mode) == OUT_SUMS && fp64(mode); }
 // A ray's result depends on the order its hits are met in (per-hit lists, closest hit): the packet
 // walks the tree in one wave.
 constexpr bool ordered(const int mode) { return output(mode) == OUT_HITS || output(mode) == OUT_CLOSEST; }
 // Kernel line integrals (the kernel table).
-constexpr bool integrates(const int mode) { return output(mode) == OUT_SUMS || output(mode) == OUT_HITS; }
+constexpr bool integrates(const int mode)
+{
+    return output(mode) == OUT_SUMS || output(mode) == OUT_WSUMS || output(mode) == OUT_HITS;
+}
 // ... in fp32: the 1/h records B, and the alternative (ALT) instantiations.
 constexpr bool f4_integrals(const int mode) { return integrates(mode) && primitive(mode) == PRIM_F4; }
 // Modes with an origin-lattice (LAT) instantiation.
@@ -162,6 +186,12 @@ struct TraceArgs {
     float* hit_dist;
     uint32_t* stats;        // OUT_STATS, 4 per ray
     int* status;            // set to GRACE_STACK_OVERFLOW on stack exhaustion
+    // OUT_WSUMS (appended: the fields above keep their offsets): the launch's first weight
+    // column and first output column; candidate i's weight of channel c is weights[i w_stride + c],
+    // ray r's sum of channel c goes to out_sums[r out_stride + c] (partial: [n_rays][channels][split]).
+    const float* weights;
+    int w_stride;
+    int out_stride;
 };
 
 

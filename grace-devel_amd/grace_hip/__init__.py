@@ -261,13 +261,18 @@ def min_max_components(data, n_comp, first=0):
     return lo, hi
 
 
-def build_tree(spheres, tree, low=None, high=None):
-    """tests/helper/tree.cuh:15-43: 30-bit keys, Euclidean deltas, sorts spheres in place."""
+def build_tree(spheres, tree, low=None, high=None, want_perm=False):
+    """tests/helper/tree.cuh:15-43: 30-bit keys, Euclidean deltas, sorts spheres in place.
+    want_perm=True returns (tree, perm) instead: perm[j] is the caller's index of the sphere now
+    at position j (int32, from the same sort), so per-particle data in the caller's order is
+    brought into tree order by data[perm]."""
     deltas = torch.empty(len(spheres) + 1, dtype=torch.float32, device=spheres.device)
-    morton_keys30_sort_sph(spheres, low, high)
+    keys = torch.empty(len(spheres), dtype=torch.int32, device=spheres.device)
+    morton_keys_sph(spheres, keys, low, high)
+    perm = sort_by_key(keys, spheres, 0, 30, want_perm=want_perm)
     euclidean_deltas_sph(spheres, deltas)
     ALBVH_sph(spheres, deltas, tree)
-    return tree
+    return (tree, perm) if want_perm else tree
 
 
 # ---------------------------------------------------------------------------------------
@@ -475,6 +480,33 @@ def trace_cumulative_sph(rays, spheres, tree, cumulated, check=False):
     if check:
         trace_status()
     return cumulated
+
+
+def trace_cumulative_weighted_sph(rays, spheres, tree, weights, out=None, check=False):
+    """Weighted, multi-channel column densities in one traversal (an extension the reference
+    lacks): out[r, c] = sum over ray r's hits i of fl32(weights[i, c] * I_ri), I_ri being the term
+    trace_cumulative_sph adds, summed per channel in its class order.  weights: float32 [n] or
+    [n, C] (1 <= C <= 64), in the order of `spheres` (tree order: see build_tree(want_perm=True));
+    out: float32 [n_rays] or [n_rays, C] to match (allocated if None).  Channels are traced four
+    at a time, each group a walk of its own."""
+    _check_rays(rays)
+    if weights.dtype != torch.float32:
+        raise ValueError("weights must be float32")
+    if weights.dim() not in (1, 2) or weights.shape[0] != len(spheres):
+        raise ValueError("weights must have shape [n_spheres] or [n_spheres, C]")
+    n_ch = 1 if weights.dim() == 1 else weights.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("weights must have 1..64 channels")
+    shape = (len(rays),) if weights.dim() == 1 else (len(rays), n_ch)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rays.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape:
+        raise ValueError("out must be float32 of shape %s" % (shape,))
+    _check(_lib.grace_trace_cumulative_weighted_f4(*_trace_args(rays, spheres, tree), _ptr(weights),
+                                                   C.c_int(n_ch), _ptr(out), _stream()))
+    if check:
+        trace_status()
+    return out
 
 
 INT32_MAX = 2 ** 31 - 1

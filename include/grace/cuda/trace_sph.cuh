@@ -182,6 +182,37 @@ GRACE_HOST void trace_cumulative_sph(
     detail::check_trace_status();
 }
 
+// Extension (the reference has no such call): weighted, multi-channel column densities in one
+// traversal -- grace_trace_cumulative_weighted_f4 (grace_hip.h).  d_weights holds n_channels
+// weights per sphere, sphere-major and in the order of d_spheres (the tree's sorted order);
+// d_cumulated[r * n_channels + c] is ray r's sum of fl(w[i][c] I_ri), I_ri being the term
+// trace_cumulative_sph adds.  Channels are traced four at a time, each group a walk of its own.
+template <typename Real4>
+GRACE_HOST void trace_cumulative_weighted_sph(
+    const thrust::device_vector<Ray>& d_rays,
+    const thrust::device_vector<Real4>& d_spheres,
+    const Tree& d_tree,
+    const thrust::device_vector<float>& d_weights,
+    const int n_channels,
+    thrust::device_vector<float>& d_cumulated)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_cumulative_weighted_sph: float4 spheres only (float weights and sums)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("trace_cumulative_weighted_sph: n_channels must be 1..64");
+    if (d_weights.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_cumulative_weighted_sph: d_weights must hold n_channels per sphere");
+    if (d_cumulated.size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_cumulative_weighted_sph: d_cumulated must hold n_channels per ray");
+    const detail::TreeArgs t = detail::tree_args(d_tree);
+    GRACE_STATUS_CHECK(grace_trace_cumulative_weighted_f4(
+        detail::raw(d_rays), d_rays.size(), reinterpret_cast<const float*>(detail::raw(d_spheres)),
+        d_spheres.size(), t.nodes, t.n_nodes, t.leaves, t.root, detail::raw(d_weights), n_channels,
+        detail::raw(d_cumulated), NULL));
+    detail::check_trace_status();
+}
+
 template <typename Real4, typename IndexType, typename Real>
 GRACE_HOST void trace_sph(
     const thrust::device_vector<Ray>& d_rays,

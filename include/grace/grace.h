@@ -30,6 +30,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "grace_hip.h"
@@ -619,6 +620,32 @@ inline void trace_cumulative_sph(const device_vector<Ray>& d_rays,
                                                 d_spheres.size(), &d_tree.nodes.data()->x,
                                                 d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
                                                 d_tree.root_index_ptr, d_cumulated.data(), nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
+// Extension (the reference has no such call): weighted, multi-channel column densities in one
+// traversal (grace_trace_cumulative_weighted_f4, grace_hip.h): d_cumulated[r * n_channels + c] =
+// sum over ray r's hits i of fl(d_weights[i * n_channels + c] * I_ri), spheres in tree order.
+template <typename Real4>
+inline void trace_cumulative_weighted_sph(const device_vector<Ray>& d_rays,
+                                          const device_vector<Real4>& d_spheres, const Tree& d_tree,
+                                          const device_vector<float>& d_weights, int n_channels,
+                                          device_vector<float>& d_cumulated)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_cumulative_weighted_sph: float4 spheres only (float weights and sums)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("trace_cumulative_weighted_sph: n_channels must be 1..64");
+    if (d_weights.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_cumulative_weighted_sph: d_weights must hold n_channels per sphere");
+    if (d_cumulated.size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_cumulative_weighted_sph: d_cumulated must hold n_channels per ray");
+    detail::check(grace_trace_cumulative_weighted_f4(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                                     d_spheres.size(), &d_tree.nodes.data()->x,
+                                                     d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                                     d_tree.root_index_ptr, d_weights.data(), n_channels,
+                                                     d_cumulated.data(), nullptr));
     detail::check(grace_trace_status(nullptr));
 }
 

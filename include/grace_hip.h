@@ -260,6 +260,24 @@ grace_status grace_trace_cumulative_f4(const void* d_rays, size_t n_rays, const 
                                        size_t n_spheres, const int* d_nodes, size_t n_nodes,
                                        const int* d_leaves, const int* d_root,
                                        float* d_cumulated, grace_stream stream);
+/* Weighted, multi-channel column densities -- an extension the reference lacks: the terms of
+ * OnHit_sphere_cumulate (functors/trace.cuh:164-186) scaled as multiply_by_weights scales per-hit
+ * integrals (kernels/weights.cuh:12-50), summed per ray without writing any hit:
+ *   d_out[r * n_channels + c] = sum over hits i of ray r of fl32(d_weights[i * n_channels + c] * I_ri)
+ * where I_ri is the term grace_trace_cumulative_f4 adds for that (ray, sphere) pair and i indexes
+ * d_spheres as passed (the tree's sorted order).  Each channel is summed in the same class-ordered
+ * fp32 order as grace_trace_cumulative_f4.  Exact mode (grace_trace_set_exact_integrals(1)): I_ri is
+ * the reference's per-hit integral and the result is that sum bit for bit.  Default mode: within
+ * 1e-5 of sum |w| I of the fp64 sum (the weight is folded into the term's 1/h^2 factor).  Weights of
+ * 1.0f give grace_trace_cumulative_f4's bits in both modes.  1 <= n_channels <= 64; channels are
+ * traced four at a time, each group of four a walk of its own.  Weights are read on every call
+ * (never cached).  GRACE_INVALID_ARGUMENT for n_channels outside 1..64 or null weights; zero rays:
+ * GRACE_OK, nothing written. */
+grace_status grace_trace_cumulative_weighted_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                                size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                                const int* d_leaves, const int* d_root,
+                                                const float* d_weights, int n_channels, float* d_out,
+                                                grace_stream stream);
 /* Per-hit outputs written from d_ray_offsets[ray] (RayEntry_from_array +
  * OnHit_sphere_individual, include/grace/cuda/functors/trace.cuh:44-60,196-235). */
 grace_status grace_trace_hits_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
