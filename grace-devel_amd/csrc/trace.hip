@@ -84,14 +84,22 @@
 // Roofline: divergent tree walk, integer/fp32 scalar-operand work -- no MFMA.  Algorithmic
 // bytes per ray: 28 + 64 * nodes + 16 * leaves + 16 * spheres tested + 4,
 // counted per ray by the `stats` instantiation below.
+#include "kernel_tables.hpp"
 #include "trace_kernel.hpp"
 #include "trace_plan.hpp"
 
+#include <cmath>
 #include <cstdlib>
 
 using namespace grace_hip;
 
 namespace grace_hip {
+
+// The built-in SPH kernels' line-integral tables (kernel_tables.hpp, GRACE_SPH_KERNEL_* order): one
+// device array, whose rows a context's trace calls point to, and its host copy.
+static_assert(GRACE_SPH_KERNEL_TABLE_ROWS == GRACE_SPH_KERNEL_WENDLAND_C6 + 1, "one table per built-in kernel");
+__device__ double g_sph_kernel_tables[GRACE_SPH_KERNEL_TABLE_ROWS][N_TABLE] = GRACE_SPH_KERNEL_TABLES_INIT;
+static const double k_sph_kernel_tables[GRACE_SPH_KERNEL_TABLE_ROWS][N_TABLE] = GRACE_SPH_KERNEL_TABLES_INIT;
 
 static grace_status trace_state_destroy(Context& c)
 {
@@ -100,6 +108,7 @@ static grace_status trace_state_destroy(Context& c)
     GRACE_TRY(scene_release(ts));
     GRACE_TRY(rays_release(ts));
     if (ts.hits.chunk_counts) GRACE_TRY_HIP(hipFree(ts.hits.chunk_counts));
+    if (ts.custom_table) GRACE_TRY_HIP(hipFree(ts.custom_table));
     if (ts.status) GRACE_TRY_HIP(hipFree(ts.status));
     if (ts.ev0) GRACE_TRY_HIP(hipEventDestroy(ts.ev0));
     if (ts.ev1) GRACE_TRY_HIP(hipEventDestroy(ts.ev1));
@@ -113,7 +122,11 @@ grace_status trace_state(TraceState** out)
     Context* c = nullptr;
     GRACE_TRY(current_context(&c));
     if (!c->trace) {
+        void* tables = nullptr;     // on the context's device, which is the current one
+        GRACE_TRY_HIP(hipGetSymbolAddress(&tables, HIP_SYMBOL(g_sph_kernel_tables)));
         c->trace = new TraceState();
+        c->trace->builtin_tables = static_cast<const double*>(tables);
+        c->trace->kernel_table = c->trace->builtin_tables + GRACE_SPH_KERNEL_CUBIC * N_TABLE;
         g_trace_state_destroy = trace_state_destroy;
     }
     *out = c->trace;
@@ -145,6 +158,7 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     GRACE_TRY(trace_state(&ts_ptr));
     TraceState& ts = *ts_ptr;
     GRACE_TRY(ensure_status(ts, stream));
+    a.kernel_table = ts.kernel_table;     // this call's table, whatever the context selects later
     FrameGuard frame;
     // Split per-hit trace for small batches (see TraceArgs / hits_plan_kernel): chunk size =
     // a power of two >= one granule giving at most MAX_HIT_CHUNKS chunks.
@@ -784,8 +798,20 @@ grace_status grace_hit_integrals_f32(const float* d_b2, const float* d_h, size_t
 {
     GRACE_REQUIRE(n == 0 || (d_b2 && d_h && d_out), "hit_integrals: null pointer");
     if (n == 0) return GRACE_OK;
-    hit_integrals_kernel<<<stream_grid(n, 256), 256, 0, as_stream(stream)>>>(d_b2, d_h, n, d_out);
+    TraceState* ts = nullptr;
+    GRACE_TRY(trace_state(&ts));
+    hit_integrals_kernel<<<stream_grid(n, 256), 256, 0, as_stream(stream)>>>(d_b2, d_h, n, d_out,
+                                                                             ts->kernel_table);
     GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+grace_status grace_sph_kernel_table(int kind, double* h_out51)
+{
+    GRACE_REQUIRE(kind >= GRACE_SPH_KERNEL_CUBIC && kind <= GRACE_SPH_KERNEL_WENDLAND_C6,
+                  "sph_kernel_table: kind must be a built-in GRACE_SPH_KERNEL_* (0..5)");
+    GRACE_REQUIRE(h_out51, "sph_kernel_table: null output");
+    for (int i = 0; i < N_TABLE; ++i) h_out51[i] = k_sph_kernel_tables[kind][i];
     return GRACE_OK;
 }
 
@@ -886,6 +912,48 @@ grace_status grace_trace_set_exact_integrals(int enabled)
 {
     GRACE_TRACE_STATE();
     ts.exact_integrals = enabled != 0;
+    return GRACE_OK;
+}
+
+grace_status grace_trace_set_sph_kernel(int kind)
+{
+    GRACE_REQUIRE(kind >= GRACE_SPH_KERNEL_CUBIC && kind <= GRACE_SPH_KERNEL_WENDLAND_C6,
+                  "set_sph_kernel: kind must be a built-in GRACE_SPH_KERNEL_* (0..5); a custom table is "
+                  "set with grace_trace_set_sph_kernel_table");
+    GRACE_TRACE_STATE();
+    ts.sph_kernel = kind;
+    ts.kernel_table = ts.builtin_tables + kind * N_TABLE;
+    return GRACE_OK;
+}
+
+grace_status grace_trace_set_sph_kernel_table(const double* h_table, int n)
+{
+    GRACE_REQUIRE(h_table && n == N_TABLE, "set_sph_kernel_table: the table must hold 51 values");
+    for (int i = 0; i < N_TABLE; ++i)
+        GRACE_REQUIRE(std::isfinite(h_table[i]) && h_table[i] >= 0.0,
+                      "set_sph_kernel_table: every value must be finite and >= 0");
+    GRACE_REQUIRE(h_table[N_TABLE - 1] == 0.0, "set_sph_kernel_table: the last value (b = H) must be 0");
+    GRACE_TRACE_STATE();
+    // Calls already queued may read the buffer: let them finish before it is overwritten.
+    GRACE_TRY_HIP(hipDeviceSynchronize());
+    if (!ts.custom_table)
+        GRACE_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&ts.custom_table), N_TABLE * sizeof(double)));
+    GRACE_TRY_HIP(hipMemcpy(ts.custom_table, h_table, N_TABLE * sizeof(double), hipMemcpyHostToDevice));
+    for (int i = 0; i < N_TABLE; ++i) ts.custom_host[i] = h_table[i];
+    ts.sph_kernel = GRACE_SPH_KERNEL_CUSTOM;
+    ts.kernel_table = ts.custom_table;
+    return GRACE_OK;
+}
+
+grace_status grace_trace_get_sph_kernel(int* h_kind, double* h_table51)
+{
+    GRACE_TRACE_STATE();
+    if (h_kind) *h_kind = ts.sph_kernel;
+    if (h_table51) {
+        const double* t = ts.sph_kernel == GRACE_SPH_KERNEL_CUSTOM ? ts.custom_host
+                                                                   : k_sph_kernel_tables[ts.sph_kernel];
+        for (int i = 0; i < N_TABLE; ++i) h_table51[i] = t[i];
+    }
     return GRACE_OK;
 }
 

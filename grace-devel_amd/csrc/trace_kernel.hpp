@@ -11,26 +11,6 @@ namespace {
 
 using namespace grace_hip;
 
-// include/grace/cuda/trace_sph.cuh:32-48
-__constant__ double c_kernel_table[N_TABLE] = {
-    1.90986019771937, 1.90563449910964, 1.89304415940934, 1.87230928086763,
-    1.84374947679902, 1.80776276033034, 1.76481079856299, 1.71540816859939,
-    1.66011373131439, 1.59952322363667, 1.53426266082279, 1.46498233888091,
-    1.39235130929287, 1.31705223652377, 1.23977618317103, 1.16121278415369,
-    1.08201943664419, 1.00288866679720, 0.924475767210246, 0.847415371038733,
-    0.772316688105931, 0.699736940377312, 0.630211918937167, 0.564194562399538,
-    0.502076205853037, 0.444144023534733, 0.390518196140658, 0.341148855945766,
-    0.295941946237307, 0.254782896476983, 0.217538645099225, 0.184059547649710,
-    0.154181189781890, 0.127726122453554, 0.104505535066266,
-    8.432088120445191E-002, 6.696547102921641E-002, 5.222604427168923E-002,
-    3.988433820097490E-002, 2.971866601747601E-002, 2.150552303075515E-002,
-    1.502124104014533E-002, 1.004371608622562E-002, 6.354242122978656E-003,
-    3.739494884706115E-003, 1.993729589156428E-003, 9.212900163813992E-004,
-    3.395908945333921E-004, 8.287326418242995E-005, 7.387919939044624E-006,
-    0.000000000000000E+000
-};
-
-
 __device__ __forceinline__ bool any_lane(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 
 // Integer min/max on float bit patterns, as the reference's vmin/vmax PTX
@@ -160,12 +140,13 @@ __device__ __forceinline__ bool tri_intersect(const double ddx, const double ddy
 // traversal would produce: zeros, denormals, b2 -> h^2, huge/small h).
 __global__ __launch_bounds__(256) void hit_integrals_kernel(const float* __restrict__ b2,
                                                             const float* __restrict__ h, size_t n,
-                                                            float* __restrict__ out)
+                                                            float* __restrict__ out,
+                                                            const double* __restrict__ table)
 {
     __shared__ double2 s_lut[N_TABLE];
     if (threadIdx.x < N_TABLE) {
-        const double y0 = c_kernel_table[threadIdx.x];
-        const double y1 = threadIdx.x + 1 < N_TABLE ? c_kernel_table[threadIdx.x + 1] : y0;
+        const double y0 = table[threadIdx.x];
+        const double y1 = threadIdx.x + 1 < N_TABLE ? table[threadIdx.x + 1] : y0;
         s_lut[threadIdx.x] = make_double2(y0, y1 - y0);
     }
     __syncthreads();
@@ -421,14 +402,14 @@ void trace_kernel(const TraceArgs a)
             static_assert(TRACE_BLOCK >= 256, "one table entry per thread");
             float2 e = make_float2(0.f, 0.f);
             if (threadIdx.x < N_TABLE - 1) {
-                const double y0 = c_kernel_table[threadIdx.x], dy = c_kernel_table[threadIdx.x + 1] - y0;
+                const double y0 = a.kernel_table[threadIdx.x], dy = a.kernel_table[threadIdx.x + 1] - y0;
                 e = make_float2(float(y0 - double(threadIdx.x) * dy), float(dy));
             }
             if (threadIdx.x < LUTF_N) s_lutf[threadIdx.x] = e;
         } else if (threadIdx.x < N_TABLE) {
             const int i0 = threadIdx.x;
-            const double y0 = c_kernel_table[i0];
-            const double y1 = i0 + 1 < N_TABLE ? c_kernel_table[i0 + 1] : y0;
+            const double y0 = a.kernel_table[i0];
+            const double y1 = i0 + 1 < N_TABLE ? a.kernel_table[i0 + 1] : y0;
             s_lut[threadIdx.x] = make_double2(y0, y1 - y0);
         }
         __syncthreads();

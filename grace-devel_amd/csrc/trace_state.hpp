@@ -192,6 +192,10 @@ struct TraceArgs {
     const float* weights;
     int w_stride;
     int out_stride;
+    // Integrating outputs (appended as well): the SPH kernel's 51-entry line-integral table, device
+    // memory (a row of the built-in tables, or the context's custom table).  Captured when the call
+    // is enqueued; the prologue copies it into LDS (s_lut / s_lutf) and nothing else reads it.
+    const double* kernel_table;
 };
 
 
@@ -286,6 +290,14 @@ struct TraceState {
     bool hits_stage_split = true;          // split per-hit walk: stage heavy packets' hits in LDS
     bool cache_validation = true;          // validate cached records by signature before every use
     bool cache_auto = true;                // cache the records of a scene / ray batch seen twice in a row
+    // SPH kernel (grace_trace_set_sph_kernel*): GRACE_SPH_KERNEL_* (-1: custom) and its device table,
+    // a row of the built-in tables (set when the state is created) or custom_table.  Only ever
+    // copied into TraceArgs::kernel_table: no cached record depends on it.
+    int sph_kernel = 0;
+    const double* builtin_tables = nullptr;  // device address of the built-in tables, [6][N_TABLE]
+    const double* kernel_table = nullptr;
+    double* custom_table = nullptr;          // N_TABLE doubles, allocated by the first custom table
+    double custom_host[N_TABLE] = {};        // its host copy (grace_trace_get_sph_kernel)
     Scene scene;
     RayOrder rays;
     HitsCache hits;

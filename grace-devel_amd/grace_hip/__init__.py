@@ -329,6 +329,52 @@ def set_exact_integrals(enabled):
     _check(_lib.grace_trace_set_exact_integrals(C.c_int(1 if enabled else 0)))
 
 
+# SPH kernels of the integrating traces (include/grace_hip.h, GRACE_SPH_KERNEL_*); the sphere's w is
+# the kernel's support radius H.
+SPH_KERNELS = ("cubic", "quartic", "quintic", "wendland_c2", "wendland_c4", "wendland_c6")
+SPH_KERNEL_CUSTOM = -1
+
+
+def _kernel_kind(name):
+    if name not in SPH_KERNELS:
+        raise ValueError("unknown SPH kernel %r (one of %s)" % (name, ", ".join(SPH_KERNELS)))
+    return SPH_KERNELS.index(name)
+
+
+def sph_kernel_table(name):
+    """A built-in kernel's 51 line integrals F_i = int f(sqrt((i/50)^2 + z^2)) dz (support radius 1),
+    float64.  Host only: needs no device."""
+    out = (C.c_double * N_TABLE)()
+    _check(_lib.grace_sph_kernel_table(C.c_int(_kernel_kind(name)), out))
+    return np.array(out, np.float64)
+
+
+def set_sph_kernel(kernel):
+    """The current context's SPH kernel for every integrating trace (column densities, weighted sums,
+    per-hit integrals, hit_integrals): a name of SPH_KERNELS, or a table of 51 float64 values (finite,
+    >= 0, the last one 0).  Selecting a name switches a pointer; a table is copied to the device
+    after a device synchronisation (queued traces may still read the previous one).  ValueError
+    for anything else; the active kernel is then left as it was.  Calls already enqueued keep
+    the kernel they were enqueued with."""
+    if isinstance(kernel, str):
+        _check(_lib.grace_trace_set_sph_kernel(C.c_int(_kernel_kind(kernel))))
+        return
+    t = np.asarray(kernel)
+    if t.dtype.kind not in "fiu" or t.ndim != 1:
+        raise ValueError("an SPH kernel table must be a 1-D array of 51 numbers")
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    _check(_lib.grace_trace_set_sph_kernel_table(t.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(len(t))))
+
+
+def sph_kernel():
+    """(name, float64 table) of the current context's SPH kernel; name is "custom" for a caller's table."""
+    kind = C.c_int(0)
+    out = (C.c_double * N_TABLE)()
+    _check(_lib.grace_trace_get_sph_kernel(C.byref(kind), out))
+    name = "custom" if kind.value == SPH_KERNEL_CUSTOM else SPH_KERNELS[kind.value]
+    return name, np.array(out, np.float64)
+
+
 def set_cache_validation(enabled):
     """1 (default): cached scene / ray records are validated by signature before every use."""
     _check(_lib.grace_trace_set_cache_validation(C.c_int(1 if enabled else 0)))

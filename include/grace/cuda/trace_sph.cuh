@@ -23,8 +23,11 @@
 #include "grace/detail/raw.h"
 #include "grace/ray.h"
 
+#include <array>
 #include <limits>
+#include <stdexcept>
 #include <type_traits>
+#include <vector>
 
 namespace grace {
 
@@ -211,6 +214,43 @@ GRACE_HOST void trace_cumulative_weighted_sph(
         d_spheres.size(), t.nodes, t.n_nodes, t.leaves, t.root, detail::raw(d_weights), n_channels,
         detail::raw(d_cumulated), NULL));
     detail::check_trace_status();
+}
+
+// Extension (the reference has no such choice): the SPH kernel of every integrating trace --
+// column densities, weighted sums, the per-hit integrals of trace_sph / trace_with_sentinels_sph
+// (grace_trace_set_sph_kernel*, grace_hip.h).  A sphere's w is the kernel's support radius H.  A
+// per-context knob: the reference-signature calls above and below keep their signatures and use
+// the kernel selected when they run.  Default SphKernel::cubic, the reference's table (N_table
+// values above).  set_sph_kernel_table takes 51 values (finite, >= 0, the last one 0), else
+// std::invalid_argument with the active kernel unchanged; it synchronises the device before it
+// overwrites the context's table buffer.  sph_kernel_table gives a built-in kernel's values, for
+// instance for an OnHit_sphere_cumulate-style functor of the generic trace.
+enum class SphKernel {
+    cubic = GRACE_SPH_KERNEL_CUBIC,
+    quartic = GRACE_SPH_KERNEL_QUARTIC,
+    quintic = GRACE_SPH_KERNEL_QUINTIC,
+    wendland_c2 = GRACE_SPH_KERNEL_WENDLAND_C2,
+    wendland_c4 = GRACE_SPH_KERNEL_WENDLAND_C4,
+    wendland_c6 = GRACE_SPH_KERNEL_WENDLAND_C6
+};
+
+GRACE_HOST void set_sph_kernel(const SphKernel kernel)
+{
+    GRACE_STATUS_CHECK(grace_trace_set_sph_kernel(static_cast<int>(kernel)));
+}
+
+GRACE_HOST void set_sph_kernel_table(const std::vector<double>& table)
+{
+    if (table.size() != size_t(N_table))
+        throw std::invalid_argument("set_sph_kernel_table: the table must hold 51 values");
+    GRACE_STATUS_CHECK(grace_trace_set_sph_kernel_table(table.data(), int(table.size())));
+}
+
+GRACE_HOST std::array<double, N_table> sph_kernel_table(const SphKernel kernel)
+{
+    std::array<double, N_table> t;
+    GRACE_STATUS_CHECK(grace_sph_kernel_table(static_cast<int>(kernel), t.data()));
+    return t;
 }
 
 template <typename Real4, typename IndexType, typename Real>

@@ -27,6 +27,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <array>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -314,6 +315,43 @@ inline void trace_cumulative_sph(const device_vector<Ray>& d_rays,
                                             d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
                                             d_tree.root_index_ptr, d_cumulated.data(), nullptr));
     detail::check(grace_trace_status(nullptr));
+}
+
+// Extension (the reference has no such choice): the SPH kernel of every integrating trace --
+// column densities, weighted sums, the per-hit integrals of trace_sph / trace_with_sentinels_sph
+// (grace_trace_set_sph_kernel*, grace_hip.h).  A sphere's w is the kernel's support radius H.  A
+// per-context knob: the reference-signature calls above and below keep their signatures and use
+// the kernel selected when they run.  Default SphKernel::cubic, the reference's table (the
+// N_table values of trace_sph.cuh).  set_sph_kernel_table takes 51 values (finite, >= 0, the last
+// one 0), else std::invalid_argument with the active kernel unchanged; it synchronises the device
+// before it overwrites the context's table buffer.  sph_kernel_table gives a built-in kernel's values, for
+// instance for an OnHit_sphere_cumulate-style functor of the generic trace.
+enum class SphKernel {
+    cubic = GRACE_SPH_KERNEL_CUBIC,
+    quartic = GRACE_SPH_KERNEL_QUARTIC,
+    quintic = GRACE_SPH_KERNEL_QUINTIC,
+    wendland_c2 = GRACE_SPH_KERNEL_WENDLAND_C2,
+    wendland_c4 = GRACE_SPH_KERNEL_WENDLAND_C4,
+    wendland_c6 = GRACE_SPH_KERNEL_WENDLAND_C6
+};
+
+inline void set_sph_kernel(SphKernel kernel)
+{
+    detail::check(grace_trace_set_sph_kernel(static_cast<int>(kernel)));
+}
+
+inline void set_sph_kernel_table(const std::vector<double>& table)
+{
+    if (table.size() != 51)
+        throw std::invalid_argument("set_sph_kernel_table: the table must hold 51 values");
+    detail::check(grace_trace_set_sph_kernel_table(table.data(), int(table.size())));
+}
+
+inline std::array<double, 51> sph_kernel_table(SphKernel kernel)
+{
+    std::array<double, 51> t;
+    detail::check(grace_sph_kernel_table(static_cast<int>(kernel), t.data()));
+    return t;
 }
 
 // trace_sph.cuh:112-168

@@ -296,7 +296,8 @@ grace_status grace_trace_stats_f4(const void* d_rays, size_t n_rays, const float
 
 /* The per-hit kernel integral of OnHit_sphere_cumulate / OnHit_sphere_individual
  * (include/grace/cuda/functors/trace.cuh:181-186, 221-224) evaluated on arrays:
- * out[i] = lerp(50 * sqrt(b2[i]) / h[i], table) / h[i]^2, bit-for-bit the traversal's value. */
+ * out[i] = lerp(50 * sqrt(b2[i]) / h[i], table) / h[i]^2, bit-for-bit the traversal's value, with
+ * the context's SPH kernel table (grace_trace_set_sph_kernel). */
 grace_status grace_hit_integrals_f32(const float* d_b2, const float* d_h, size_t n, float* d_out,
                                      grace_stream stream);
 
@@ -338,6 +339,39 @@ grace_status grace_trace_set_packet_width(int rays_per_packet);
  * the result is then bit-identical to the CPU oracle's class-ordered sum, ~20 % slower.
  * The per-hit outputs (grace_trace_hits_f4, grace_hit_integrals_f32) always use the latter. */
 grace_status grace_trace_set_exact_integrals(int enabled);
+
+/* ---- SPH kernel of the integrating traces (not part of the reference API) -----------------------
+ * A sphere's w is the kernel's support radius H: W(r, H) = H^-3 f(r / H), zero for r >= H, with
+ * 4 pi int_0^1 f(q) q^2 dq = 1.  Every integrating trace -- the column densities of
+ * grace_trace_cumulative_f4 / _d4 / _f4_f64 and _weighted_f4, the per-hit integrals of
+ * grace_trace_hits_f4 / _d4 / _f4_f64, and grace_hit_integrals_f32 -- adds, per hit,
+ * lerp(F, 50 sqrt(b^2) / H) / H^2 with the same operations in every mode; F is the kernel's table of
+ * 51 line integrals F_i = int f(sqrt((i/50)^2 + z^2)) dz over the whole chord, F_50 = 0.  Hit
+ * counts, stats and closest-triangle traces do not use it.  The kernel is a per-context knob; a
+ * trace call uses the table selected when it is enqueued.  Default: GRACE_SPH_KERNEL_CUBIC, the
+ * reference's cubic spline (M4) table bit for bit.  The other built-in tables are the exact
+ * integrals of their kernels (INTEGRATION.md lists them and their lerp's volume bias). */
+#define GRACE_SPH_KERNEL_CUSTOM      (-1)
+#define GRACE_SPH_KERNEL_CUBIC       0
+#define GRACE_SPH_KERNEL_QUARTIC     1   /* M5 */
+#define GRACE_SPH_KERNEL_QUINTIC     2   /* M6 */
+#define GRACE_SPH_KERNEL_WENDLAND_C2 3
+#define GRACE_SPH_KERNEL_WENDLAND_C4 4
+#define GRACE_SPH_KERNEL_WENDLAND_C6 5
+/* Selects a built-in kernel (0..5): only switches a pointer, no synchronisation.
+ * GRACE_INVALID_ARGUMENT for anything else (GRACE_SPH_KERNEL_CUSTOM included). */
+grace_status grace_trace_set_sph_kernel(int kind);
+/* Selects a caller's table of n == 51 host doubles, every one finite and >= 0, the last one 0.
+ * The table is copied to a device buffer of the context; the call SYNCHRONISES THE DEVICE first
+ * (hipDeviceSynchronize), because trace calls still queued may read the buffer it overwrites.
+ * Anything else: GRACE_INVALID_ARGUMENT, and the active kernel stays unchanged. */
+grace_status grace_trace_set_sph_kernel_table(const double* h_table, int n);
+/* The active kernel: its GRACE_SPH_KERNEL_* (GRACE_SPH_KERNEL_CUSTOM for a caller's table) and its
+ * 51 values.  Either pointer may be NULL. */
+grace_status grace_trace_get_sph_kernel(int* h_kind, double* h_table51);
+/* A built-in kernel's 51 values (0..5, else GRACE_INVALID_ARGUMENT).  Host only: needs no context
+ * and no device. */
+grace_status grace_sph_kernel_table(int kind, double* h_out51);
 
 /* Subtrees with at most this many primitives are swept -- one test per cluster of 64 consecutive
  * primitives, then culling rounds over the surviving clusters -- instead of being descended
