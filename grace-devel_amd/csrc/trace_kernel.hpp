@@ -31,15 +31,24 @@ __device__ __forceinline__ void aabbs_hit(const float ix, const float iy, const 
     const float by_R = (R.z - oy) * iy, ty_R = (R.w - oy) * iy;
     const float bz_R = (Z.z - oz) * iz, tz_R = (Z.w - oz) * iz;
 
+    // A ray in the plane of a slab's face (zero direction component: 1/d = +-inf; face == origin)
+    // makes that face's product 0 * inf = NaN.  The reference's min / max then keep the OTHER
+    // face's +-inf and reject a box the ray touches -- and a sphere whose box face fl(c +- h)
+    // rounds onto the origin can still be hit by that ray (b2 = fl(q^2) < fl(h^2) for |q| < h):
+    // the walk would drop a hit the brute-force test finds.  Such a ray lies in the closed slab,
+    // so a NaN counts as -inf for the entry and +inf for the exit.  (Conservative: more node
+    // visits at most; every hit is still decided by the exact test.)
+    auto entry = [](const float t) { return t != t ? -INFINITY : t; };
+    auto exit_ = [](const float t) { return t != t ? INFINITY : t; };
     const int zero = __float_as_int(0.0f), ilen = __float_as_int(len);
-    const int tmin_L = imax(imax(__float_as_int(fminf(bx_L, tx_L)), __float_as_int(fminf(by_L, ty_L))),
-                            imax(imin(__float_as_int(bz_L), __float_as_int(tz_L)), zero));
-    const int tmax_L = imin(imin(__float_as_int(fmaxf(bx_L, tx_L)), __float_as_int(fmaxf(by_L, ty_L))),
-                            imin(imax(__float_as_int(bz_L), __float_as_int(tz_L)), ilen));
-    const int tmin_R = imax(imax(__float_as_int(fminf(bx_R, tx_R)), __float_as_int(fminf(by_R, ty_R))),
-                            imax(imin(__float_as_int(bz_R), __float_as_int(tz_R)), zero));
-    const int tmax_R = imin(imin(__float_as_int(fmaxf(bx_R, tx_R)), __float_as_int(fmaxf(by_R, ty_R))),
-                            imin(imax(__float_as_int(bz_R), __float_as_int(tz_R)), ilen));
+    const int tmin_L = imax(imax(__float_as_int(fminf(entry(bx_L), entry(tx_L))), __float_as_int(fminf(entry(by_L), entry(ty_L)))),
+                            imax(imin(__float_as_int(entry(bz_L)), __float_as_int(entry(tz_L))), zero));
+    const int tmax_L = imin(imin(__float_as_int(fmaxf(exit_(bx_L), exit_(tx_L))), __float_as_int(fmaxf(exit_(by_L), exit_(ty_L)))),
+                            imin(imax(__float_as_int(exit_(bz_L)), __float_as_int(exit_(tz_L))), ilen));
+    const int tmin_R = imax(imax(__float_as_int(fminf(entry(bx_R), entry(tx_R))), __float_as_int(fminf(entry(by_R), entry(ty_R)))),
+                            imax(imin(__float_as_int(entry(bz_R)), __float_as_int(entry(tz_R))), zero));
+    const int tmax_R = imin(imin(__float_as_int(fmaxf(exit_(bx_R), exit_(tx_R))), __float_as_int(fmaxf(exit_(by_R), exit_(ty_R)))),
+                            imin(imax(__float_as_int(exit_(bz_R)), __float_as_int(exit_(tz_R))), ilen));
     // two bare comparisons: their ballots fold onto the v_cmp results
     hit_r = __int_as_float(tmax_R) >= __int_as_float(tmin_R);
     hit_l = __int_as_float(tmax_L) >= __int_as_float(tmin_L);
@@ -758,7 +767,13 @@ void trace_kernel(const TraceArgs a)
     bool flat = FLAT_OK && (axis >= 0 || is_pencil);
     int groups_kept = 0;                    // surviving groups of this packet (wave-uniform)
     const float4* const group_boxes = a.C + 2 * ((size_t(a.n_prims) + 63) >> 6) + 1;
-    const int n_groups = FLAT_OK ? int((size_t(a.n_prims) + (size_t(1) << a.group_shift) - 1) >> a.group_shift) : 0;
+    // The passes sweep [0, covered): the primitives the tree's leaves cover (node_prims_kernel),
+    // n_prims unless the tree was built over a prefix of the array traced.  (Group boxes past
+    // that prefix still contain its primitives: conservative.)  Leaves that do not start at 0:
+    // the walk.
+    const int covered = FLAT_OK ? min(__float_as_int(group_boxes[-1].y), a.n_prims) : 0;
+    if (covered < 0) flat = false;
+    const int n_groups = FLAT_OK ? int((size_t(max(covered, 0)) + (size_t(1) << a.group_shift) - 1) >> a.group_shift) : 0;
     unsigned long long group_mask = 0ull;   // surviving groups of the current pass, not yet swept
     int group_next = 0;                     // first group of the next pass
     // All passes are made up front, their loads in flight together (made one by one between the
@@ -855,7 +870,7 @@ void trace_kernel(const TraceArgs a)
             const int g = group_next - 64 + __builtin_ctzll(group_mask);
             group_mask &= group_mask - 1ull;
             sweep_first = g << a.group_shift;
-            sweep_count = min(1 << a.group_shift, a.n_prims - sweep_first);
+            sweep_count = min(1 << a.group_shift, covered - sweep_first);
             // A wave of a split packet skips groups none of whose granules it owns.
             if (SPLIT) {
                 bool mine = false;
@@ -908,7 +923,22 @@ void trace_kernel(const TraceArgs a)
             // node count, no gain each time (2.91 vs 2.92 ms).  The ~100 node tests per packet are a
             // chain of dependent loads; their vector work is not what the walk waits for.)
             bool hit_l, hit_r;
-            aabbs_hit(ix, iy, iz, ox, oy, oz, len, L, R, Z, hit_l, hit_r);
+            if constexpr (fp64(MODE)) {
+                // The fp64 tests accept spheres the float node boxes need not contain: double4
+                // centres +- radii are narrowed to the nearest float (the corner can move inward by
+                // half an ulp: a tangent hit of a sphere with h ~ ulp(|c|) falls outside its box),
+                // and the fp64 test of float4 spheres admits |s - o| up to h (1 + 2^-23) per
+                // co-ordinate.  Both lie within 2^-21 (|lo| + |hi|) of the box (>= 2^-21 max(|c|, h)),
+                // the cluster boxes' slack.
+                auto widen = [](const float4 b) {   // {lo, hi, lo, hi}
+                    const float s0 = (fabsf(b.x) + fabsf(b.y)) * 4.76837158203125e-07f;   // 2^-21
+                    const float s1 = (fabsf(b.z) + fabsf(b.w)) * 4.76837158203125e-07f;
+                    return make_float4(b.x - s0, b.y + s0, b.z - s1, b.w + s1);
+                };
+                aabbs_hit(ix, iy, iz, ox, oy, oz, len, widen(L), widen(R), widen(Z), hit_l, hit_r);
+            } else {
+                aabbs_hit(ix, iy, iz, ox, oy, oz, len, L, R, Z, hit_l, hit_r);
+            }
             const unsigned long long vote_r = __builtin_amdgcn_ballot_w64(hit_r);
             const unsigned long long vote_l = __builtin_amdgcn_ballot_w64(hit_l);
 #ifdef GRACE_PACKET_STATS

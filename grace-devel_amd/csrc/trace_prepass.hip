@@ -258,6 +258,10 @@ __global__ __launch_bounds__(256) void tri_prepass_kernel(const float* __restric
 
 // Primitive range of every node: a node's leaves are consecutive (nodes.h:27-28) and so are
 // their primitives, [leaves[first].x, leaves[last].x + leaves[last].y).
+// The root's range also goes to the .y of the tail record (r2_min_slot[1]): the end of the
+// primitives the leaves cover when they start at 0, else -1.  A tree built over a prefix of the
+// array traced covers fewer than n_prims; the flat group passes, which do not walk the tree,
+// sweep only that prefix (the walk and the reference never reach the rest).
 __global__ __launch_bounds__(256) void node_prims_kernel(const int4* __restrict__ nodes4,
                                                          const int4* __restrict__ leaves, int n_nodes,
                                                          int2* __restrict__ out,
@@ -268,7 +272,12 @@ __global__ __launch_bounds__(256) void node_prims_kernel(const int4* __restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     // (the slot the cluster-box pass reduces the scene's smallest r^2 into starts out huge: this
     // launch precedes that pass on the stream)
-    if (i == 0 && r2_min_slot) *r2_min_slot = 0x7f7f7f7fu;
+    if (i == 0 && r2_min_slot) {
+        *r2_min_slot = 0x7f7f7f7fu;
+        // the root's range: from the first leaf (0) to the end of the last (n_nodes)
+        const int4 l0 = leaves[0], ln = leaves[n_nodes];
+        r2_min_slot[1] = uint32_t(l0.x == 0 ? ln.x + ln.y : -1);
+    }
     if (i >= n_nodes) return;
     const int4 n0 = nodes4[4 * size_t(i)];
     const int4 lf = leaves[n0.z], ll = leaves[n0.w];

@@ -1120,3 +1120,88 @@ void go_brute_cumulative_d4(const go_ray* rays, size_t n_rays, const double* s, 
     }
 }
 
+
+int go_sphere_hit_d4(const go_ray* ray, const double* s, double* b2, double* dist)
+{
+    return sphere_hit_d(ray, s, b2, dist);
+}
+
+/* Per-hit outputs of trace_sph<double4, int, double> (trace_sph.cuh:143-167) given exclusive
+ * offsets: ascending primitive index, the double integral and the double distance. */
+void go_brute_hits_d4(const go_ray* rays, size_t n_rays, const double* s, size_t n,
+                      const int* offsets, int* idx, double* integrals, double* dists)
+{
+    #pragma omp parallel for schedule(dynamic, 16)
+    for (size_t ri = 0; ri < n_rays; ++ri) {
+        go_ray ray = rays[ri];
+        int o = offsets[ri]; double b2, d;
+        for (size_t si = 0; si < n; ++si)
+            if (sphere_hit_d(&ray, s + 4 * si, &b2, &d)) {
+                idx[o] = (int)si; integrals[o] = hit_integral_d(b2, s[4 * si + 3]); dists[o] = d; ++o;
+            }
+    }
+}
+
+/* sphere_hit<float4, double> (generic/intersect.h:9-55 with Real4 = float4, Real = double): the
+ * differences s - o are formed in float and widened, everything after in double; the radius test
+ * compares against the float product w * w. */
+static inline int sphere_hit_f4d(const go_ray* ray, const go_f4* s, double* b2, double* dot_p)
+{
+    double px = (float)(s->x - ray->ox), py = (float)(s->y - ray->oy), pz = (float)(s->z - ray->oz);
+    double rx = ray->dx, ry = ray->dy, rz = ray->dz;
+    *dot_p = px * rx + py * ry + pz * rz;
+    double bx = px - *dot_p * rx, by = py - *dot_p * ry, bz = pz - *dot_p * rz;
+    *b2 = bx * bx + by * by + bz * bz;
+    if (*b2 >= (double)(s->w * s->w)) return 0;
+    if (*dot_p < 0.0f) return 0;
+    if (*dot_p >= ray->length) return 0;
+    return 1;
+}
+
+int go_sphere_hit_f4d(const go_ray* ray, const go_f4* s, double* b2, double* dist)
+{
+    return sphere_hit_f4d(ray, s, b2, dist);
+}
+
+void go_brute_hitcounts_f4d(const go_ray* rays, size_t n_rays, const go_f4* s, size_t n, int* counts)
+{
+    #pragma omp parallel for schedule(dynamic, 16)
+    for (size_t ri = 0; ri < n_rays; ++ri) {
+        go_ray ray = rays[ri];
+        int hits = 0; double b2, d;
+        for (size_t si = 0; si < n; ++si) hits += sphere_hit_f4d(&ray, &s[si], &b2, &d);
+        counts[ri] = hits;
+    }
+}
+
+/* The hit lists of sphere_hit<float4, double>: ascending primitive index, the double b2 and the
+ * double distance of each hit (the per-hit integrals follow from b2 and w). */
+void go_brute_hits_f4d(const go_ray* rays, size_t n_rays, const go_f4* s, size_t n,
+                       const int* offsets, int* idx, double* b2s, double* dists)
+{
+    #pragma omp parallel for schedule(dynamic, 16)
+    for (size_t ri = 0; ri < n_rays; ++ri) {
+        go_ray ray = rays[ri];
+        int o = offsets[ri]; double b2, d;
+        for (size_t si = 0; si < n; ++si)
+            if (sphere_hit_f4d(&ray, &s[si], &b2, &d)) { idx[o] = (int)si; b2s[o] = b2; dists[o] = d; ++o; }
+    }
+}
+
+/* sphere_hit on n (ray, sphere) PAIRS: kind 0 = <float4, float> (b2, dot widened from float),
+ * 1 = <float4, double>, 2 = <double4, double> (s: 4 doubles per sphere). */
+void go_sphere_hit_pairs(const go_ray* rays, const void* s, size_t n, int kind, int* hit,
+                         double* b2, double* dot)
+{
+    for (size_t i = 0; i < n; ++i) {
+        if (kind == 0) {
+            float fb2, fd;
+            hit[i] = sphere_hit(&rays[i], (const go_f4*)s + i, &fb2, &fd);
+            b2[i] = fb2; dot[i] = fd;
+        } else if (kind == 1) {
+            hit[i] = sphere_hit_f4d(&rays[i], (const go_f4*)s + i, &b2[i], &dot[i]);
+        } else {
+            hit[i] = sphere_hit_d(&rays[i], (const double*)s + 4 * i, &b2[i], &dot[i]);
+        }
+    }
+}

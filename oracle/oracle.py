@@ -378,3 +378,48 @@ def brute_cumulative_d4(rays, prims, blocks=SUM_BLOCKS):
                                  C.c_int(blocks))
     return out
 
+
+
+def brute_hits_d4(rays, prims):
+    """trace_sph<double4, int, double>: offsets (exclusive), idx, integrals, distances (float64)."""
+    counts = brute_hitcounts_d4(rays, prims)
+    offsets = np.empty_like(counts)
+    total = lib().go_exclusive_scan_i32(_p(counts), C.c_size_t(len(counts)), _p(offsets))
+    idx = np.empty(total, np.int32); integ = np.empty(total, np.float64); dist = np.empty(total, np.float64)
+    rays = _rays(rays); prims = np.ascontiguousarray(prims, np.float64)
+    lib().go_brute_hits_d4(_p(rays), C.c_size_t(len(rays)), _p(prims), C.c_size_t(len(prims)),
+                           _p(offsets), _p(idx), _p(integ), _p(dist))
+    return offsets, idx, integ, dist
+
+
+# -- float4 spheres under the fp64 test (sphere_hit<float4, double>) ---------------------------
+
+def brute_hitcounts_f4d(rays, prims):
+    rays = _rays(rays); prims = _f4(prims)
+    out = np.empty(len(rays), np.int32)
+    lib().go_brute_hitcounts_f4d(_p(rays), C.c_size_t(len(rays)), _p(prims), C.c_size_t(len(prims)), _p(out))
+    return out
+
+
+def brute_hits_f4d(rays, prims):
+    """offsets (exclusive), idx, b2 (float64), distances (float64) of the fp64 test's hits."""
+    counts = brute_hitcounts_f4d(rays, prims)
+    offsets = np.empty_like(counts)
+    total = lib().go_exclusive_scan_i32(_p(counts), C.c_size_t(len(counts)), _p(offsets))
+    idx = np.empty(total, np.int32); b2 = np.empty(total, np.float64); dist = np.empty(total, np.float64)
+    rays = _rays(rays); prims = _f4(prims)
+    lib().go_brute_hits_f4d(_p(rays), C.c_size_t(len(rays)), _p(prims), C.c_size_t(len(prims)),
+                            _p(offsets), _p(idx), _p(b2), _p(dist))
+    return offsets, idx, b2, dist
+
+
+def sphere_hit_pairs(rays, prims, kind):
+    """The oracle's sphere_hit on (rays[i], prims[i]) pairs.  kind 0: <float4, float>, 1: <float4,
+    double>, 2: <double4, double>.  Returns (hit bool, b2 float64, dot float64)."""
+    rays = _rays(rays)
+    prims = np.ascontiguousarray(prims, np.float64 if kind == 2 else np.float32)
+    assert len(rays) == len(prims)
+    n = len(rays)
+    hit = np.empty(n, np.int32); b2 = np.empty(n, np.float64); dot = np.empty(n, np.float64)
+    lib().go_sphere_hit_pairs(_p(rays), _p(prims), C.c_size_t(n), C.c_int(kind), _p(hit), _p(b2), _p(dot))
+    return hit.astype(bool), b2, dot
