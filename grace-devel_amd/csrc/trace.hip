@@ -89,7 +89,6 @@
 #include "trace_plan.hpp"
 
 #include <cmath>
-#include <cstdlib>
 
 using namespace grace_hip;
 
@@ -146,6 +145,354 @@ grace_status ensure_status(TraceState& ts, hipStream_t stream)
     return GRACE_OK;
 }
 
+struct LaunchPlan {   // how a call is launched: everything that follows from the sizes and the knobs alone
+    int width = 64, n_packets = 0;   // rays per packet, packets
+    int split = 1;                   // waves launched per packet ...
+    bool dev_split = false;          // ... of which the device picks the working ones
+    // split per-hit trace of small batches (see TraceArgs / hits_plan_kernel); packets of 64 rays
+    int hit_chunk_shift = GRANULE_SHIFT, hit_chunks = 0, hit_split = 1;
+    size_t hit_packets = 0;
+    bool hits_split = false;         // this per-hit trace splits its packets by chunk ranges
+    bool keep_chunks = false;        // this hit-count call keeps its chunk counts for that per-hit trace
+    bool reorder = false;            // rays walk in coherence order
+    bool lattice = false;            // the device flag picks the LAT instantiation (TraceArgs::lat_dev) ...
+    int lat_split = 0;               // ... over this many waves per packet where one wave is planned (0: not)
+    bool fast_b = false;             // column densities by the fast integral: records B50, the ALT kernels
+    int treelet = 0, treelet_axis = 0;
+};
+
+template <int MODE>
+LaunchPlan plan_launch(const TraceState& ts, const bool keep_requested, const size_t n_rays, const size_t n_prims)
+{
+    LaunchPlan p;
+    // Split per-hit trace for small batches (see TraceArgs / hits_plan_kernel): chunk size =
+    // a power of two >= one granule giving at most MAX_HIT_CHUNKS chunks.
+    while ((((n_prims - 1) >> p.hit_chunk_shift) + 1) > size_t(MAX_HIT_CHUNKS)) ++p.hit_chunk_shift;
+    p.hit_chunks = int(((n_prims - 1) >> p.hit_chunk_shift) + 1);
+    p.hit_packets = ceil_div(n_rays, size_t(64));
+    // Does a per-hit trace of this batch split?  (also asked by the hit-count call that keeps chunk counts)
+    const bool split_hits = ts.width <= 0 && p.hit_packets < 4096 && p.hit_chunks >= 8 && ts.split != 1;
+    p.hits_split = MODE == MODE_HITS && split_hits;
+    p.keep_chunks = MODE == MODE_COUNT && keep_requested && split_hits;
+    if (p.hits_split) {     // (2 to 8 waves per packet)
+        if (ts.split > 0) p.hit_split = ts.split;
+        else while (p.hit_split < 8 && p.hit_packets * p.hit_split < 16384) p.hit_split *= 2;
+    }
+    // Per-hit and triangle traces cannot split a packet among waves (their outputs are ordered
+    // / reduced per ray inside one wave); with few rays they use narrower packets instead:
+    // 2-4x the waves, each with a tighter beam, on a chip that would otherwise sit idle.
+    if (ts.width > 0) p.width = ts.width;
+    else if (ordered(MODE) && !p.hits_split)
+        while (p.width > 16 && ceil_div(n_rays, size_t(p.width)) < 4096) p.width /= 2;
+    // Hit counts and column densities split packets eight ways at most; a batch too small to fill
+    // the chip even then (< 512 packets) also gets narrower packets (10^7 particles, 12288 HEALPix
+    // rays: 3.5 -> 2.0 ms at 16 rays per packet; from 49152 rays on it loses: config 3 0.87 -> 0.95 ms).
+    else if (class_split(MODE) && ts.split <= 0)
+        while (p.width > 16 && ceil_div(n_rays, size_t(p.width)) * SUM_CLASSES < 4096) p.width /= 2;
+    p.n_packets = ceil_div(n_rays, size_t(p.width));
+    p.reorder = ts.ray_reorder && n_rays > 64;
+    // Waves per packet: two resident sets of waves (2 x 8192) for small ray batches.
+    if (class_split(MODE)) {
+        // (column densities: a batch of exactly 16384 packets -- the 1024^2 frame -- still gets a
+        // second wave per packet, 32768 waves; see choose_split.  Larger batches run one.)
+        const size_t wave_budget = f4_sums(MODE) ? 16385 : 16384;
+        if (ts.split > 0) p.split = ts.split;
+        else {
+            while (p.split < SUM_CLASSES && size_t(p.n_packets) * p.split < wave_budget) p.split *= 2;
+            // (the device picks the working waves per packet: scenes with spheres smaller than the ray
+            // spacing want four -- see lat_split below --, one-direction batches two, others one)
+            if (f4_sums(MODE) && p.split > 1 && p.split < ts.lat_split && p.reorder && p.width == 64)
+                p.split = ts.lat_split;
+        }
+    }
+    if (p.hits_split) p.split = p.hit_split;
+    // (the working waves per packet are chosen on the device, by ray_keys_kernel)
+    p.dev_split = f4_class_split(MODE) && p.split > 1 && ts.split <= 0;
+    p.lattice = has_lattice(MODE) && p.reorder;
+    // A batch of >= 16384 packets runs one wave per packet -- unless the device flag says the scene
+    // holds spheres smaller than the ray spacing (clustered SPH data: dense cores).  Such scenes
+    // have packets dozens of times heavier than the median (10^7 particles, 90 % of them in 50
+    // clumps: with the lattice cull the heaviest of 16384 waves still lived 14x the mean and set
+    // the kernel time), so the lattice instantiation of these batches is the class-split kernel
+    // with four waves per packet: the heaviest packets' work is spread over four SIMDs (measured
+    // on two clustered scenes: K = 2 / 4 / 8 -> 3.62 / 3.47 / 4.24 ms and 4.24 / 3.42 / 3.71 ms;
+    // one wave: 4.66 and 6.78 ms).  Same class sums, same bits.
+    if (f4_class_split(MODE) && p.split == 1 && p.lattice && p.width == 64
+        && ts.lat_split > 0 && ts.split <= 0)   // (an explicit grace_trace_set_packet_split is obeyed)
+        p.lat_split = ts.lat_split;
+    p.fast_b = f4_sums(MODE) && !ts.exact_integrals;
+    // Subtrees of up to this many primitives are swept -- cluster tests, then culling rounds
+    // over the surviving clusters -- rather than descended.
+    // Axis-aligned packets test a cluster's box against their origin rectangle (sharp: large
+    // subtrees pay; 16384 measured best in round 2); pencil packets test it
+    // against the bundle's side planes, general packets its circumscribed sphere.
+    // (re-measured after the pencil cluster test became a box-against-side-planes test: sphere
+    // scenes now prefer 8192 there too -- config 2 column densities 1.74 -> 1.46 ms, hit counts
+    // 1.54 -> 1.19, config 3 0.94 -> 0.87 --; triangles, culled through bounding spheres, keep 512:
+    // 5.3 / 4.6 / 2.8 ms for the three cameras against 6.9 / 5.8 / 3.0 at 8192)
+    // (round 3, after the test-free 16-byte survivor rounds made the sweeps cheaper relative to
+    // the walk: axis-aligned packets prefer 32768 -- 1024^2 frame 2.82 -> 2.78 ms, its 1/2, 1/4,
+    // 1/8 shards 1.53 -> 1.46, 0.84 -> 0.80, 0.51 -> 0.47 ms (their split waves each repeat the
+    // walk); 65536 the same, 131072 worse; clustered scenes +3 %.  Pencil / general packets stay
+    // at 8192: config 2 1.47 / 1.50 / 1.50 ms at 8192 / 16384 / 32768, config 3 0.87 / 0.83 / 0.86.)
+    const int auto_treelet = (MODE == MODE_TRI) ? 512 : 8192, auto_treelet_axis = 32768;
+#ifdef GRACE_PACKET_STATS
+    p.treelet = ts.treelet < 0 ? auto_treelet : ts.treelet;
+    p.treelet_axis = ts.treelet < 0 ? auto_treelet_axis : ts.treelet;
+#else
+    p.treelet = (MODE == MODE_STATS) ? 0 : (ts.treelet < 0 ? auto_treelet : ts.treelet);
+    p.treelet_axis = (MODE == MODE_STATS) ? 0 : (ts.treelet < 0 ? auto_treelet_axis : ts.treelet);
+#endif
+    return p;
+}
+
+struct TraceBuffers {   // a call's buffers in its workspace frame (null: not needed)
+    unsigned long long* sig = nullptr;   // signature partials (launch_signatures)
+    // scene records derived per call (not cached)
+    float4* A = nullptr; float2* B = nullptr; double* T64 = nullptr; int2* node_prims = nullptr; float4* C = nullptr;
+    float* partial = nullptr; double* partial_d = nullptr;   // class sums of split packets
+    int *chunk_counts = nullptr, *chunk_off = nullptr, *scratch_counts = nullptr;   // split per-hit trace
+    int4* wave_map = nullptr; int *n_wave_map = nullptr, *pk_first = nullptr, *pk_parts = nullptr;
+    uint32_t *pk_prefix = nullptr, *pk_total = nullptr;
+    // ray order; ext: 12 extents + [12] the device-side split + [13] the lattice flag (per call)
+    uint32_t* ext = nullptr; uint32_t* keys = nullptr; uint32_t* perm = nullptr;
+};
+
+// Opens the call's frame and points `a` at its scene records and ray order, cached or derived here.
+// Side effects in this order: the caches' `seen` keys, a cache allocated on FILL, the frame, the
+// signatures, the scene pre-pass, the ray order (or, for a cached order, the device-side choices).
+template <int MODE>
+grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGuard& frame, const LaunchPlan& p,
+                         const size_t n_rays, const size_t n_prims, const size_t n_nodes, hipStream_t stream)
+{
+    // ---- which cached records does this call use?  (see trace_state.hpp) -------------------
+    // NONE: derive into the workspace (a scene / batch seen for the first time);  FILL: the
+    // same arrays as the previous call -- derive into the cache;  CHECK: cached -- validate by
+    // signature on the device, the gated pre-pass recomputes if stale;  TRUST: cached, and the
+    // caller has switched validation off.
+    enum CacheUse { USE_NONE, USE_FILL, USE_CHECK, USE_TRUST };
+    auto decide = [&](const bool have, const bool pinned, const bool repeat) {
+        if (have) return ts.cache_validation ? USE_CHECK : USE_TRUST;
+        return (ts.cache_auto && repeat && !pinned) ? USE_FILL : USE_NONE;
+    };
+    CacheUse scene_use = USE_NONE, rays_use = USE_NONE;
+    const SceneKey skey{primitive(MODE), a.spheres, a.nodes, a.leaves, n_prims, n_nodes};
+    // The fp64 modes' records (inflated for the fp64 test) are derived per call: the scene cache
+    // is neither read nor filled nor counted as seen by them, so float calls on the same arrays
+    // cache exactly as they would without them.
+    if (!fp64(MODE) && MODE != MODE_STATS) {
+        scene_use = decide(ts.scene.valid && ts.scene.key == skey, ts.scene.valid && ts.scene.pinned,
+                           ts.scene.seen == skey);
+        ts.scene.seen = skey;
+        if (scene_use == USE_FILL && scene_cache_alloc(ts, skey) != GRACE_OK) scene_use = USE_NONE;   // (no memory: no cache)
+    }
+    const RayKey rkey{a.rays, n_rays};
+    if (p.reorder) {
+        rays_use = decide(ts.rays.valid && ts.rays.key == rkey, ts.rays.valid && ts.rays.pinned,
+                          ts.rays.seen == rkey);
+        ts.rays.seen = rkey;
+        if (rays_use == USE_FILL && rays_cache_alloc(ts, rkey) != GRACE_OK) rays_use = USE_NONE;
+    }
+    const bool scene_cached = scene_use != USE_NONE, rays_cached = rays_use != USE_NONE;
+    const bool scene_sig = scene_use == USE_FILL || scene_use == USE_CHECK;
+    const bool rays_sig = rays_use == USE_FILL || rays_use == USE_CHECK, sig = scene_sig || rays_sig;
+    // The frame's layout: carve(base) takes the buffers from `base` and returns the bytes taken; over
+    // base == nullptr it only counts, so the frame is sized by the same code that carves it.
+    auto carve = [&](char* const base) {
+        size_t used = 0;
+        auto take = [&](auto*& ptr, const size_t count) {
+            using T = std::remove_reference_t<decltype(*ptr)>;
+            ptr = base ? reinterpret_cast<T*>(base + used) : nullptr;
+            used += Workspace::aligned(count * sizeof(T));
+        };
+        if (sig) take(b.sig, sig_partial_words());
+        if (!scene_cached) {
+            take(b.A, n_prims + 4);
+            if (f4_integrals(MODE)) take(b.B, n_prims + 4);
+            if (MODE == MODE_TRI) take(b.T64, 9 * (n_prims + 4));
+            take(b.node_prims, n_nodes); take(b.C, cluster_record_count(n_prims));
+        }
+        if (f4_sums(MODE)) take(b.partial, n_rays * SUM_CLASSES * channels(MODE));
+        if (double_sums(MODE)) take(b.partial_d, n_rays * SUM_CLASSES);
+        if (p.hits_split) {
+            take(b.chunk_counts, n_rays * size_t(p.hit_chunks)); take(b.chunk_off, n_rays * size_t(p.hit_chunks));
+            take(b.scratch_counts, n_rays); take(b.wave_map, p.hit_packets * p.hit_split); take(b.n_wave_map, 16);
+            take(b.pk_prefix, p.hit_packets * size_t(p.hit_chunks));
+            take(b.pk_total, p.hit_packets + 16); take(b.pk_first, p.hit_packets + 16); take(b.pk_parts, p.hit_packets + 16);
+        }
+        if (p.reorder) { take(b.ext, 16); take(b.keys, n_rays); take(b.perm, n_rays); }
+        return used;
+    };
+    const size_t own = carve(nullptr);
+    // (ray_order's sort carves its temporaries after these)
+    GRACE_TRY(frame.begin(own + (p.reorder ? sort_ws_bytes(n_rays, 4, 0) : 0), stream));
+    carve(Workspace::take<char>(own));
+    if (sig) {
+        SigRequest rq;
+        if (scene_sig) {
+            rq.prims = a.spheres; rq.prims_bytes = n_prims * (MODE == MODE_TRI ? 36 : 16);
+            rq.nodes = a.nodes; rq.nodes_bytes = n_nodes * 64;
+            rq.leaves = a.leaves; rq.leaves_bytes = (n_nodes + 1) * 16;
+            rq.scene_ctl = ts.scene.ctl; rq.scene_force = scene_use == USE_FILL;
+        }
+        if (rays_sig) {
+            rq.rays = a.rays; rq.rays_bytes = n_rays * 28;
+            rq.rays_ctl = ts.rays.ctl; rq.rays_force = rays_use == USE_FILL; rq.rays_ext = ts.rays.ext;
+        }
+        GRACE_TRY(launch_signatures(rq, b.sig, stream));
+    }
+    if (scene_cached) {
+        Scene& sc = ts.scene;
+        if (scene_use != USE_TRUST) {
+            // (gated by the cache's stale flag: a first fill is forced stale)
+            GRACE_TRY(scene_fill(skey.kind, a.spheres, n_prims, a.nodes, n_nodes, a.leaves, sc.A, sc.B1, sc.B50,
+                                 sc.T64, sc.node_prims, sc.C, stream, &sc.ctl->stale));
+            sc.valid = true;
+        }
+        a.A = sc.A; a.T64 = sc.T64; a.node_prims = sc.node_prims; a.C = sc.C;
+        a.B = f4_integrals(MODE) ? (p.fast_b ? sc.B50 : sc.B1) : nullptr;
+    } else {
+        GRACE_TRY(scene_fill(skey.kind, primitive(MODE) == PRIM_D4 ? static_cast<const void*>(a.spheres_d) : a.spheres,
+                             n_prims, a.nodes, n_nodes, a.leaves, b.A, p.fast_b ? nullptr : b.B, p.fast_b ? b.B : nullptr,
+                             b.T64, b.node_prims, b.C, stream));
+        a.A = b.A; a.B = b.B; a.T64 = b.T64; a.node_prims = b.node_prims; a.C = b.C;
+    }
+    if (p.reorder) {
+        const float4* scene_min = a.C + 2 * ((n_prims + 63) / 64);
+        uint32_t* lat_flag = p.lattice ? b.ext + 13 : nullptr;
+        int* split_dev = p.dev_split ? reinterpret_cast<int*>(b.ext + 12) : nullptr;
+        const int split_flags = f4_sums(MODE) ? SPLIT_WIDE_BUDGET : 0;
+        if (rays_cached) {
+            RayOrder& ro = ts.rays;
+            if (rays_use != USE_TRUST) {
+                // (gated by the cache's stale flag; the order lands in the cache's own buffers)
+                GRACE_TRY(ray_order(a.rays, n_rays, ro.ext, b.keys, ro.perm, nullptr, nullptr, 0, 0, nullptr,
+                                    stream, &ro.ctl->stale));
+                ro.valid = true;
+            }
+            // cached order: only this call's device-side choices remain
+            if (lat_flag || split_dev)
+                GRACE_TRY(launch_choose_variants(ro.ext, int(n_rays), scene_min, lat_flag, p.n_packets,
+                                                 p.split | split_flags, split_dev, stream));
+            a.perm = ro.perm;
+        } else {
+            GRACE_TRY(ray_order(a.rays, n_rays, b.ext, b.keys, b.perm, scene_min, lat_flag, p.n_packets,
+                                p.split | split_flags, split_dev, stream));
+            a.perm = b.perm;
+        }
+        a.lat_dev = reinterpret_cast<const int*>(lat_flag); a.split_dev = split_dev;
+    }
+    return GRACE_OK;
+}
+
+// Both variants of a kernel with a lattice instantiation (the device flag lets one run).
+template <int MODE, bool SPLIT, bool ALT = false>
+void launch_walk(const int grid, const TraceArgs& args, hipStream_t stream)
+{
+    trace_kernel<MODE, SPLIT, ALT, false><<<grid, TRACE_BLOCK, 0, stream>>>(args);
+    if constexpr (has_lattice(MODE))
+        if (args.lat_dev) trace_kernel<MODE, SPLIT, ALT, true><<<grid, TRACE_BLOCK, 0, stream>>>(args);
+}
+
+// The walk of a planned call and the kernels around it.  kept: the chunk counts a hit-count call
+// has kept for this per-hit trace (null: count them here).
+template <int MODE>
+grace_status dispatch(const TraceState& ts, const TraceArgs& a, const TraceBuffers& b, const LaunchPlan& p,
+                      const int* kept, const size_t n_rays, hipStream_t stream)
+{
+    const int grid = ceil_div(size_t(p.n_packets) * p.split, TRACE_BLOCK / 64);
+    // Upper levels of the class sum tree: k partial sums per ray (k_dev: the device's k, if set;
+    // run_if: the kernel returns at once if *run_if == 0).  Counts are summed by atomics.
+    auto combine = [&](const int k, const int* k_dev, const int* run_if) -> grace_status {
+        const int g = ceil_div(n_rays * channels(MODE), 256);   // (one thread per ray and channel)
+        if constexpr (double_sums(MODE))
+            combine_classes_kernel<double><<<g, 256, 0, stream>>>(a.partial_d, int(n_rays), k, k_dev, a.out_sums_d, run_if);
+        else if constexpr (weighted(MODE))
+            combine_channel_classes_kernel<<<g, 256, 0, stream>>>(a.partial, int(n_rays), channels(MODE), k, k_dev,
+                                                                  a.out_sums, a.out_stride, run_if);
+        else if constexpr (f4_sums(MODE))
+            combine_classes_kernel<float><<<g, 256, 0, stream>>>(a.partial, int(n_rays), k, k_dev, a.out_sums, run_if);
+        else return GRACE_OK;
+        GRACE_CHECK_LAUNCH();
+        return GRACE_OK;
+    };
+    if constexpr (class_split(MODE)) {
+        auto walk = [&](auto alt_tag) -> grace_status {
+            constexpr bool ALT = decltype(alt_tag)::value;
+            if constexpr (has_lattice(MODE)) if (p.lat_split) {   // one wave, or the LAT kernel split (see plan_launch)
+                if (output(MODE) == OUT_COUNTS)
+                    GRACE_TRY_HIP(hipMemsetAsync(a.out_counts, 0, n_rays * sizeof(int), stream));
+                trace_kernel<MODE, false, ALT, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
+                GRACE_CHECK_LAUNCH();
+                TraceArgs a_lat = a;
+                a_lat.split = p.lat_split; a_lat.split_dev = nullptr;
+                trace_kernel<MODE, true, ALT, true><<<ceil_div(size_t(p.n_packets) * p.lat_split, TRACE_BLOCK / 64),
+                                                      TRACE_BLOCK, 0, stream>>>(a_lat);
+                GRACE_CHECK_LAUNCH();
+                return combine(p.lat_split, nullptr, a.lat_dev);
+            }
+            if (p.split > 1) launch_walk<MODE, true, ALT>(grid, a, stream);
+            else launch_walk<MODE, false, ALT>(grid, a, stream);
+            return GRACE_OK;
+        };
+        if constexpr (f4_sums(MODE)) GRACE_TRY(p.fast_b ? walk(std::true_type()) : walk(std::false_type()));
+        else GRACE_TRY(walk(std::false_type()));
+    } else if constexpr (MODE == MODE_HITS) {
+        if (p.hits_split) {
+            // 1. hits per (ray, chunk): the counting walk, split by summation class -- unless the
+            //    hit-count call made for this trace_sph has kept them (grace_trace_hitcounts_keep_f4)
+            const int* counts = kept;
+            if (!kept) {
+                TraceArgs c = a;
+                c.chunk_counts = b.chunk_counts; c.out_counts = b.scratch_counts;
+                GRACE_TRY_HIP(hipMemsetAsync(b.chunk_counts, 0, n_rays * size_t(p.hit_chunks) * 4, stream));
+                GRACE_TRY_HIP(hipMemsetAsync(b.scratch_counts, 0, n_rays * 4, stream));
+                launch_walk<MODE_COUNT, true>(grid, c, stream);
+                GRACE_CHECK_LAUNCH();
+                counts = b.chunk_counts;
+            }
+            // 2. output offsets per (ray, chunk); the launched waves dealt to the packets by hit
+            //    totals; each packet's chunks cut into its waves' ranges
+            hits_offsets_kernel<<<ceil_div(n_rays, 4), 256, 0, stream>>>(counts, a.offsets, int(n_rays),
+                                                                         p.hit_chunks, b.chunk_off);
+            GRACE_CHECK_LAUNCH();
+            hits_plan_kernel<<<p.n_packets, MAX_HIT_CHUNKS, 0, stream>>>(counts, a.perm, int(n_rays),
+                                                                         p.hit_chunks, b.pk_prefix, b.pk_total);
+            GRACE_CHECK_LAUNCH();
+            hits_assign_kernel<<<1, 1024, 0, stream>>>(b.pk_total, p.n_packets, p.n_packets * p.split, p.hit_chunks,
+                                                       b.pk_first, b.pk_parts, b.n_wave_map,
+                                                       ts.hits_stage_split ? 200000ull : 0ull);
+            GRACE_CHECK_LAUNCH();
+            hits_bounds_kernel<<<p.n_packets, 64, 0, stream>>>(b.pk_prefix, b.pk_total, b.pk_first, b.pk_parts,
+                                                               p.hit_chunks, b.wave_map);
+            GRACE_CHECK_LAUNCH();
+            // 3. the per-hit walk, wave w owning wave_map[w]'s range of chunks
+            //    Heavy packets (output-bandwidth-bound: 10^5 isotropic rays through 10^6 large spheres,
+            //    410 k hits per packet: 18.0 -> 11.0 ms) stage their hits in LDS and store them eight
+            //    per ray at a time; light ones (61 M hits over 768 packets: 3.6 ms direct, 4.5 staged)
+            //    store directly.  The hit total is known on the device only: BOTH variants are
+            //    launched and the plan's flag (hits_assign_kernel) lets one of them run -- no read-back,
+            //    no host synchronisation inside the call.
+            TraceArgs staged = a, direct = a;
+            staged.stage_dev = direct.stage_dev = b.n_wave_map + 4;
+            staged.stage_want = 1; direct.stage_want = 0;
+            launch_walk<MODE, true, true>(grid, staged, stream);
+            GRACE_CHECK_LAUNCH();
+            launch_walk<MODE, true, false>(grid, direct, stream);
+        } else if (p.n_packets >= 4096) {
+            launch_walk<MODE, false, true>(grid, a, stream);
+        } else {
+            launch_walk<MODE, false, false>(grid, a, stream);
+        }
+    } else {
+        launch_walk<MODE, false>(grid, a, stream);
+    }
+    GRACE_CHECK_LAUNCH();
+    GRACE_TRY(stamps_report(MODE));
+    if (p.split > 1) GRACE_TRY(combine(p.split, a.split_dev, nullptr));
+    return GRACE_OK;
+}
+
 template <int MODE>
 grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n_nodes,
                           hipStream_t stream)
@@ -159,389 +506,41 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     TraceState& ts = *ts_ptr;
     GRACE_TRY(ensure_status(ts, stream));
     a.kernel_table = ts.kernel_table;     // this call's table, whatever the context selects later
-    FrameGuard frame;
-    // Split per-hit trace for small batches (see TraceArgs / hits_plan_kernel): chunk size =
-    // a power of two >= one granule giving at most MAX_HIT_CHUNKS chunks.
-    int hit_chunk_shift = GRANULE_SHIFT;
-    while ((((n_spheres - 1) >> hit_chunk_shift) + 1) > size_t(MAX_HIT_CHUNKS)) ++hit_chunk_shift;
-    const int hit_chunks = int(((n_spheres - 1) >> hit_chunk_shift) + 1);
-    const size_t hit_packets = ceil_div(n_rays, size_t(64));
-    int hit_split = 1;
-    if (MODE == MODE_HITS && ts.width <= 0 && hit_packets < 4096 && hit_chunks >= 8) {
-        if (ts.split > 0) hit_split = ts.split;
-        else while (hit_split < 8 && hit_packets * hit_split < 16384) hit_split *= 2;
-    }
-    const bool hits_split = hit_split > 1;
-    int* chunk_counts = nullptr; int* chunk_off = nullptr;
-    int* scratch_counts = nullptr;
-    int4* wave_map = nullptr; int* n_wave_map = nullptr;
-    uint32_t* pk_prefix = nullptr; uint32_t* pk_total = nullptr; int* pk_first = nullptr; int* pk_parts = nullptr;
-    // Would the per-hit trace of this batch use the split path?  (the same rule, for the hit-count
-    // call that is asked to keep its chunk counts)
-    const bool keep_chunks = MODE == MODE_COUNT && a.keep_chunks && ts.width <= 0 && hit_packets < 4096
-        && hit_chunks >= 8 && ts.split != 1;
-    const bool reuse_chunks = MODE == MODE_HITS && hits_split && ts.hits.valid && ts.hits.rays == a.rays
+    const LaunchPlan p = plan_launch<MODE>(ts, a.keep_chunks, n_rays, n_spheres);
+    const bool reuse_chunks = p.hits_split && ts.hits.valid && ts.hits.rays == a.rays
         && ts.hits.n_rays == n_rays && ts.hits.prims == static_cast<const void*>(a.spheres)
-        && ts.hits.n_prims == n_spheres && ts.hits.n_chunks == hit_chunks;
+        && ts.hits.n_prims == n_spheres && ts.hits.n_chunks == p.hit_chunks;
     if (chunked(MODE)) ts.hits.valid = false;   // consumed, or stale from here on
-    if (keep_chunks) {
-        const size_t need = n_rays * size_t(hit_chunks);
-        if (ts.hits.capacity < need) {
-            if (ts.hits.chunk_counts) { GRACE_TRY_HIP(hipDeviceSynchronize()); GRACE_TRY_HIP(hipFree(ts.hits.chunk_counts)); }
-            ts.hits.chunk_counts = nullptr; ts.hits.capacity = 0;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&ts.hits.chunk_counts), need * sizeof(int));
-            if (e != hipSuccess) return set_error(GRACE_OUT_OF_MEMORY, __FILE__, __LINE__, hipGetErrorString(e));
-            ts.hits.capacity = need;
-        }
+    const size_t need = n_rays * size_t(p.hit_chunks);
+    if (p.keep_chunks && ts.hits.capacity < need) {
+        if (ts.hits.chunk_counts) { GRACE_TRY_HIP(hipDeviceSynchronize()); GRACE_TRY_HIP(hipFree(ts.hits.chunk_counts)); }
+        ts.hits.chunk_counts = nullptr; ts.hits.capacity = 0;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ts.hits.chunk_counts), need * sizeof(int));
+        if (e != hipSuccess) return set_error(GRACE_OUT_OF_MEMORY, __FILE__, __LINE__, hipGetErrorString(e));
+        ts.hits.capacity = need;
     }
-    // Per-hit and triangle traces cannot split a packet among waves (their outputs are ordered
-    // / reduced per ray inside one wave); with few rays they use narrower packets instead:
-    // 2-4x the waves, each with a tighter beam, on a chip that would otherwise sit idle.
-    int width = 64;
-    if (ts.width > 0) width = ts.width;
-    else if (ordered(MODE) && !hits_split)
-        while (width > 16 && ceil_div(n_rays, size_t(width)) < 4096) width /= 2;
-    // Hit counts and column densities split packets eight ways at most; a batch too small to fill
-    // the chip even then (< 512 packets) also gets narrower packets (10^7 particles, 12288 HEALPix
-    // rays: 3.5 -> 2.0 ms at 16 rays per packet; from 49152 rays on it loses: config 3 0.87 -> 0.95 ms).
-    else if (class_split(MODE) && ts.split <= 0)
-        while (width > 16 && ceil_div(n_rays, size_t(width)) * SUM_CLASSES < 4096) width /= 2;
-    a.width = width;
-    const int n_packets = ceil_div(n_rays, size_t(width));
-    // Waves per packet: two resident sets of waves (2 x 8192) for small ray batches.
-    int split = 1;
-    if (class_split(MODE)) {
-        // (column densities: a batch of exactly 16384 packets -- the 1024^2 frame -- still gets a
-        // second wave per packet, 32768 waves; see choose_split.  Larger batches run one.)
-        const size_t wave_budget = f4_sums(MODE) ? 16385 : 16384;
-        if (ts.split > 0) split = ts.split;
-        else {
-            while (split < SUM_CLASSES && size_t(n_packets) * split < wave_budget) split *= 2;
-            // (the device picks the working waves per packet: scenes with spheres smaller than the ray
-            // spacing want four -- see lat_split below --, one-direction batches two, others one)
-            if (f4_sums(MODE) && split > 1 && split < ts.lat_split && ts.ray_reorder && n_rays > 64
-                && width == 64)
-                split = ts.lat_split;
-        }
-    }
-    if (hits_split) split = hit_split;
-    a.split = split;
-    a.split_dev = nullptr;
-    // (the working waves per packet are chosen on the device, by ray_keys_kernel)
-    const bool dev_split = f4_class_split(MODE) && split > 1 && ts.split <= 0;
-    {
-        constexpr bool need_b = f4_integrals(MODE);
-        const bool fast_b = f4_sums(MODE) && !ts.exact_integrals;
-        const bool reorder = ts.ray_reorder && n_rays > 64;
-        // ---- which cached records does this call use?  (see trace_state.hpp) -------------------
-        // NONE: derive into the workspace (a scene / batch seen for the first time);  FILL: the
-        // same arrays as the previous call -- derive into the cache;  CHECK: cached -- validate by
-        // signature on the device, the gated pre-pass recomputes if stale;  TRUST: cached, and the
-        // caller has switched validation off.
-        enum { USE_NONE, USE_FILL, USE_CHECK, USE_TRUST };
-        auto decide = [&](const bool have, const bool pinned, const bool repeat) {
-            if (have) return ts.cache_validation ? USE_CHECK : USE_TRUST;
-            return (ts.cache_auto && repeat && !pinned) ? USE_FILL : USE_NONE;
-        };
-        int scene_use = USE_NONE, rays_use = USE_NONE;
-        SceneKey skey;
-        skey.kind = primitive(MODE);
-        skey.prims = a.spheres; skey.nodes = a.nodes; skey.leaves = a.leaves;
-        skey.n_prims = n_spheres; skey.n_nodes = n_nodes;
-        // The fp64 modes' records (inflated for the fp64 test) are derived per call: the scene cache
-        // is neither read nor filled nor counted as seen by them, so float calls on the same arrays
-        // cache exactly as they would without them.
-        if (!fp64(MODE) && MODE != MODE_STATS) {
-            scene_use = decide(ts.scene.valid && ts.scene.key == skey, ts.scene.valid && ts.scene.pinned,
-                               ts.scene.seen == skey);
-            ts.scene.seen = skey;
-            if (scene_use == USE_FILL && scene_cache_alloc(ts, skey) != GRACE_OK) scene_use = USE_NONE;   // (no memory: no cache)
-        }
-        RayKey rkey;
-        rkey.rays = a.rays; rkey.n = n_rays;
-        if (reorder) {
-            rays_use = decide(ts.rays.valid && ts.rays.key == rkey, ts.rays.valid && ts.rays.pinned,
-                              ts.rays.seen == rkey);
-            ts.rays.seen = rkey;
-            if (rays_use == USE_FILL && rays_cache_alloc(ts, rkey) != GRACE_OK) rays_use = USE_NONE;
-        }
-        const bool scene_cached = scene_use != USE_NONE, rays_cached = rays_use != USE_NONE;
-        const bool any_sig = scene_use == USE_FILL || scene_use == USE_CHECK || rays_use == USE_FILL || rays_use == USE_CHECK;
-        const size_t n_clusters = (n_spheres + 63) / 64;
-        GRACE_TRY(frame.begin((scene_cached ? 0 : Workspace::aligned((n_spheres + 4) * sizeof(float4))
-                                               + Workspace::aligned((n_spheres + 4) * sizeof(float2))
-                                               + Workspace::aligned(n_nodes * sizeof(int2))
-                                               + Workspace::aligned(cluster_record_count(n_spheres) * sizeof(float4))
-                                               + (MODE == MODE_TRI ? Workspace::aligned(72 * (n_spheres + 4)) : 0))
-                                   + (hits_split ? 2 * Workspace::aligned(n_rays * size_t(hit_chunks) * 4)
-                                                   + Workspace::aligned(hit_packets * hit_split * sizeof(int4))
-                                                   + Workspace::aligned(hit_packets * size_t(hit_chunks) * 4)
-                                                   + 4 * Workspace::aligned(hit_packets * 4 + 64)
-                                                   + Workspace::aligned(n_rays * 4) : 0)
-                                   + (f4_sums(MODE) ? Workspace::aligned(n_rays * SUM_CLASSES * channels(MODE) * 4) : 0)
-                                   + (double_sums(MODE) ? Workspace::aligned(n_rays * SUM_CLASSES * 8) : 0)
-                                   + (reorder ? 2 * Workspace::aligned(n_rays * 4)
-                                                + sort_ws_bytes(n_rays, 4, 0) : 0)
-                                   + (any_sig ? Workspace::aligned(sig_partial_words() * 8) : 0) + 1024, stream));
-        if (any_sig) {
-            SigRequest rq;
-            if (scene_use == USE_FILL || scene_use == USE_CHECK) {
-                rq.prims = a.spheres; rq.prims_bytes = n_spheres * (MODE == MODE_TRI ? 36 : 16);
-                rq.nodes = a.nodes; rq.nodes_bytes = n_nodes * 64;
-                rq.leaves = a.leaves; rq.leaves_bytes = (n_nodes + 1) * 16;
-                rq.scene_ctl = ts.scene.ctl; rq.scene_force = scene_use == USE_FILL;
-            }
-            if (rays_use == USE_FILL || rays_use == USE_CHECK) {
-                rq.rays = a.rays; rq.rays_bytes = n_rays * 28;
-                rq.rays_ctl = ts.rays.ctl; rq.rays_force = rays_use == USE_FILL; rq.rays_ext = ts.rays.ext;
-            }
-            GRACE_TRY(launch_signatures(rq, Workspace::take<unsigned long long>(sig_partial_words()), stream));
-        }
-        if (scene_cached) {
-            Scene& sc = ts.scene;
-            if (scene_use != USE_TRUST) {
-                // (gated by the cache's stale flag: a first fill is forced stale)
-                GRACE_TRY(scene_fill(skey.kind, a.spheres, n_spheres, a.nodes, n_nodes, a.leaves, sc.A, sc.B1, sc.B50,
-                                     sc.T64, sc.node_prims, sc.C, stream, &sc.ctl->stale));
-                sc.valid = true;
-            }
-            a.A = sc.A;
-            a.B = need_b ? (fast_b ? sc.B50 : sc.B1) : nullptr;
-            a.T64 = sc.T64;
-            a.node_prims = sc.node_prims;
-            a.C = sc.C;
-        } else {
-            float4* A = Workspace::take<float4>(n_spheres + 4);
-            float2* B = need_b ? Workspace::take<float2>(n_spheres + 4) : nullptr;
-            double* T64 = (MODE == MODE_TRI) ? Workspace::take<double>(9 * (n_spheres + 4)) : nullptr;
-            int2* node_prims = Workspace::take<int2>(n_nodes);
-            float4* C = Workspace::take<float4>(cluster_record_count(n_spheres));
-            GRACE_TRY(scene_fill(skey.kind, primitive(MODE) == PRIM_D4 ? static_cast<const void*>(a.spheres_d) : a.spheres,
-                                 n_spheres, a.nodes, n_nodes, a.leaves, A, fast_b ? nullptr : B, fast_b ? B : nullptr,
-                                 T64, node_prims, C, stream));
-            a.A = A; a.B = B; a.T64 = T64; a.node_prims = node_prims; a.C = C;
-        }
-        a.partial = f4_sums(MODE) ? Workspace::take<float>(n_rays * SUM_CLASSES * channels(MODE)) : nullptr;
-        a.partial_d = double_sums(MODE) ? Workspace::take<double>(n_rays * SUM_CLASSES) : nullptr;
-        if (hits_split) {
-            chunk_counts = Workspace::take<int>(n_rays * size_t(hit_chunks));
-            chunk_off = Workspace::take<int>(n_rays * size_t(hit_chunks));
-            wave_map = Workspace::take<int4>(hit_packets * hit_split);
-            pk_prefix = Workspace::take<uint32_t>(hit_packets * size_t(hit_chunks));
-            pk_total = Workspace::take<uint32_t>(hit_packets + 16);
-            pk_first = Workspace::take<int>(hit_packets + 16);
-            pk_parts = Workspace::take<int>(hit_packets + 16);
-            n_wave_map = Workspace::take<int>(16);
-            scratch_counts = Workspace::take<int>(n_rays);
-        }
-        // Subtrees of up to this many primitives are swept -- cluster tests, then culling rounds
-        // over the surviving clusters -- rather than descended.
-        // Axis-aligned packets test a cluster's box against their origin rectangle (sharp: large
-        // subtrees pay; 16384 measured best in round 2); pencil packets test it
-        // against the bundle's side planes, general packets its circumscribed sphere.
-        // (re-measured after the pencil cluster test became a box-against-side-planes test: sphere
-        // scenes now prefer 8192 there too -- config 2 column densities 1.74 -> 1.46 ms, hit counts
-        // 1.54 -> 1.19, config 3 0.94 -> 0.87 --; triangles, culled through bounding spheres, keep 512:
-        // 5.3 / 4.6 / 2.8 ms for the three cameras against 6.9 / 5.8 / 3.0 at 8192)
-        // (round 3, after the test-free 16-byte survivor rounds made the sweeps cheaper relative to
-        // the walk: axis-aligned packets prefer 32768 -- 1024^2 frame 2.82 -> 2.78 ms, its 1/2, 1/4,
-        // 1/8 shards 1.53 -> 1.46, 0.84 -> 0.80, 0.51 -> 0.47 ms (their split waves each repeat the
-        // walk); 65536 the same, 131072 worse; clustered scenes +3 %.  Pencil / general packets stay
-        // at 8192: config 2 1.47 / 1.50 / 1.50 ms at 8192 / 16384 / 32768, config 3 0.87 / 0.83 / 0.86.)
-        const int auto_treelet = (MODE == MODE_TRI) ? 512 : 8192, auto_treelet_axis = 32768;
-#ifdef GRACE_PACKET_STATS
-        a.treelet = ts.treelet < 0 ? auto_treelet : ts.treelet;
-        a.treelet_axis = ts.treelet < 0 ? auto_treelet_axis : ts.treelet;
-#else
-        a.treelet = (MODE == MODE_STATS) ? 0 : (ts.treelet < 0 ? auto_treelet : ts.treelet);
-        a.treelet_axis = (MODE == MODE_STATS) ? 0 : (ts.treelet < 0 ? auto_treelet_axis : ts.treelet);
-#endif
-        if (reorder) {
-            // ext: 12 extents + [12] the device-side split + [13] the lattice flag (per call)
-            uint32_t* ext = Workspace::take<uint32_t>(16);
-            uint32_t* keys = Workspace::take<uint32_t>(n_rays);
-            uint32_t* perm = Workspace::take<uint32_t>(n_rays);
-            uint32_t* lat_flag = has_lattice(MODE) ? ext + 13 : nullptr;
-            int* split_dev = dev_split ? reinterpret_cast<int*>(ext + 12) : nullptr;
-            const int split_flags = f4_sums(MODE) ? SPLIT_WIDE_BUDGET : 0;
-            if (rays_cached) {
-                RayOrder& ro = ts.rays;
-                if (rays_use != USE_TRUST) {
-                    // (gated by the cache's stale flag; the order lands in the cache's own buffers)
-                    GRACE_TRY(ray_order(a.rays, n_rays, ro.ext, keys, ro.perm, nullptr, nullptr, 0, 0, nullptr,
-                                        stream, &ro.ctl->stale));
-                    ro.valid = true;
-                }
-                // cached order: only this call's device-side choices remain
-                if (lat_flag || split_dev) {
-                    GRACE_TRY(launch_choose_variants(ro.ext, int(n_rays), a.C + 2 * n_clusters, lat_flag,
-                                                     n_packets, split | split_flags, split_dev, stream));
-                }
-                a.perm = ro.perm;
-            } else {
-                GRACE_TRY(ray_order(a.rays, n_rays, ext, keys, perm, a.C + 2 * n_clusters, lat_flag, n_packets,
-                                    split | split_flags, split_dev, stream));
-                a.perm = perm;
-            }
-            if (has_lattice(MODE)) a.lat_dev = reinterpret_cast<const int*>(ext + 13);
-            if (dev_split) a.split_dev = reinterpret_cast<const int*>(ext + 12);
-        }
-    }
-    a.n_rays = int(n_rays);
-    a.n_nodes = int(n_nodes);
-    a.status = ts.status;
-    a.n_prims = int(n_spheres);
-    a.group_shift = group_shift(n_spheres);
-    a.chunk_shift = hit_chunk_shift;
-    a.n_chunks = hit_chunks;
-    a.chunk_counts = nullptr;
-    a.chunk_off = chunk_off;
-    a.wave_map = wave_map;
-    a.n_wave_map = n_wave_map;
-    if (split > 1 && output(MODE) == OUT_COUNTS)
+    FrameGuard frame;
+    TraceBuffers b;
+    GRACE_TRY(use_records<MODE>(ts, a, b, frame, p, n_rays, n_spheres, n_nodes, stream));
+    a.width = p.width; a.split = p.split; a.treelet = p.treelet; a.treelet_axis = p.treelet_axis;
+    a.n_rays = int(n_rays); a.n_nodes = int(n_nodes); a.n_prims = int(n_spheres); a.status = ts.status;
+    a.group_shift = group_shift(n_spheres); a.chunk_shift = p.hit_chunk_shift; a.n_chunks = p.hit_chunks;
+    a.partial = b.partial; a.partial_d = b.partial_d;
+    a.chunk_off = b.chunk_off; a.wave_map = b.wave_map; a.n_wave_map = b.n_wave_map;
+    if (p.split > 1 && output(MODE) == OUT_COUNTS)
         GRACE_TRY_HIP(hipMemsetAsync(a.out_counts, 0, n_rays * sizeof(int), stream));
-    if (keep_chunks && split > 1) {
+    if (p.keep_chunks && p.split > 1) {
         a.chunk_counts = ts.hits.chunk_counts;
-        GRACE_TRY_HIP(hipMemsetAsync(ts.hits.chunk_counts, 0, n_rays * size_t(hit_chunks) * 4, stream));
-        ts.hits.valid = true;
-        ts.hits.rays = a.rays; ts.hits.n_rays = n_rays;
-        ts.hits.prims = a.spheres; ts.hits.n_prims = n_spheres; ts.hits.n_chunks = hit_chunks;
+        GRACE_TRY_HIP(hipMemsetAsync(ts.hits.chunk_counts, 0, n_rays * size_t(p.hit_chunks) * 4, stream));
+        ts.hits.valid = true; ts.hits.rays = a.rays; ts.hits.n_rays = n_rays;
+        ts.hits.prims = a.spheres; ts.hits.n_prims = n_spheres; ts.hits.n_chunks = p.hit_chunks;
     }
     if (ts.timing) {
-        if (!ts.ev0) {
-            GRACE_TRY_HIP(hipEventCreate(&ts.ev0));
-            GRACE_TRY_HIP(hipEventCreate(&ts.ev1));
-        }
+        if (!ts.ev0) { GRACE_TRY_HIP(hipEventCreate(&ts.ev0)); GRACE_TRY_HIP(hipEventCreate(&ts.ev1)); }
         GRACE_TRY_HIP(hipEventRecord(ts.ev0, stream));
     }
-    const int grid = ceil_div(size_t(n_packets) * split, TRACE_BLOCK / 64);
     ts.last_lat_dev = a.lat_dev; ts.last_lat_stream = stream;
-    // Both variants of a kernel with a lattice instantiation (the device flag lets one run).
-    auto both = [&](auto mode_tag, auto split_tag, auto alt_tag, const TraceArgs& args) {
-        constexpr int M = decltype(mode_tag)::value;
-        constexpr bool S = decltype(split_tag)::value, A = decltype(alt_tag)::value;
-        trace_kernel<M, S, A, false><<<grid, TRACE_BLOCK, 0, stream>>>(args);
-        if (args.lat_dev) trace_kernel<M, S, A, true><<<grid, TRACE_BLOCK, 0, stream>>>(args);
-    };
-    using T = std::true_type; using F = std::false_type;
-    using M_ = std::integral_constant<int, MODE>;
-    // A batch of >= 16384 packets runs one wave per packet -- unless the device flag says the scene
-    // holds spheres smaller than the ray spacing (clustered SPH data: dense cores).  Such scenes
-    // have packets dozens of times heavier than the median (10^7 particles, 90 % of them in 50
-    // clumps: with the lattice cull the heaviest of 16384 waves still lived 14x the mean and set
-    // the kernel time), so the lattice instantiation of these batches is the class-split kernel
-    // with four waves per packet: the heaviest packets' work is spread over four SIMDs (measured
-    // on two clustered scenes: K = 2 / 4 / 8 -> 3.62 / 3.47 / 4.24 ms and 4.24 / 3.42 / 3.71 ms;
-    // one wave: 4.66 and 6.78 ms).  Same class sums, same bits.
-    const bool lat_split = f4_class_split(MODE) && split == 1 && a.lat_dev && width == 64
-        && ts.lat_split > 0 && ts.split <= 0;   // (an explicit grace_trace_set_packet_split is obeyed)
-    auto one_or_split = [&](auto alt_tag) -> grace_status {
-        constexpr bool A = decltype(alt_tag)::value;
-        if (MODE == MODE_COUNT) GRACE_TRY_HIP(hipMemsetAsync(a.out_counts, 0, n_rays * sizeof(int), stream));
-        trace_kernel<MODE, false, A, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
-        GRACE_CHECK_LAUNCH();
-        TraceArgs a8 = a;
-        a8.split = ts.lat_split; a8.split_dev = nullptr;
-        trace_kernel<MODE, true, A, true><<<ceil_div(size_t(n_packets) * ts.lat_split, TRACE_BLOCK / 64), TRACE_BLOCK, 0, stream>>>(a8);
-        GRACE_CHECK_LAUNCH();
-        if (MODE == MODE_CUMULATIVE) {
-            combine_classes_kernel<float><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial, int(n_rays), ts.lat_split,
-                                                                              nullptr, a.out_sums, a.lat_dev);
-            GRACE_CHECK_LAUNCH();
-        }
-        if (weighted(MODE)) {
-            combine_channel_classes_kernel<<<ceil_div(n_rays * channels(MODE), 256), 256, 0, stream>>>(
-                a.partial, int(n_rays), channels(MODE), ts.lat_split, nullptr, a.out_sums, a.out_stride, a.lat_dev);
-            GRACE_CHECK_LAUNCH();
-        }
-        return GRACE_OK;
-    };
-    if constexpr (f4_sums(MODE)) {
-        if (ts.exact_integrals) {
-            if (split > 1) both(M_(), T(), F(), a);
-            else if (lat_split) GRACE_TRY(one_or_split(F()));
-            else both(M_(), F(), F(), a);
-        } else {
-            if (split > 1) both(M_(), T(), T(), a);
-            else if (lat_split) GRACE_TRY(one_or_split(T()));
-            else both(M_(), F(), T(), a);
-        }
-    } else if constexpr (MODE == MODE_HITS) {
-        if (hits_split) {
-            // 1. hits per (ray, chunk): the counting walk, split by summation class -- unless the
-            //    hit-count call made for this trace_sph has kept them (grace_trace_hitcounts_keep_f4)
-            const int* counts = ts.hits.chunk_counts;
-            if (!reuse_chunks) {
-                TraceArgs c = a;
-                c.chunk_counts = chunk_counts;
-                c.out_counts = scratch_counts;
-                GRACE_TRY_HIP(hipMemsetAsync(chunk_counts, 0, n_rays * size_t(hit_chunks) * 4, stream));
-                GRACE_TRY_HIP(hipMemsetAsync(scratch_counts, 0, n_rays * 4, stream));
-                both(std::integral_constant<int, MODE_COUNT>(), T(), F(), c);
-                GRACE_CHECK_LAUNCH();
-                counts = chunk_counts;
-            }
-            // 2. output offsets per (ray, chunk); the launched waves dealt to the packets by hit
-            //    totals; each packet's chunks cut into its waves' ranges
-            hits_offsets_kernel<<<ceil_div(n_rays, 4), 256, 0, stream>>>(counts, a.offsets, int(n_rays),
-                                                                         hit_chunks, chunk_off);
-            GRACE_CHECK_LAUNCH();
-            hits_plan_kernel<<<n_packets, MAX_HIT_CHUNKS, 0, stream>>>(counts, a.perm, int(n_rays),
-                                                                       hit_chunks, pk_prefix, pk_total);
-            GRACE_CHECK_LAUNCH();
-            hits_assign_kernel<<<1, 1024, 0, stream>>>(pk_total, n_packets, n_packets * split, hit_chunks,
-                                                       pk_first, pk_parts, n_wave_map,
-                                                       ts.hits_stage_split ? 200000ull : 0ull);
-            GRACE_CHECK_LAUNCH();
-            hits_bounds_kernel<<<n_packets, 64, 0, stream>>>(pk_prefix, pk_total, pk_first, pk_parts,
-                                                             hit_chunks, wave_map);
-            GRACE_CHECK_LAUNCH();
-            // 3. the per-hit walk, wave w owning wave_map[w]'s range of chunks
-            //    Heavy packets (output-bandwidth-bound: 10^5 isotropic rays through 10^6 large spheres,
-            //    410 k hits per packet: 18.0 -> 11.0 ms) stage their hits in LDS and store them eight
-            //    per ray at a time; light ones (61 M hits over 768 packets: 3.6 ms direct, 4.5 staged)
-            //    store directly.  The hit total is known on the device only: BOTH variants are
-            //    launched and the plan's flag (hits_assign_kernel) lets one of them run -- no read-back,
-            //    no host synchronisation inside the call.
-            TraceArgs staged = a, direct = a;
-            staged.stage_dev = direct.stage_dev = n_wave_map + 4;
-            staged.stage_want = 1;
-            direct.stage_want = 0;
-            both(M_(), T(), T(), staged);
-            GRACE_CHECK_LAUNCH();
-            both(M_(), T(), F(), direct);
-        } else if (n_packets >= 4096) {
-            both(M_(), F(), T(), a);
-        } else {
-            both(M_(), F(), F(), a);
-        }
-    } else if constexpr (MODE == MODE_COUNT) {
-        if (split > 1) both(M_(), T(), F(), a);
-        else if (lat_split) GRACE_TRY(one_or_split(F()));
-        else both(M_(), F(), F(), a);
-    } else if constexpr (class_split(MODE)) {
-        if (split > 1) trace_kernel<MODE, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);
-        else trace_kernel<MODE, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
-    } else {
-        trace_kernel<MODE, false><<<grid, TRACE_BLOCK, 0, stream>>>(a);
-    }
-    GRACE_CHECK_LAUNCH();
-    GRACE_TRY(stamps_report(MODE));
-    if (double_sums(MODE) && split > 1) {
-        combine_classes_kernel<double><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial_d, int(n_rays), split,
-                                                                                   nullptr, a.out_sums_d);
-        GRACE_CHECK_LAUNCH();
-    }
-    if (MODE == MODE_CUMULATIVE && split > 1) {
-        combine_classes_kernel<float><<<ceil_div(n_rays, 256), 256, 0, stream>>>(a.partial, int(n_rays),
-                                                                                 split, a.split_dev, a.out_sums);
-        GRACE_CHECK_LAUNCH();
-    }
-    if (weighted(MODE) && split > 1) {
-        combine_channel_classes_kernel<<<ceil_div(n_rays * channels(MODE), 256), 256, 0, stream>>>(
-            a.partial, int(n_rays), channels(MODE), split, a.split_dev, a.out_sums, a.out_stride);
-        GRACE_CHECK_LAUNCH();
-    }
+    GRACE_TRY(dispatch<MODE>(ts, a, b, p, reuse_chunks ? ts.hits.chunk_counts : nullptr, n_rays, stream));
     if (ts.timing) {
         GRACE_TRY_HIP(hipEventRecord(ts.ev1, stream));
         ts.ev_valid = true;

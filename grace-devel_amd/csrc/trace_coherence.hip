@@ -98,7 +98,7 @@ __device__ int choose_split(const uint32_t* __restrict__ ext12, int n_packets, i
     const int budget = (launched_arg & SPLIT_WIDE_BUDGET) ? 32768 : 16384;
     int k = launched;
     // (a scene with spheres smaller than the ray spacing has packets of very unequal weight: it
-    // keeps every launched wave -- see lat_split in launch_trace)
+    // keeps every launched wave -- see lat_split in plan_launch, trace.hip)
     if (one_direction && !lattice) {
         // Measured on 1/8 ... 1/1 shards of the 1024^2 frame (2048 ... 16384 packets): best K =
         // 4, 2, 2, 1.  The split kernels run 8 waves per SIMD: 8192 waves fill the chip once;
@@ -112,7 +112,7 @@ __device__ int choose_split(const uint32_t* __restrict__ ext12, int n_packets, i
         if (k < launched && n_packets >= 6144 && n_packets * k * 2 <= budget) k *= 2;
     } else if (!lattice) {
         // incoherent batches: the smallest K that puts 16384 waves in flight (the launch may be
-        // sized for more: column densities, see launch_trace)
+        // sized for more: column densities, see plan_launch)
         k = 1;
         while (k < launched && n_packets * k < 16384) k *= 2;
     }
@@ -209,7 +209,7 @@ __device__ void choose_variants(const uint32_t* __restrict__ ext12, int n, const
         // One origin (point sources, cameras): the rays' spacing at the far end of the longest ray,
         // 4 pi L^2 / n for a full sphere (an upper bound for partial ones).  There is no lattice to
         // cull against, but such scenes have the same very unequal packets: the flag sends the batch
-        // to four waves per packet (launch_trace) all the same.
+        // to four waves per packet (plan_launch) all the same.
         if (!lat && e1 == 0.f && ext12[15] != 0u) {
             const float len = ord2f_u(ext12[15]);
             if (len > 0.f && len < INFINITY) lat = r2_min < 2.0f * (12.566371f * len * len / float(n));
