@@ -1,0 +1,563 @@
+// SPH interpolation at points (grace_interpolate_points_f4 / grace_interpolate_grid_f4): the field
+//   A(p) = sum over spheres i containing p of fl(w_i W(|p - x_i|, H_i))
+// summed per channel in the class order of the column densities, and the number of spheres that
+// contain p.  An extension the reference lacks; the arithmetic is stated in include/grace_hip.h.
+//
+// One wave owns a PACKET of 64 points: a brick of lattice points (8 x 8 x 1 for a slice, 4 x 4 x 4
+// for a volume; positions formed in registers), or 64 consecutive points of a Morton order of the
+// caller's points (keys against the tree's root box, read on the device; sorted by the library's
+// own sort in the call's workspace) that lie in one Morton cell of ~256 points on average: a packet
+// of 64 consecutive sorted points may straddle a jump of the curve and span half the scene, and the
+// wave that owns it then tests every sphere in that box against all its lanes (10^6 random points
+// in bench.py's scene: 99 ms with such packets, most of it the tail of a few straddling waves).
+// Packets start every 64 sorted points and wherever the cell changes (a scan on the device; the
+// grid is launched for the upper bound n / 64 + cells, surplus waves exit).
+//
+// The packet's box is reduced across the wave, and the wave walks the ALBVH against it: wave-uniform node loads and tests, a 128-entry packet stack held one
+// entry per lane (the trace's convention, overflow reported through the status word), left child
+// first, so leaves come in ascending primitive order.  A leaf's primitives are swept in culling
+// rounds of 64-aligned clusters: each lane loads one candidate and tests its box against the
+// packet's box (conservatively: the boxes are widened by 2^-20 of their bounds, far more than the
+// half ulp by which fl(x - H) can move inward); a ballot compacts the survivors into LDS as
+// {x, y, z, H^2}, {1/H, 1/H^3} and the walk's <= 4 weights, and every lane then runs the survivor
+// list in ascending order against its own point.  A cluster never straddles a granule of 1024
+// primitives, so a round is one summation class: the running sum of the current class stays in
+// VGPRs and is swapped with a per-class LDS slot when the class changes -- each class sum is the
+// fp32 sum in ascending index order -- and the epilogue adds the 8 class sums pairwise.
+//
+// Containment d2 < fl(H^2) with d2 formed in fp32 is never true for a point outside the exact box
+// [x - H, x + H] of a sphere (|dx| >= H there, and every fp32 step is monotonic), so the widened
+// box tests drop no contained sphere: results are a function of the point and the scene only.
+#include "common.hpp"
+#include "trace_state.hpp"
+
+#include "grace/generic/morton.h"
+
+using namespace grace_hip;
+
+namespace {
+
+constexpr int IP_BLOCK = 256;
+constexpr int IP_WAVES = IP_BLOCK / 64;
+constexpr int IP_STACK = 128;
+constexpr int IP_CHANNELS = 4;     // channels per walk
+constexpr float IP_SLACK = 9.5367431640625e-07f;   // 2^-20
+
+struct InterpArgs {
+    // points entry point: n_points records of `stride` floats, visited in the order `perm`
+    const float* points;
+    int stride;
+    const uint32_t* perm;
+    int n_points;
+    const uint32_t* starts;      // packet p: sorted points [starts[p], starts[p + 1])
+    const uint32_t* n_starts;    // number of packets (device)
+    // grid entry point (points == nullptr): p(i, j, k) = org + i u + j v + k w
+    float org[3], eu[3], ev[3], ew[3];
+    int dims[3];
+    int brick[3];          // lattice points per packet along i, j, k
+    int nb[2];             // packets along i, j
+    int n_packets;
+    const float4* spheres;
+    const float4* nodes;
+    int n_nodes;
+    const int4* leaves;
+    const int* root;
+    const float* weights;  // this walk's first channel; sphere i's channel c at weights[i w_stride + c]
+    int w_stride;
+    float* out;            // point p's channel c at out[p out_stride + c]
+    int out_stride;
+    int* counts;           // or null
+    int* status;
+    unsigned long long* tests;   // measurement hook: survivor tests (lanes x survivors), or null
+};
+
+// Correctly rounded sqrt for x = 0 or x >= 2^-96 (finite): v_sqrt_f32 is within 1 ulp, the two FMA
+// residuals pick the neighbour if it is closer (the trace's sqrt_rn_normal).
+__device__ __forceinline__ float sqrt_rn_normal(const float x)
+{
+    const float y = __builtin_amdgcn_sqrtf(x);
+    const float ym = __int_as_float(__float_as_int(y) - 1);
+    const float yp = __int_as_float(__float_as_int(y) + 1);
+    const float rm = __builtin_fmaf(-ym, y, x);
+    const float rp = __builtin_fmaf(-yp, y, x);
+    float r = (0.0f >= rm) ? ym : y;
+    r = (0.0f < rp) ? yp : r;
+    return r;
+}
+
+__device__ __forceinline__ float sqrt_rn(const float x)
+{
+    const bool tiny = x < 1.2621774e-29f && x > 0.0f;   // 2^-96: the general expansion (practically never)
+    return __builtin_amdgcn_ballot_w64(tiny) ? __builtin_sqrtf(x) : sqrt_rn_normal(x);
+}
+
+__device__ __forceinline__ float pow4(const float t)
+{
+    const float t2 = t * t;
+    return t2 * t2;
+}
+
+// K = f(q) in the fp32 operation sequence of include/grace_hip.h ("SPH interpolation at points");
+// u = max(1 - q, 0), normalisation constant last.  (-ffp-contract=off: no operation is fused.)
+template <int KIND>
+__device__ __forceinline__ float kernel_f(const float q)
+{
+    const float u = fmaxf(1.0f - q, 0.0f);
+    if constexpr (KIND == GRACE_SPH_KERNEL_CUBIC) {
+        const float inner = ((6.0f * q - 6.0f) * (q * q)) + 1.0f;
+        const float outer = 2.0f * ((u * u) * u);
+        return (q < 0.5f ? inner : outer) * float(8.0 / M_PI);
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_QUARTIC) {
+        const float t2 = fmaxf(u - 0.4f, 0.0f), t3 = fmaxf(u - 0.8f, 0.0f);
+        return ((pow4(u) - 5.0f * pow4(t2)) + 10.0f * pow4(t3)) * float(25.0 * 39.0625 / (32.0 * M_PI));
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_QUINTIC) {
+        const float t2 = fmaxf(u - float(1.0 / 3.0), 0.0f), t3 = fmaxf(u - float(2.0 / 3.0), 0.0f);
+        return ((pow4(u) * u - 6.0f * (pow4(t2) * t2)) + 15.0f * (pow4(t3) * t3))
+            * float(9.0 * 243.0 / (40.0 * M_PI));
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_WENDLAND_C2) {
+        return (pow4(u) * (4.0f * q + 1.0f)) * float(21.0 / (2.0 * M_PI));
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_WENDLAND_C4) {
+        const float u6 = pow4(u) * (u * u);
+        return (u6 * (q * (q * float(35.0 / 3.0) + 6.0f) + 1.0f)) * float(495.0 / (32.0 * M_PI));
+    } else {
+        static_assert(KIND == GRACE_SPH_KERNEL_WENDLAND_C6, "built-in SPH kernels only");
+        const float u4 = pow4(u);
+        return ((u4 * u4) * (q * (q * (32.0f * q + 25.0f) + 8.0f) + 1.0f)) * float(1365.0 / (64.0 * M_PI));
+    }
+}
+
+__device__ __forceinline__ float wave_min(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// [lo, hi] widened by 2^-20 of each bound overlaps the packet box (NaN: no).
+__device__ __forceinline__ bool overlaps(const float lo, const float hi, const float plo, const float phi)
+{
+    return lo - fabsf(lo) * IP_SLACK <= phi && hi + fabsf(hi) * IP_SLACK >= plo;
+}
+
+// Orders LDS stores of some lanes before loads of others within the wave.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// NW = channels of this walk (0: counts only).
+template <int KIND, int NW>
+__global__ __launch_bounds__(IP_BLOCK) void interpolate_kernel(const InterpArgs a)
+{
+    constexpr int NS = NW > 0 ? NW : 1;
+    __shared__ float4 s_rec[IP_WAVES][64];               // survivors: {x, y, z, H^2}
+    __shared__ float2 s_inv[IP_WAVES][NW > 0 ? 64 : 1];  // {1/H, 1/H^3}
+    __shared__ float s_w[IP_WAVES][NW > 0 ? 64 : 1][NS]; // weights
+    __shared__ float s_cls[IP_WAVES][NW > 0 ? 8 : 1][NS][64];   // class sums, per lane
+
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int packet = blockIdx.x * IP_WAVES + wv;
+    if (packet >= a.n_packets) return;                   // (wave-uniform)
+
+    // ---- the packet's points ----
+    float px, py, pz;
+    bool active;
+    size_t slot;                                         // output index of this lane's point
+    if (a.points) {
+        if (packet >= int(*a.n_starts)) return;          // (wave-uniform)
+        const uint32_t first = a.starts[packet], end = a.starts[packet + 1];
+        const uint32_t sp = first + uint32_t(lane);
+        active = sp < end;
+        const uint32_t src = active ? a.perm[sp] : 0u;
+        slot = src;
+        const float* q = a.points + size_t(src) * a.stride;
+        px = q[0]; py = q[1]; pz = q[2];
+    } else {
+        const int bi = packet % a.nb[0], bj = (packet / a.nb[0]) % a.nb[1], bk = packet / (a.nb[0] * a.nb[1]);
+        const int li = lane % a.brick[0], lj = (lane / a.brick[0]) % a.brick[1], lk = lane / (a.brick[0] * a.brick[1]);
+        const int i = bi * a.brick[0] + li, j = bj * a.brick[1] + lj, k = bk * a.brick[2] + lk;
+        active = i < a.dims[0] && j < a.dims[1] && k < a.dims[2];
+        slot = (size_t(k) * a.dims[1] + j) * a.dims[0] + i;
+        const float fi = float(i), fj = float(j), fk = float(k);
+        px = ((a.org[0] + fi * a.eu[0]) + fj * a.ev[0]) + fk * a.ew[0];
+        py = ((a.org[1] + fi * a.eu[1]) + fj * a.ev[1]) + fk * a.ew[1];
+        pz = ((a.org[2] + fi * a.eu[2]) + fj * a.ev[2]) + fk * a.ew[2];
+    }
+    if (!active) px = py = pz = __int_as_float(0x7fc00000);   // NaN: outside every box and sphere
+    // (fminf / fmaxf skip NaN points; a packet of NaN points keeps +inf / -inf and culls everything)
+    const float plo_x = wave_min(px), phi_x = wave_max(px);
+    const float plo_y = wave_min(py), phi_y = wave_max(py);
+    const float plo_z = wave_min(pz), phi_z = wave_max(pz);
+
+    // ---- class sums ----
+    float acc[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) acc[c] = 0.0f;
+    if constexpr (NW > 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int c = 0; c < NW; ++c) s_cls[wv][k][c][lane] = 0.0f;
+    }
+    int cur = 0;                                         // class of acc (wave-uniform)
+    int count = 0;
+    unsigned long long tests = 0;
+
+    // ---- packet stack: entry e in lane (e & 63) of stk0 (e < 64) or stk1 ----
+    int stk0 = 0, stk1 = 0, sp = -1;
+    bool overflow = false;
+    auto push = [&](const int value) {
+        if (sp >= IP_STACK - 1) { overflow = true; return; }   // bounds check before every push
+        ++sp;
+        if (sp < 64) stk0 = lane == sp ? value : stk0;
+        else stk1 = lane == sp - 64 ? value : stk1;
+    };
+    push(*a.root);
+
+    while (sp >= 0) {
+        const int idx = sp < 64 ? __builtin_amdgcn_readlane(stk0, sp) : __builtin_amdgcn_readlane(stk1, sp - 64);
+        --sp;
+        if (idx < a.n_nodes) {
+            const float4* np = a.nodes + 4 * size_t(idx);
+            const float4 n0 = np[0], L = np[1], R = np[2], Z = np[3];
+            const bool hit_l = overlaps(L.x, L.y, plo_x, phi_x) && overlaps(L.z, L.w, plo_y, phi_y)
+                && overlaps(Z.x, Z.y, plo_z, phi_z);
+            const bool hit_r = overlaps(R.x, R.y, plo_x, phi_x) && overlaps(R.z, R.w, plo_y, phi_y)
+                && overlaps(Z.z, Z.w, plo_z, phi_z);
+            if (hit_r) push(__float_as_int(n0.y));
+            if (hit_l) push(__float_as_int(n0.x));       // popped first: ascending primitive order
+            continue;
+        }
+        const int4 lf = a.leaves[idx - a.n_nodes];
+        const int r_lo = lf.x, r_hi = lf.x + lf.y;
+        for (int cl = r_lo >> 6; cl <= (r_hi - 1) >> 6; ++cl) {
+            const int pj = (cl << 6) + lane;
+            const bool in = pj >= r_lo && pj < r_hi;
+            const int pc = min(max(pj, r_lo), r_hi - 1);
+            const float4 s = a.spheres[pc];
+            const bool keep = in && overlaps(s.x - s.w, s.x + s.w, plo_x, phi_x)
+                && overlaps(s.y - s.w, s.y + s.w, plo_y, phi_y) && overlaps(s.z - s.w, s.z + s.w, plo_z, phi_z);
+            const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
+            if (mask == 0ull) continue;
+            const int n_surv = __builtin_popcountll(mask);
+            if constexpr (NW > 0) {
+                const int cls = (cl >> (GRANULE_SHIFT - 6)) & (SUM_CLASSES - 1);
+                if (cls != cur) {
+#pragma unroll
+                    for (int c = 0; c < NW; ++c) {
+                        s_cls[wv][cur][c][lane] = acc[c];
+                        acc[c] = s_cls[wv][cls][c][lane];
+                    }
+                    cur = cls;
+                }
+            }
+            if (keep) {
+                const int pos = __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
+                s_rec[wv][pos] = make_float4(s.x, s.y, s.z, s.w * s.w);
+                if constexpr (NW > 0) {
+                    const float ih = 1.0f / s.w;
+                    s_inv[wv][pos] = make_float2(ih, (ih * ih) * ih);
+#pragma unroll
+                    for (int c = 0; c < NW; ++c) s_w[wv][pos][c] = a.weights[size_t(pc) * a.w_stride + c];
+                }
+            }
+            wave_sync();
+            tests += uint64_t(n_surv);
+            for (int j = 0; j < n_surv; ++j) {
+                const float4 r = s_rec[wv][j];
+                const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
+                const float d2 = (dx * dx + dy * dy) + dz * dz;
+                if (d2 < r.w) {
+                    ++count;
+                    if constexpr (NW > 0) {
+                        const float2 inv = s_inv[wv][j];
+                        const float W = kernel_f<KIND>(sqrt_rn(d2) * inv.x) * inv.y;
+#pragma unroll
+                        for (int c = 0; c < NW; ++c) acc[c] = acc[c] + s_w[wv][j][c] * W;
+                    }
+                }
+            }
+            wave_sync();
+        }
+    }
+
+    if (overflow && lane == 0) *a.status = GRACE_STACK_OVERFLOW;
+    const unsigned long long n_active = __builtin_popcountll(__builtin_amdgcn_ballot_w64(active));
+    if (a.tests && lane == 0) atomicAdd(a.tests, tests * n_active);
+    if (!active) return;
+    if (a.counts) a.counts[slot] = count;
+    if constexpr (NW > 0) {
+#pragma unroll
+        for (int c = 0; c < NW; ++c) s_cls[wv][cur][c][lane] = acc[c];
+#pragma unroll
+        for (int c = 0; c < NW; ++c) {
+            float t[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t[k] = s_cls[wv][k][c][lane];
+            const float s01 = t[0] + t[1], s23 = t[2] + t[3], s45 = t[4] + t[5], s67 = t[6] + t[7];
+            a.out[slot * a.out_stride + c] = (s01 + s23) + (s45 + s67);
+        }
+    }
+}
+
+// 30-bit Morton keys of the points against the tree's root box (read here: no host round trip);
+// points are clamped into the box (NaN: to its lower corner).
+__global__ __launch_bounds__(256) void interp_keys_kernel(const float* __restrict__ pts, size_t n, int stride,
+                                                          const float4* __restrict__ nodes, int n_nodes,
+                                                          const int* __restrict__ root, uint32_t* __restrict__ keys)
+{
+    const int r = *root;
+    float lo[3] = { 0.f, 0.f, 0.f }, hi[3] = { 0.f, 0.f, 0.f };
+    if (r >= 0 && r < n_nodes) {
+        const float4 L = nodes[4 * size_t(r) + 1], R = nodes[4 * size_t(r) + 2], Z = nodes[4 * size_t(r) + 3];
+        lo[0] = fminf(L.x, R.x); hi[0] = fmaxf(L.y, R.y);
+        lo[1] = fminf(L.z, R.z); hi[1] = fmaxf(L.w, R.w);
+        lo[2] = fminf(Z.x, Z.z); hi[2] = fmaxf(Z.y, Z.w);
+    }
+    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+        uint32_t c[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float v = fminf(fmaxf(pts[i * size_t(stride) + d], lo[d]), hi[d]);
+            const float ext = hi[d] - lo[d];
+            const float t = ext > 0.0f ? (v - lo[d]) / ext : 0.0f;
+            c[d] = min(uint32_t(fmaxf(t, 0.0f) * 1023.0f), 1023u);
+        }
+        keys[i] = grace::morton_key(c[0], c[1], c[2]);
+    }
+}
+
+// Packet starts of the sorted points: every 64th point and every change of the Morton cell
+// (key >> shift).  flags -> (scan) -> positions; the last thread also writes the end sentinel.
+__global__ __launch_bounds__(256) void interp_flags_kernel(const uint32_t* __restrict__ keys, size_t n, int shift,
+                                                           uint32_t* __restrict__ flags)
+{
+    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+        flags[i] = (i % 64 == 0 || (keys[i] >> shift) != (keys[i - 1] >> shift)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void interp_starts_kernel(const uint32_t* __restrict__ flags,
+                                                            const uint32_t* __restrict__ pos, size_t n,
+                                                            uint32_t* __restrict__ starts)
+{
+    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+        if (flags[i]) starts[pos[i]] = uint32_t(i);
+        if (i == n - 1) starts[pos[i] + flags[i]] = uint32_t(n);
+    }
+}
+
+// Process-wide measurement hook (grace_interpolate_enable_stats): a device counter of survivor tests.
+unsigned long long* g_tests = nullptr;
+bool g_stats = false;
+
+grace_status ensure_status(TraceState& ts, hipStream_t stream)
+{
+    if (!ts.status) {
+        GRACE_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&ts.status), sizeof(int)));
+        GRACE_TRY_HIP(hipMemsetAsync(ts.status, 0, sizeof(int), stream));
+    }
+    return GRACE_OK;
+}
+
+template <int KIND>
+grace_status launch_kind(const InterpArgs& a, int nw, hipStream_t stream)
+{
+    const int blocks = ceil_div(size_t(a.n_packets), IP_WAVES);
+    switch (nw) {
+    case 1: interpolate_kernel<KIND, 1><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
+    case 2: interpolate_kernel<KIND, 2><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
+    case 3: interpolate_kernel<KIND, 3><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
+    default: interpolate_kernel<KIND, 4><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
+    }
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+grace_status launch_walk(const InterpArgs& a, int kind, int nw, hipStream_t stream)
+{
+    if (nw == 0) {
+        interpolate_kernel<GRACE_SPH_KERNEL_CUBIC, 0><<<ceil_div(size_t(a.n_packets), IP_WAVES), IP_BLOCK, 0, stream>>>(a);
+        GRACE_CHECK_LAUNCH();
+        return GRACE_OK;
+    }
+    switch (kind) {
+    case GRACE_SPH_KERNEL_CUBIC: return launch_kind<GRACE_SPH_KERNEL_CUBIC>(a, nw, stream);
+    case GRACE_SPH_KERNEL_QUARTIC: return launch_kind<GRACE_SPH_KERNEL_QUARTIC>(a, nw, stream);
+    case GRACE_SPH_KERNEL_QUINTIC: return launch_kind<GRACE_SPH_KERNEL_QUINTIC>(a, nw, stream);
+    case GRACE_SPH_KERNEL_WENDLAND_C2: return launch_kind<GRACE_SPH_KERNEL_WENDLAND_C2>(a, nw, stream);
+    case GRACE_SPH_KERNEL_WENDLAND_C4: return launch_kind<GRACE_SPH_KERNEL_WENDLAND_C4>(a, nw, stream);
+    default: return launch_kind<GRACE_SPH_KERNEL_WENDLAND_C6>(a, nw, stream);
+    }
+}
+
+// Checks shared by both entry points, and the scene / output fields of the arguments.
+grace_status interp_common(InterpArgs& a, const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                           size_t n_nodes, const int* d_leaves, const int* d_root, const float* d_weights,
+                           int n_channels, float* d_out, int* d_counts, TraceState** ts_out)
+{
+    GRACE_REQUIRE(d_spheres && d_nodes && d_leaves && d_root, "interpolate: null scene pointer");
+    GRACE_REQUIRE(n_nodes >= 1 && n_nodes < (size_t(1) << 30), "interpolate: bad node count");
+    GRACE_REQUIRE(n_spheres > 0 && n_spheres < (size_t(1) << 31), "interpolate: bad sphere count");
+    GRACE_REQUIRE(d_out || d_counts, "interpolate: no output");
+    if (d_out) {
+        GRACE_REQUIRE(n_channels >= 1 && n_channels <= 64, "interpolate: channels must be 1..64");
+        GRACE_REQUIRE(d_weights, "interpolate: null weights");
+    }
+    TraceState* ts = nullptr;
+    GRACE_TRY(trace_state(&ts));
+    GRACE_REQUIRE(ts->sph_kernel >= GRACE_SPH_KERNEL_CUBIC && ts->sph_kernel <= GRACE_SPH_KERNEL_WENDLAND_C6,
+                  "interpolate: a custom SPH kernel table has no kernel function f(q)");
+    a.spheres = reinterpret_cast<const float4*>(d_spheres);
+    a.nodes = reinterpret_cast<const float4*>(d_nodes);
+    a.n_nodes = int(n_nodes);
+    a.leaves = reinterpret_cast<const int4*>(d_leaves);
+    a.root = d_root;
+    a.w_stride = n_channels;
+    a.out_stride = n_channels;
+    *ts_out = ts;
+    return GRACE_OK;
+}
+
+// The walks of one call: channels four at a time, counts with the first walk.
+grace_status interp_walks(InterpArgs a, TraceState& ts, const float* d_weights, int n_channels, float* d_out,
+                          int* d_counts, hipStream_t stream)
+{
+    GRACE_TRY(ensure_status(ts, stream));
+    a.status = ts.status;
+    a.tests = nullptr;
+    if (g_stats && g_tests) {
+        GRACE_TRY_HIP(hipMemsetAsync(g_tests, 0, sizeof(unsigned long long), stream));
+        a.tests = g_tests;
+    }
+    if (ts.timing) {
+        if (!ts.ev0) { GRACE_TRY_HIP(hipEventCreate(&ts.ev0)); GRACE_TRY_HIP(hipEventCreate(&ts.ev1)); }
+        GRACE_TRY_HIP(hipEventRecord(ts.ev0, stream));
+    }
+    if (!d_out) {
+        a.counts = d_counts;
+        GRACE_TRY(launch_walk(a, ts.sph_kernel, 0, stream));
+    }
+    for (int g = 0; d_out && g < n_channels; g += IP_CHANNELS) {
+        a.weights = d_weights + g;
+        a.out = d_out + g;
+        a.counts = g == 0 ? d_counts : nullptr;
+        GRACE_TRY(launch_walk(a, ts.sph_kernel, min(IP_CHANNELS, n_channels - g), stream));
+    }
+    if (ts.timing) {
+        GRACE_TRY_HIP(hipEventRecord(ts.ev1, stream));
+        ts.ev_valid = true;
+    }
+    return GRACE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                         const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                         size_t n_nodes, const int* d_leaves, const int* d_root,
+                                         const float* d_weights, int n_channels,
+                                         float* d_out, int* d_counts, grace_stream stream)
+{
+    GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "interpolate: elements per point must be 3..16");
+    GRACE_REQUIRE(n_points < (size_t(1) << 31), "interpolate: too many points");
+    if (n_points == 0) return GRACE_OK;   // (before the output checks: a caller's empty arrays may be null)
+    GRACE_REQUIRE(d_points, "interpolate: null points");
+    InterpArgs a = {};
+    TraceState* ts = nullptr;
+    GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
+                            d_out, d_counts, &ts));
+    const hipStream_t stream_ = as_stream(stream);
+    // Morton cells of ~256 points of a uniform set: 8^L cells, L = the largest level with 8^L <= n / 256
+    int level = 0;
+    while (level < 10 && (size_t(1) << (3 * (level + 1))) * 256 <= n_points) ++level;
+    const int shift = 30 - 3 * level;
+    const size_t max_packets = (n_points + 63) / 64 + (size_t(1) << (3 * level));
+    FrameGuard frame;
+    GRACE_TRY(frame.begin(4 * Workspace::aligned(n_points * 4) + Workspace::aligned((max_packets + 1) * 4)
+                          + Workspace::aligned(scan_ws_count(n_points) * 4) + Workspace::aligned(4)
+                          + sort_ws_bytes(n_points, 4, 0), stream_));
+    uint32_t* keys = Workspace::take<uint32_t>(n_points);
+    uint32_t* perm = Workspace::take<uint32_t>(n_points);
+    uint32_t* flags = Workspace::take<uint32_t>(n_points);
+    uint32_t* pos = Workspace::take<uint32_t>(n_points);
+    uint32_t* starts = Workspace::take<uint32_t>(max_packets + 1);
+    uint32_t* scan_ws = Workspace::take<uint32_t>(scan_ws_count(n_points));
+    uint32_t* n_starts = Workspace::take<uint32_t>(1);
+    interp_keys_kernel<<<stream_grid(n_points, 256), 256, 0, stream_>>>(d_points, n_points, elems_per_point,
+                                                                       a.nodes, a.n_nodes, d_root, keys);
+    GRACE_CHECK_LAUNCH();
+    GRACE_TRY(sort_pairs_u32_nested(keys, nullptr, n_points, 0, 0, 30, perm, stream_));
+    interp_flags_kernel<<<stream_grid(n_points, 256), 256, 0, stream_>>>(keys, n_points, shift, flags);
+    GRACE_CHECK_LAUNCH();
+    GRACE_TRY(exclusive_scan_u32(flags, pos, n_points, scan_ws, n_starts, stream_));
+    interp_starts_kernel<<<stream_grid(n_points, 256), 256, 0, stream_>>>(flags, pos, n_points, starts);
+    GRACE_CHECK_LAUNCH();
+    a.points = d_points;
+    a.stride = elems_per_point;
+    a.perm = perm;
+    a.n_points = int(n_points);
+    a.starts = starts;
+    a.n_starts = n_starts;
+    a.n_packets = int(max_packets);
+    return interp_walks(a, *ts, d_weights, n_channels, d_out, d_counts, stream_);
+}
+
+grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                       size_t n_nodes, const int* d_leaves, const int* d_root,
+                                       const float* d_weights, int n_channels,
+                                       float* d_out, int* d_counts, grace_stream stream)
+{
+    GRACE_REQUIRE(h_origin3 && h_uvw9 && h_dims3, "interpolate_grid: null lattice argument");
+    GRACE_REQUIRE(h_dims3[0] > 0 && h_dims3[1] > 0 && h_dims3[2] > 0, "interpolate_grid: dimensions must be positive");
+    const size_t n = size_t(h_dims3[0]) * size_t(h_dims3[1]) * size_t(h_dims3[2]);
+    GRACE_REQUIRE(n < (size_t(1) << 31), "interpolate_grid: too many lattice points");
+    InterpArgs a = {};
+    TraceState* ts = nullptr;
+    GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
+                            d_out, d_counts, &ts));
+    for (int d = 0; d < 3; ++d) {
+        a.org[d] = h_origin3[d];
+        a.eu[d] = h_uvw9[d]; a.ev[d] = h_uvw9[3 + d]; a.ew[d] = h_uvw9[6 + d];
+        a.dims[d] = h_dims3[d];
+    }
+    const bool slice = h_dims3[2] == 1;
+    a.brick[0] = slice ? 8 : 4; a.brick[1] = slice ? 8 : 4; a.brick[2] = slice ? 1 : 4;
+    a.nb[0] = ceil_div(size_t(h_dims3[0]), a.brick[0]);
+    a.nb[1] = ceil_div(size_t(h_dims3[1]), a.brick[1]);
+    const size_t packets = size_t(a.nb[0]) * a.nb[1] * size_t(ceil_div(size_t(h_dims3[2]), a.brick[2]));
+    GRACE_REQUIRE(packets < (size_t(1) << 31) / 64, "interpolate_grid: too many lattice points");
+    a.n_packets = int(packets);
+    return interp_walks(a, *ts, d_weights, n_channels, d_out, d_counts, as_stream(stream));
+}
+
+grace_status grace_interpolate_enable_stats(int enabled)
+{
+    if (enabled && !g_tests)
+        GRACE_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&g_tests), sizeof(unsigned long long)));
+    g_stats = enabled != 0;
+    return GRACE_OK;
+}
+
+grace_status grace_interpolate_last_stats(unsigned long long* h_survivor_tests)
+{
+    GRACE_REQUIRE(h_survivor_tests, "interpolate_last_stats: null output");
+    GRACE_REQUIRE(g_stats && g_tests, "interpolate_last_stats: statistics are not enabled");
+    GRACE_TRY_HIP(hipDeviceSynchronize());
+    GRACE_TRY_HIP(hipMemcpy(h_survivor_tests, g_tests, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return GRACE_OK;
+}
+
+} // extern "C"

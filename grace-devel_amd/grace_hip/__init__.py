@@ -555,6 +555,94 @@ def trace_cumulative_weighted_sph(rays, spheres, tree, weights, out=None, check=
     return out
 
 
+def _interp_outputs(n_points, n_spheres, weights, out, counts, device):
+    """Checks weights / out / counts of an interpolation call and allocates what is missing."""
+    if weights is None:
+        if out is not None:
+            raise ValueError("out needs weights")
+        if counts is None:
+            counts = torch.empty(n_points, dtype=torch.int32, device=device)
+        n_ch, shape = 0, None
+    else:
+        if weights.dtype != torch.float32:
+            raise ValueError("weights must be float32")
+        if weights.dim() not in (1, 2) or weights.shape[0] != n_spheres:
+            raise ValueError("weights must have shape [n_spheres] or [n_spheres, C]")
+        n_ch = 1 if weights.dim() == 1 else weights.shape[1]
+        if not 1 <= n_ch <= 64:
+            raise ValueError("weights must have 1..64 channels")
+        shape = (n_points,) if weights.dim() == 1 else (n_points, n_ch)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=device)
+        if out.dtype != torch.float32 or tuple(out.shape) != shape:
+            raise ValueError("out must be float32 of shape %s" % (shape,))
+    if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (n_points,)):
+        raise ValueError("counts must be int32 of shape [%d]" % n_points)
+    return n_ch, out, counts
+
+
+def _interp_scene(spheres, tree):
+    return (_ptr(_spheres(spheres)), C.c_size_t(len(spheres)), _ptr(tree.nodes), C.c_size_t(tree.n_nodes),
+            _ptr(tree.leaves), _ptr(tree.root_index))
+
+
+def interpolate_sph(points, spheres, tree, weights=None, out=None, counts=None, check=False):
+    """The SPH field at points (an extension the reference lacks):
+    out[p, c] = sum over spheres i containing point p of fl32(weights[i, c] * W(|p - x_i|, H_i)), with
+    the context's SPH kernel (set_sph_kernel; a custom table is refused), summed per channel in the
+    class order of the column densities; counts[p] = the number of spheres containing p.
+    points: float32 [n, 3..16] (x y z first); weights: float32 [n_spheres] or [n_spheres, C]
+    (1 <= C <= 64) in the order of `spheres` (tree order: build_tree(want_perm=True)), or None for
+    counts only.  Returns out (None without weights) and counts (allocated when weights is None or
+    counts is given)."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    n_ch, out, counts = _interp_outputs(len(points), len(spheres), weights, out, counts, points.device)
+    _check(_lib.grace_interpolate_points_f4(_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
+                                            *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
+                                            _ptr(out), _ptr(counts), _stream()))
+    if check:
+        trace_status()
+    return out, counts
+
+
+def interpolate_grid_sph(origin, u, v, w, dims, spheres, tree, weights=None, out=None, counts=None,
+                         check=False):
+    """interpolate_sph over the lattice p(i, j, k) = origin + i u + j v + k w (fp32, per component
+    fl(fl(fl(o + fl(i u)) + fl(j v)) + fl(k w))), dims = (nx, ny, nz); nz = 1 is a slice (oblique
+    ones too).  out: float32 [nz, ny, nx] or [nz, ny, nx, C]; counts: int32 [nz, ny, nx]."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) <= 0:
+        raise ValueError("grid dimensions must be positive")
+    n = nx * ny * nz
+    dev = spheres.device
+    flat_out = None if out is None else out.view(n, *out.shape[3:])
+    flat_counts = None if counts is None else counts.view(n)
+    n_ch, flat_out, flat_counts = _interp_outputs(n, len(spheres), weights, flat_out, flat_counts, dev)
+    o3 = (C.c_float * 3)(*[float(x) for x in origin])
+    uvw = (C.c_float * 9)(*[float(x) for x in (*u, *v, *w)])
+    d3 = (C.c_int * 3)(nx, ny, nz)
+    _check(_lib.grace_interpolate_grid_f4(o3, uvw, d3, *_interp_scene(spheres, tree), _ptr(weights),
+                                          C.c_int(n_ch), _ptr(flat_out), _ptr(flat_counts), _stream()))
+    if check:
+        trace_status()
+    grid = lambda t: None if t is None else t.view(nz, ny, nx, *t.shape[1:])
+    return grid(flat_out), grid(flat_counts)
+
+
+def interpolate_enable_stats(enabled=True):
+    """Measurement hook: count survivor tests of every interpolation call (process-wide)."""
+    _check(_lib.grace_interpolate_enable_stats(C.c_int(1 if enabled else 0)))
+
+
+def interpolate_last_stats():
+    """Survivor tests (active lanes x survivors) of the last interpolation call; synchronises."""
+    v = C.c_ulonglong(0)
+    _check(_lib.grace_interpolate_last_stats(C.byref(v)))
+    return v.value
+
+
 INT32_MAX = 2 ** 31 - 1
 
 

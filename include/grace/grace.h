@@ -687,6 +687,65 @@ inline void trace_cumulative_weighted_sph(const device_vector<Ray>& d_rays,
     detail::check(grace_trace_status(nullptr));
 }
 
+// Extension (the reference has no such call): the SPH field at points and on lattices
+// (grace_interpolate_points_f4 / _grid_f4, grace_hip.h): d_out[p * n_channels + c] = sum over spheres i
+// containing point p of fl(d_weights[i * n_channels + c] W_ip), spheres in tree order, the context's
+// SPH kernel; d_counts[p] = the number of spheres containing p.  Points are 3..16 floats, x y z first.
+namespace detail {
+template <typename PointType, typename Real4>
+inline void interp_check(const device_vector<Real4>& d_spheres, const device_vector<float>& d_weights,
+                         int n_channels, size_t n_points, size_t n_out)
+{
+    static_assert(std::is_same<Real4, float4>::value, "interpolate_sph: float4 spheres only (float weights and outputs)");
+    static_assert(sizeof(PointType) % sizeof(float) == 0 && sizeof(PointType) >= 3 * sizeof(float)
+                      && sizeof(PointType) <= 16 * sizeof(float),
+                  "interpolate_sph: points are 3..16 floats, x y z first");
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("interpolate_sph: n_channels must be 1..64");
+    if (d_weights.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("interpolate_sph: d_weights must hold n_channels per sphere");
+    if (n_out != n_points * size_t(n_channels))
+        throw std::invalid_argument("interpolate_sph: d_out must hold n_channels per point");
+}
+} // namespace detail
+
+template <typename PointType, typename Real4>
+inline void interpolate_sph(const device_vector<PointType>& d_points, const device_vector<Real4>& d_spheres,
+                            const Tree& d_tree, const device_vector<float>& d_weights, int n_channels,
+                            device_vector<float>& d_out, device_vector<int>* d_counts = nullptr)
+{
+    detail::interp_check<PointType>(d_spheres, d_weights, n_channels, d_points.size(), d_out.size());
+    if (d_counts && d_counts->size() != d_points.size())
+        throw std::invalid_argument("interpolate_sph: d_counts must hold one count per point");
+    detail::check(grace_interpolate_points_f4(reinterpret_cast<const float*>(d_points.data()), d_points.size(),
+                                              int(sizeof(PointType) / sizeof(float)), &d_spheres.data()->x,
+                                              d_spheres.size(), &d_tree.nodes.data()->x, d_tree.leaves.size() - 1,
+                                              &d_tree.leaves.data()->x, d_tree.root_index_ptr, d_weights.data(),
+                                              n_channels, d_out.data(), d_counts ? d_counts->data() : nullptr,
+                                              nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
+template <typename Real4>
+inline void interpolate_grid_sph(const float3 origin, const float3 u, const float3 v, const float3 w,
+                                 const int nx, const int ny, const int nz, const device_vector<Real4>& d_spheres,
+                                 const Tree& d_tree, const device_vector<float>& d_weights, int n_channels,
+                                 device_vector<float>& d_out)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        throw std::invalid_argument("interpolate_grid_sph: dimensions must be positive");
+    detail::interp_check<float3>(d_spheres, d_weights, n_channels, size_t(nx) * size_t(ny) * size_t(nz),
+                                 d_out.size());
+    const float o3[3] = { origin.x, origin.y, origin.z };
+    const float uvw[9] = { u.x, u.y, u.z, v.x, v.y, v.z, w.x, w.y, w.z };
+    const int d3[3] = { nx, ny, nz };
+    detail::check(grace_interpolate_grid_f4(o3, uvw, d3, &d_spheres.data()->x, d_spheres.size(),
+                                            &d_tree.nodes.data()->x, d_tree.leaves.size() - 1,
+                                            &d_tree.leaves.data()->x, d_tree.root_index_ptr, d_weights.data(),
+                                            n_channels, d_out.data(), nullptr, nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
 inline void trace_sph(const device_vector<Ray>& d_rays, const device_vector<float4>& d_spheres,
                       const Tree& d_tree, device_vector<int>& d_ray_offsets,
                       device_vector<int>& d_hit_indices, device_vector<double>& d_hit_integrals,

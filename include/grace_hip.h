@@ -608,6 +608,65 @@ grace_status grace_trace_hits_f4_f64(const void* d_rays, size_t n_rays, const fl
                                      int* d_hit_indices, double* d_hit_integrals,
                                      double* d_hit_distances, grace_stream stream);
 
+/* ---- SPH interpolation at points (an extension the reference lacks) -----------------------------
+ * The SPH field of the spheres (tree order, as traced) at points, with the context's SPH kernel
+ * (grace_trace_set_sph_kernel; a sphere's w is the support radius H, W(r, H) = H^-3 f(r / H)):
+ *   d_out[p * n_channels + c] = sum over spheres i containing point p of fl32(d_weights[i * n_channels + c] * W_ip)
+ *   d_counts[p]               = number of spheres i containing point p
+ * Weights in tree order as for grace_trace_cumulative_weighted_f4 (weights = m gives the density,
+ * m / rho * A the field A); read on every call, never cached.  Containment is d2 < fl(H * H),
+ * strict: a point on a sphere's surface is not contained; NaN points and points outside every
+ * sphere get 0 and a count of 0.
+ *
+ * Arithmetic (fp32, every operation rounded, none fused), per point p and sphere {x, H}:
+ *   d = p - x per component;  d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz));
+ *   ih = fl(1 / H);  q = fl(sqrt_rn(d2) * ih);  u = max(fl(1 - q), 0);
+ *   K = f(q), below;  W = fl(K * fl(fl(ih * ih) * ih));  term_c = fl(w_c * W).
+ * f(q) with p4(t) = fl(fl(t*t) * fl(t*t)), constants rounded to fp32, the normalisation last:
+ *   cubic (M4, support H):  q < 0.5 ? fl(fl(fl(fl(6q) - 6) * fl(q*q)) + 1) : fl(2 * fl(fl(u*u) * u)),  times 8/pi
+ *   quartic:  t2 = max(fl(u - 0.4), 0), t3 = max(fl(u - 0.8), 0);
+ *             fl(fl(p4(u) - fl(5 p4(t2))) + fl(10 p4(t3))),  times 25 2.5^4 / (32 pi)
+ *   quintic:  t2 = max(fl(u - 1/3), 0), t3 = max(fl(u - 2/3), 0), p5(t) = fl(p4(t) * t);
+ *             fl(fl(p5(u) - fl(6 p5(t2))) + fl(15 p5(t3))),  times 9 3^5 / (40 pi)
+ *   Wendland C2:  fl(p4(u) * fl(fl(4q) + 1)),  times 21 / (2 pi)
+ *   Wendland C4:  fl(fl(p4(u) * fl(u*u)) * fl(fl(q * fl(fl(q * 35/3) + 6)) + 1)),  times 495 / (32 pi)
+ *   Wendland C6:  fl(fl(p4(u) * p4(u)) * fl(fl(q * fl(fl(q * fl(fl(32q) + 25)) + 8)) + 1)),  times 1365 / (64 pi)
+ * (the functions of tools/gen_kernel_tables.py, written in u = 1 - q).  Each channel is summed in
+ * the class order of the column densities: class (i >> 10) & 7, fp32 sums in ascending index within
+ * each class, the 8 class sums added pairwise ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)).  The result is a
+ * function of the point and the scene only: not of the point order, elems_per_point, the entry
+ * point, the trace's cache knobs.
+ *
+ * Points: n_points records of elems_per_point (3..16) floats, x y z first (the layout of
+ * grace_morton_keys30_points); outputs in the caller's order (the call orders points internally by
+ * Morton keys against the tree's root box, computed and sorted on the device).
+ * Grid: the lattice p(i, j, k) = origin + i u + j v + k w, per component
+ * fl(fl(fl(o + fl(i*u)) + fl(j*v)) + fl(k*w)), 0 <= i < dims[0] ..., outputs row-major (k slowest,
+ * i fastest); dims[2] == 1 is a slice (oblique slices allowed).  h_uvw9 = {u, v, w}.
+ *
+ * Either output may be NULL, not both; d_out needs non-NULL weights and 1 <= n_channels <= 64
+ * (channels are walked four at a time).  GRACE_INVALID_ARGUMENT, nothing written: bad
+ * elems_per_point, channel count, dimension or scene, or a custom SPH kernel table (there is no
+ * f(q)).  Zero points: GRACE_OK, nothing written.  A packet that exhausts its 128-entry stack sets
+ * the status word of grace_trace_status (GRACE_STACK_OVERFLOW); nothing is written out of bounds.
+ * Stream-ordered, no host synchronisation, no allocation (the context workspace): capturable. */
+grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                         const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                         size_t n_nodes, const int* d_leaves, const int* d_root,
+                                         const float* d_weights, int n_channels,
+                                         float* d_out, int* d_counts, grace_stream stream);
+grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                       size_t n_nodes, const int* d_leaves, const int* d_root,
+                                       const float* d_weights, int n_channels,
+                                       float* d_out, int* d_counts, grace_stream stream);
+/* Measurement hook (process-wide, results never depend on it): when enabled, every interpolation
+ * call counts its survivor tests (active lanes x survivors of each culling round, all walks);
+ * grace_interpolate_last_stats synchronises the device and returns the last call's count.
+ * grace_trace_enable_timing / grace_trace_last_kernel_ms also time the interpolation walks. */
+grace_status grace_interpolate_enable_stats(int enabled);
+grace_status grace_interpolate_last_stats(unsigned long long* h_survivor_tests);
+
 #ifdef __cplusplus
 }
 #endif
