@@ -28,10 +28,7 @@
 // Containment d2 < fl(H^2) with d2 formed in fp32 is never true for a point outside the exact box
 // [x - H, x + H] of a sphere (|dx| >= H there, and every fp32 step is monotonic), so the widened
 // box tests drop no contained sphere: results are a function of the point and the scene only.
-#include "common.hpp"
-#include "trace_state.hpp"
-
-#include "grace/generic/morton.h"
+#include "point_packets.hpp"
 
 using namespace grace_hip;
 
@@ -71,26 +68,6 @@ struct InterpArgs {
     unsigned long long* tests;   // measurement hook: survivor tests (lanes x survivors), or null
 };
 
-// Correctly rounded sqrt for x = 0 or x >= 2^-96 (finite): v_sqrt_f32 is within 1 ulp, the two FMA
-// residuals pick the neighbour if it is closer (the trace's sqrt_rn_normal).
-__device__ __forceinline__ float sqrt_rn_normal(const float x)
-{
-    const float y = __builtin_amdgcn_sqrtf(x);
-    const float ym = __int_as_float(__float_as_int(y) - 1);
-    const float yp = __int_as_float(__float_as_int(y) + 1);
-    const float rm = __builtin_fmaf(-ym, y, x);
-    const float rp = __builtin_fmaf(-yp, y, x);
-    float r = (0.0f >= rm) ? ym : y;
-    r = (0.0f < rp) ? yp : r;
-    return r;
-}
-
-__device__ __forceinline__ float sqrt_rn(const float x)
-{
-    const bool tiny = x < 1.2621774e-29f && x > 0.0f;   // 2^-96: the general expansion (practically never)
-    return __builtin_amdgcn_ballot_w64(tiny) ? __builtin_sqrtf(x) : sqrt_rn_normal(x);
-}
-
 __device__ __forceinline__ float pow4(const float t)
 {
     const float t2 = t * t;
@@ -126,32 +103,10 @@ __device__ __forceinline__ float kernel_f(const float q)
     }
 }
 
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
 // [lo, hi] widened by 2^-20 of each bound overlaps the packet box (NaN: no).
 __device__ __forceinline__ bool overlaps(const float lo, const float hi, const float plo, const float phi)
 {
     return lo - fabsf(lo) * IP_SLACK <= phi && hi + fabsf(hi) * IP_SLACK >= plo;
-}
-
-// Orders LDS stores of some lanes before loads of others within the wave.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // NW = channels of this walk (0: counts only).
@@ -310,64 +265,9 @@ __global__ __launch_bounds__(IP_BLOCK) void interpolate_kernel(const InterpArgs 
     }
 }
 
-// 30-bit Morton keys of the points against the tree's root box (read here: no host round trip);
-// points are clamped into the box (NaN: to its lower corner).
-__global__ __launch_bounds__(256) void interp_keys_kernel(const float* __restrict__ pts, size_t n, int stride,
-                                                          const float4* __restrict__ nodes, int n_nodes,
-                                                          const int* __restrict__ root, uint32_t* __restrict__ keys)
-{
-    const int r = *root;
-    float lo[3] = { 0.f, 0.f, 0.f }, hi[3] = { 0.f, 0.f, 0.f };
-    if (r >= 0 && r < n_nodes) {
-        const float4 L = nodes[4 * size_t(r) + 1], R = nodes[4 * size_t(r) + 2], Z = nodes[4 * size_t(r) + 3];
-        lo[0] = fminf(L.x, R.x); hi[0] = fmaxf(L.y, R.y);
-        lo[1] = fminf(L.z, R.z); hi[1] = fmaxf(L.w, R.w);
-        lo[2] = fminf(Z.x, Z.z); hi[2] = fmaxf(Z.y, Z.w);
-    }
-    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
-        uint32_t c[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float v = fminf(fmaxf(pts[i * size_t(stride) + d], lo[d]), hi[d]);
-            const float ext = hi[d] - lo[d];
-            const float t = ext > 0.0f ? (v - lo[d]) / ext : 0.0f;
-            c[d] = min(uint32_t(fmaxf(t, 0.0f) * 1023.0f), 1023u);
-        }
-        keys[i] = grace::morton_key(c[0], c[1], c[2]);
-    }
-}
-
-// Packet starts of the sorted points: every 64th point and every change of the Morton cell
-// (key >> shift).  flags -> (scan) -> positions; the last thread also writes the end sentinel.
-__global__ __launch_bounds__(256) void interp_flags_kernel(const uint32_t* __restrict__ keys, size_t n, int shift,
-                                                           uint32_t* __restrict__ flags)
-{
-    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
-        flags[i] = (i % 64 == 0 || (keys[i] >> shift) != (keys[i - 1] >> shift)) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(256) void interp_starts_kernel(const uint32_t* __restrict__ flags,
-                                                            const uint32_t* __restrict__ pos, size_t n,
-                                                            uint32_t* __restrict__ starts)
-{
-    for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
-        if (flags[i]) starts[pos[i]] = uint32_t(i);
-        if (i == n - 1) starts[pos[i] + flags[i]] = uint32_t(n);
-    }
-}
-
 // Process-wide measurement hook (grace_interpolate_enable_stats): a device counter of survivor tests.
 unsigned long long* g_tests = nullptr;
 bool g_stats = false;
-
-grace_status ensure_status(TraceState& ts, hipStream_t stream)
-{
-    if (!ts.status) {
-        GRACE_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&ts.status), sizeof(int)));
-        GRACE_TRY_HIP(hipMemsetAsync(ts.status, 0, sizeof(int), stream));
-    }
-    return GRACE_OK;
-}
 
 template <int KIND>
 grace_status launch_kind(const InterpArgs& a, int nw, hipStream_t stream)
@@ -479,38 +379,16 @@ grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points,
     GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
                             d_out, d_counts, &ts));
     const hipStream_t stream_ = as_stream(stream);
-    // Morton cells of ~256 points of a uniform set: 8^L cells, L = the largest level with 8^L <= n / 256
-    int level = 0;
-    while (level < 10 && (size_t(1) << (3 * (level + 1))) * 256 <= n_points) ++level;
-    const int shift = 30 - 3 * level;
-    const size_t max_packets = (n_points + 63) / 64 + (size_t(1) << (3 * level));
     FrameGuard frame;
-    GRACE_TRY(frame.begin(4 * Workspace::aligned(n_points * 4) + Workspace::aligned((max_packets + 1) * 4)
-                          + Workspace::aligned(scan_ws_count(n_points) * 4) + Workspace::aligned(4)
-                          + sort_ws_bytes(n_points, 4, 0), stream_));
-    uint32_t* keys = Workspace::take<uint32_t>(n_points);
-    uint32_t* perm = Workspace::take<uint32_t>(n_points);
-    uint32_t* flags = Workspace::take<uint32_t>(n_points);
-    uint32_t* pos = Workspace::take<uint32_t>(n_points);
-    uint32_t* starts = Workspace::take<uint32_t>(max_packets + 1);
-    uint32_t* scan_ws = Workspace::take<uint32_t>(scan_ws_count(n_points));
-    uint32_t* n_starts = Workspace::take<uint32_t>(1);
-    interp_keys_kernel<<<stream_grid(n_points, 256), 256, 0, stream_>>>(d_points, n_points, elems_per_point,
-                                                                       a.nodes, a.n_nodes, d_root, keys);
-    GRACE_CHECK_LAUNCH();
-    GRACE_TRY(sort_pairs_u32_nested(keys, nullptr, n_points, 0, 0, 30, perm, stream_));
-    interp_flags_kernel<<<stream_grid(n_points, 256), 256, 0, stream_>>>(keys, n_points, shift, flags);
-    GRACE_CHECK_LAUNCH();
-    GRACE_TRY(exclusive_scan_u32(flags, pos, n_points, scan_ws, n_starts, stream_));
-    interp_starts_kernel<<<stream_grid(n_points, 256), 256, 0, stream_>>>(flags, pos, n_points, starts);
-    GRACE_CHECK_LAUNCH();
+    PointPackets pk;
+    GRACE_TRY(point_packets(frame, d_points, n_points, elems_per_point, a.nodes, a.n_nodes, d_root, stream_, pk));
     a.points = d_points;
     a.stride = elems_per_point;
-    a.perm = perm;
+    a.perm = pk.perm;
     a.n_points = int(n_points);
-    a.starts = starts;
-    a.n_starts = n_starts;
-    a.n_packets = int(max_packets);
+    a.starts = pk.starts;
+    a.n_starts = pk.n_starts;
+    a.n_packets = int(pk.max_packets);
     return interp_walks(a, *ts, d_weights, n_channels, d_out, d_counts, stream_);
 }
 

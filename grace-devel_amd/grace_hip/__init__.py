@@ -643,6 +643,65 @@ def interpolate_last_stats():
     return v.value
 
 
+def nearest_neighbours_sph(points, spheres, tree, k, indices=None, d2=None, check=False):
+    """The k nearest sphere centres of each point (an extension the reference lacks): spheres are
+    ranked by (d2, tree index), d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in fp32; row p holds
+    the first k.  Slots beyond the number of spheres, and every slot of a point with a non-finite
+    coordinate, are -1 / +inf.  points: float32 [n, 3..16] (x y z first); 1 <= k <= 64.
+    Returns (indices int32 [n, k], d2 float32 [n, k])."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    k = int(k)
+    if not 1 <= k <= 64:
+        raise ValueError("k must be 1..64")
+    points = points.contiguous()
+    shape = (len(points), k)
+    if indices is None:
+        indices = torch.empty(shape, dtype=torch.int32, device=points.device)
+    if d2 is None:
+        d2 = torch.empty(shape, dtype=torch.float32, device=points.device)
+    if indices.dtype != torch.int32 or tuple(indices.shape) != shape:
+        raise ValueError("indices must be int32 of shape %s" % (shape,))
+    if d2.dtype != torch.float32 or tuple(d2.shape) != shape:
+        raise ValueError("d2 must be float32 of shape %s" % (shape,))
+    _check(_lib.grace_nearest_neighbours_f4(_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
+                                            *_interp_scene(spheres, tree), C.c_int(k), _ptr(indices), _ptr(d2),
+                                            _stream()))
+    if check:
+        trace_status()
+    return indices, d2
+
+
+def smoothing_lengths_sph(spheres, tree, k, eta=1.0, out=None, check=False):
+    """Smoothing lengths from the k-th nearest neighbour: h[i] = fl(eta * sqrt(D_i)), D_i the d2 of
+    slot k-1 of nearest_neighbours_sph at sphere i's own centre (it is its own first neighbour).
+    Returns h float32 [n] in tree order (the order of `spheres`, which is only read); to use it as
+    H, write it into spheres[:, 3] and build the tree again.  1 <= k <= min(64, n); eta > 0."""
+    n = len(spheres)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=spheres.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n,):
+        raise ValueError("out must be float32 of shape [%d]" % n)
+    _check(_lib.grace_smoothing_lengths_f4(*_interp_scene(spheres, tree), C.c_int(int(k)), C.c_float(float(eta)),
+                                           _ptr(out), _stream()))
+    if check:
+        trace_status()
+    return out
+
+
+def neighbours_enable_stats(enabled=True):
+    """Measurement hook: count candidate tests and packets of every neighbour call (process-wide)."""
+    _check(_lib.grace_neighbours_enable_stats(C.c_int(1 if enabled else 0)))
+
+
+def neighbours_last_stats():
+    """(candidate tests (active lanes x survivors), packets, insertion steps (survivors for which some
+    lane of the packet inserted)) of the last neighbour call; synchronises."""
+    t = C.c_ulonglong(0); p = C.c_ulonglong(0); s = C.c_ulonglong(0)
+    _check(_lib.grace_neighbours_last_stats(C.byref(t), C.byref(p), C.byref(s)))
+    return t.value, p.value, s.value
+
+
 INT32_MAX = 2 ** 31 - 1
 
 

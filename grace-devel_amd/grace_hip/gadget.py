@@ -1,7 +1,8 @@
 """Gadget-2 (format 1) snapshot I/O for the SPH fields GRACE uses: gas positions and
-smoothing lengths.  Block layout as read by the reference's tests/helper/read_gadget.cuh:
-header of 256 B (npart[6] int32, mass[6] float64, padding) and POS, VEL, ID, [MASS], U, RHO,
-HSML blocks, every block framed by 4-byte markers.  Host-side file I/O only (numpy)."""
+smoothing lengths, and positions and masses of any particle type (read_gadget_particles).
+Block layout as read by the reference's tests/helper/read_gadget.cuh: header of 256 B
+(npart[6] int32, mass[6] float64, padding) and POS, VEL, ID, [MASS], U, RHO, HSML blocks,
+every block framed by 4-byte markers.  Host-side file I/O only (numpy)."""
 import numpy as np
 
 
@@ -61,3 +62,39 @@ def read_gadget(fname):
     out[:, :3] = p
     out[:, 3] = h
     return out
+
+
+def read_gadget_particles(fname, ptype):
+    """Returns (positions [N, 3], masses [N]), both float32, of the particles of type ptype (0..5) --
+    any type, with or without HSML.  POS holds every type in type order; a type's masses come from
+    the header, or from the MASS block when its header mass is 0 (the block holds those types only,
+    in type order)."""
+    if not 0 <= int(ptype) <= 5:
+        raise ValueError("ptype must be 0..5")
+    ptype = int(ptype)
+    with open(fname, "rb") as f:
+        raw = np.frombuffer(f.read(), np.uint8)
+    pos = 0
+
+    def take_block():
+        nonlocal pos
+        nbytes = int(raw[pos:pos + 4].view(np.int32)[0])
+        data = raw[pos + 4: pos + 4 + nbytes]
+        pos += 8 + nbytes
+        return data
+
+    header = take_block()
+    npart = [int(x) for x in header[:24].view(np.int32)]
+    mass = header[24:72].view(np.float64)
+    first = sum(npart[:ptype])
+    n = npart[ptype]
+    if n == 0:
+        return np.empty((0, 3), np.float32), np.empty(0, np.float32)
+    p = take_block().view(np.float32).reshape(-1, 3)[first:first + n].copy()
+    if mass[ptype] != 0:
+        return p, np.full(n, mass[ptype], np.float32)
+    take_block()                 # VEL
+    take_block()                 # ID
+    m_first = sum(npart[t] for t in range(ptype) if mass[t] == 0)
+    m = take_block().view(np.float32)[m_first:m_first + n].copy()
+    return p, m

@@ -746,6 +746,43 @@ inline void interpolate_grid_sph(const float3 origin, const float3 u, const floa
     detail::check(grace_trace_status(nullptr));
 }
 
+// Extension (the reference has no such call): k nearest neighbours and smoothing lengths
+// (grace_nearest_neighbours_f4 / grace_smoothing_lengths_f4, grace_hip.h): spheres ranked by
+// (d2, tree index) in fp32; d_h[i] = fl(eta sqrt(d2 of the k-th neighbour of sphere i's centre)).
+template <typename PointType, typename Real4>
+inline void nearest_neighbours_sph(const device_vector<PointType>& d_points, const device_vector<Real4>& d_spheres,
+                                   const Tree& d_tree, int k, device_vector<int>& d_indices,
+                                   device_vector<float>& d_d2)
+{
+    static_assert(std::is_same<Real4, float4>::value, "nearest_neighbours_sph: float4 spheres only");
+    static_assert(sizeof(PointType) % sizeof(float) == 0 && sizeof(PointType) >= 3 * sizeof(float)
+                      && sizeof(PointType) <= 16 * sizeof(float),
+                  "nearest_neighbours_sph: points are 3..16 floats, x y z first");
+    if (k < 1 || k > 64)
+        throw std::invalid_argument("nearest_neighbours_sph: k must be 1..64");
+    if (d_indices.size() != d_points.size() * size_t(k) || d_d2.size() != d_points.size() * size_t(k))
+        throw std::invalid_argument("nearest_neighbours_sph: d_indices and d_d2 must hold k entries per point");
+    detail::check(grace_nearest_neighbours_f4(reinterpret_cast<const float*>(d_points.data()), d_points.size(),
+                                              int(sizeof(PointType) / sizeof(float)), &d_spheres.data()->x,
+                                              d_spheres.size(), &d_tree.nodes.data()->x, d_tree.leaves.size() - 1,
+                                              &d_tree.leaves.data()->x, d_tree.root_index_ptr, k, d_indices.data(),
+                                              d_d2.data(), nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
+template <typename Real4>
+inline void smoothing_lengths_sph(const device_vector<Real4>& d_spheres, const Tree& d_tree, int k, float eta,
+                                  device_vector<float>& d_h)
+{
+    static_assert(std::is_same<Real4, float4>::value, "smoothing_lengths_sph: float4 spheres only");
+    if (d_h.size() != d_spheres.size())
+        throw std::invalid_argument("smoothing_lengths_sph: d_h must hold one value per sphere");
+    detail::check(grace_smoothing_lengths_f4(&d_spheres.data()->x, d_spheres.size(), &d_tree.nodes.data()->x,
+                                             d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                             d_tree.root_index_ptr, k, eta, d_h.data(), nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
 inline void trace_sph(const device_vector<Ray>& d_rays, const device_vector<float4>& d_spheres,
                       const Tree& d_tree, device_vector<int>& d_ray_offsets,
                       device_vector<int>& d_hit_indices, device_vector<double>& d_hit_integrals,

@@ -667,6 +667,53 @@ grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uv
 grace_status grace_interpolate_enable_stats(int enabled);
 grace_status grace_interpolate_last_stats(unsigned long long* h_survivor_tests);
 
+/* ---- Nearest neighbours and smoothing lengths (an extension the reference lacks) ---------------
+ * The k nearest sphere centres of each point, and smoothing lengths from the k-th neighbour of
+ * every particle (for particles without H: dark matter, stars).
+ *
+ * Distance (fp32, every operation rounded, none fused), per point p and sphere j (centre x_j; its w
+ * is ignored):  d = p - x per component;  d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz))
+ * (the interpolation's sequence).
+ * Order: spheres are ranked by the pair (d2, j), smallest d2 first, the lower tree index first on
+ * equal d2.  Row p holds the first k of that ranking: d_indices[p * k + s] is the tree index and
+ * d_d2[p * k + s] its d2, s = 0 .. k-1.  The result is defined exactly, ties included, and is a
+ * function of the point and the scene only: not of the point order, elems_per_point, the spheres'
+ * w or the H the tree was built with (any H >= 0), max_per_leaf, the SPH kernel or the trace's
+ * cache knobs.
+ * Padding: slots s >= n_spheres get index -1 and d2 = +inf.  A point with a non-finite coordinate
+ * gets -1 and +inf in every slot.
+ * Points: n_points records of elems_per_point (3..16) floats, x y z first, as for
+ * grace_interpolate_points_f4; outputs in the caller's order.
+ *
+ * Smoothing lengths: the query points are the sphere centres themselves, so each particle is its
+ * own neighbour at d2 = 0; d_h[i] = fl(eta * sqrt_rn(D_i)), D_i the d2 of slot k-1 of particle i's
+ * row, written in tree order to a separate array (d_spheres is only read).  k > n_spheres is
+ * refused.  More than k-1 other particles at a particle's position give h = 0.
+ *
+ * Arguments: 1 <= k <= 64; eta finite and positive; either of d_indices and d_d2 may be NULL, not
+ * both.  GRACE_INVALID_ARGUMENT, nothing written: a bad argument or scene, including
+ * n_spheres == 0 (there is no tree over zero spheres).  Zero points: GRACE_OK, nothing written
+ * (k, elems_per_point and n_points are checked first, the rest after).  The tree's leaves must
+ * cover exactly [0, n_spheres), as build_tree and build_ALBVH give; node boxes built with any H >= 0 contain the centres.  A packet that exhausts
+ * its 128-entry stack sets the status word of grace_trace_status (GRACE_STACK_OVERFLOW); nothing is
+ * written out of bounds.  Stream-ordered, no host synchronisation, no allocation (the context
+ * workspace): capturable.  grace_trace_enable_timing / grace_trace_last_kernel_ms time the walk. */
+grace_status grace_nearest_neighbours_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                         const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                         size_t n_nodes, const int* d_leaves, const int* d_root,
+                                         int k, int* d_indices, float* d_d2, grace_stream stream);
+grace_status grace_smoothing_lengths_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                        size_t n_nodes, const int* d_leaves, const int* d_root,
+                                        int k, float eta, float* d_h, grace_stream stream);
+/* Measurement hook (process-wide, results never depend on it): when enabled, every call of the two
+ * above counts its candidate tests (active lanes x survivors of each culling round, summed over
+ * packets), its packets, and its insertion steps (survivors for which at least one lane of the
+ * packet inserted into its list, summed over packets); grace_neighbours_last_stats synchronises
+ * the device and returns the last call's. */
+grace_status grace_neighbours_enable_stats(int enabled);
+grace_status grace_neighbours_last_stats(unsigned long long* h_candidate_tests, unsigned long long* h_packets,
+                                         unsigned long long* h_insertion_steps);
+
 #ifdef __cplusplus
 }
 #endif
