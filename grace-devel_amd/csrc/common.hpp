@@ -117,6 +117,15 @@ public:
     static grace_status begin(size_t bytes, hipStream_t stream);
     static void end(hipStream_t stream);
     static Context* frame_context();    // the context of the calling thread's open frame
+    // For an entry point that makes nested traces inside its own frame (ordered.hip): the bytes
+    // left in the open frame; the bump pointer, to take a batch's buffers and give them back; and
+    // growing the open frame to `bytes` in all, what it holds so far copied over (its address
+    // changes: take() pointers are re-derived from base()).
+    static size_t room();
+    static size_t mark();
+    static void rewind(size_t mark);
+    static char* base();
+    static grace_status grow_frame(size_t bytes, hipStream_t stream);
 };
 
 // Scope of one call's workspace frame: begin() makes `bytes` available on the calling thread's
@@ -171,6 +180,17 @@ grace_status sort_pairs_u32_nested(uint32_t* d_keys, void* d_values, size_t n, i
 grace_status sort_pairs_u64_nested(uint64_t* d_keys, void* d_values, size_t n, int value_bytes,
                                    int begin_bit, int end_bit, uint32_t* d_perm,
                                    hipStream_t stream);
+
+// Traces made inside the caller's open frame (trace.hip, `Nested`): the frame bytes such a call
+// on n_rays needs at most, hit counts, and the per-hit outputs at caller-made offsets.
+grace_status trace_nested_bytes(size_t n_rays, size_t n_spheres, size_t n_nodes, size_t* bytes);
+grace_status trace_hitcounts_nested(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                                    const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                                    int* d_hit_counts, hipStream_t stream);
+grace_status trace_hits_nested(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                               const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                               const int* d_ray_offsets, int* d_hit_indices, float* d_hit_integrals,
+                               float* d_hit_distances, hipStream_t stream);
 
 // Drops the prepared trace scene (grace_trace_prepare_*) if it was built over d_written.
 grace_status scene_invalidate_if_written(const void* d_written);

@@ -199,6 +199,32 @@ void Workspace::end(hipStream_t stream)
     }
 }
 
+size_t Workspace::room() { return t_frame ? t_frame->ws_capacity - t_frame->ws_used : 0; }
+size_t Workspace::mark() { return t_frame ? t_frame->ws_used : 0; }
+void Workspace::rewind(size_t mark) { if (t_frame) t_frame->ws_used = mark; }
+char* Workspace::base() { return t_frame ? t_frame->ws_base : nullptr; }
+
+grace_status Workspace::grow_frame(size_t bytes, hipStream_t stream)
+{
+    Context* c = t_frame;
+    GRACE_REQUIRE(c && c->ws_frame_open, "grow_frame: no open frame");
+    if (bytes <= c->ws_capacity) return GRACE_OK;
+    const size_t want = bytes + bytes / 4 + (size_t(1) << 20);
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess)
+        return set_error(GRACE_OUT_OF_MEMORY, __FILE__, __LINE__, hipGetErrorString(e));
+    if (c->ws_used) {
+        e = hipMemcpyAsync(p, c->ws_base, c->ws_used, hipMemcpyDeviceToDevice, stream);
+        if (e != hipSuccess) { (void)hipFree(p); return set_error(GRACE_HIP_ERROR, __FILE__, __LINE__, hipGetErrorString(e)); }
+    }
+    GRACE_TRY_HIP(hipDeviceSynchronize());
+    if (c->ws_base) GRACE_TRY_HIP(hipFree(c->ws_base));
+    c->ws_base = static_cast<char*>(p);
+    c->ws_capacity = want;
+    return GRACE_OK;
+}
+
 grace_status Workspace::release()
 {
     Context* c = nullptr;

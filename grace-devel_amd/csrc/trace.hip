@@ -246,6 +246,11 @@ LaunchPlan plan_launch(const TraceState& ts, const bool keep_requested, const si
     return p;
 }
 
+// A trace made inside another entry point's open workspace frame (the ordered integrals trace
+// their rays batch by batch): it carves from that frame instead of opening one, and leaves the
+// automatic ray cache alone.  measure: only report the frame bytes such a call needs at most.
+struct Nested { bool on = false; size_t* measure = nullptr; };
+
 struct TraceBuffers {   // a call's buffers in its workspace frame (null: not needed)
     unsigned long long* sig = nullptr;   // signature partials (launch_signatures)
     // scene records derived per call (not cached)
@@ -263,7 +268,8 @@ struct TraceBuffers {   // a call's buffers in its workspace frame (null: not ne
 // signatures, the scene pre-pass, the ray order (or, for a cached order, the device-side choices).
 template <int MODE>
 grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGuard& frame, const LaunchPlan& p,
-                         const size_t n_rays, const size_t n_prims, const size_t n_nodes, hipStream_t stream)
+                         const size_t n_rays, const size_t n_prims, const size_t n_nodes, hipStream_t stream,
+                         const Nested nested = Nested())
 {
     // ---- which cached records does this call use?  (see trace_state.hpp) -------------------
     // NONE: derive into the workspace (a scene / batch seen for the first time);  FILL: the
@@ -280,14 +286,16 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
     // The fp64 modes' records (inflated for the fp64 test) are derived per call: the scene cache
     // is neither read nor filled nor counted as seen by them, so float calls on the same arrays
     // cache exactly as they would without them.
-    if (!fp64(MODE) && MODE != MODE_STATS) {
+    if (!fp64(MODE) && MODE != MODE_STATS && !nested.measure) {
         scene_use = decide(ts.scene.valid && ts.scene.key == skey, ts.scene.valid && ts.scene.pinned,
                            ts.scene.seen == skey);
         ts.scene.seen = skey;
         if (scene_use == USE_FILL && scene_cache_alloc(ts, skey) != GRACE_OK) scene_use = USE_NONE;   // (no memory: no cache)
     }
     const RayKey rkey{a.rays, n_rays};
-    if (p.reorder) {
+    // (a nested call traces a sub-range of its caller's rays: the ray cache, which validates by
+    // content and reallocates when the range changes, neither sees nor serves it)
+    if (p.reorder && !nested.on) {
         rays_use = decide(ts.rays.valid && ts.rays.key == rkey, ts.rays.valid && ts.rays.pinned,
                           ts.rays.seen == rkey);
         ts.rays.seen = rkey;
@@ -325,7 +333,13 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
     };
     const size_t own = carve(nullptr);
     // (ray_order's sort carves its temporaries after these)
-    GRACE_TRY(frame.begin(own + (p.reorder ? sort_ws_bytes(n_rays, 4, 0) : 0), stream));
+    const size_t need = own + (p.reorder ? sort_ws_bytes(n_rays, 4, 0) : 0);
+    if (nested.measure) {   // (no cache assumed, room for the signatures a cached call adds)
+        *nested.measure = need + Workspace::aligned(sig_partial_words() * sizeof(*b.sig));
+        return GRACE_OK;
+    }
+    if (nested.on) GRACE_REQUIRE(Workspace::room() >= need, "trace: the caller's frame is too small for a nested trace");
+    else GRACE_TRY(frame.begin(need, stream));
     carve(Workspace::take<char>(own));
     if (sig) {
         SigRequest rq;
@@ -495,7 +509,7 @@ grace_status dispatch(const TraceState& ts, const TraceArgs& a, const TraceBuffe
 
 template <int MODE>
 grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n_nodes,
-                          hipStream_t stream)
+                          hipStream_t stream, const Nested nested = Nested())
 {
     GRACE_REQUIRE(a.rays && a.spheres && a.nodes && a.leaves && a.root, "trace: null pointer");
     GRACE_REQUIRE(n_rays < (size_t(1) << 31), "trace: bad ray count");
@@ -521,7 +535,8 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
     }
     FrameGuard frame;
     TraceBuffers b;
-    GRACE_TRY(use_records<MODE>(ts, a, b, frame, p, n_rays, n_spheres, n_nodes, stream));
+    GRACE_TRY(use_records<MODE>(ts, a, b, frame, p, n_rays, n_spheres, n_nodes, stream, nested));
+    if (nested.measure) return GRACE_OK;
     a.width = p.width; a.split = p.split; a.treelet = p.treelet; a.treelet_axis = p.treelet_axis;
     a.n_rays = int(n_rays); a.n_nodes = int(n_nodes); a.n_prims = int(n_spheres); a.status = ts.status;
     a.group_shift = group_shift(n_spheres); a.chunk_shift = p.hit_chunk_shift; a.n_chunks = p.hit_chunks;
@@ -589,6 +604,41 @@ grace_status scene_invalidate_if_written(const void* d_written)
         && (d_written == ts.scene.key.prims || d_written == ts.scene.key.nodes || d_written == ts.scene.key.leaves))
         return scene_release(ts);
     return GRACE_OK;
+}
+
+// Hit counts / per-hit outputs of a ray range inside the caller's open frame (see Nested).
+grace_status trace_nested_bytes(size_t n_rays, size_t n_spheres, size_t n_nodes, size_t* bytes)
+{
+    // (never dereferenced: measuring returns before any launch)
+    TraceArgs a = trace_args(bytes, bytes, reinterpret_cast<const int*>(bytes), reinterpret_cast<const int*>(bytes),
+                             reinterpret_cast<const int*>(bytes));
+    size_t counts = 0, hits = 0;
+    GRACE_TRY(launch_trace<MODE_COUNT>(a, n_rays, n_spheres, n_nodes, nullptr, Nested{true, &counts}));
+    GRACE_TRY(launch_trace<MODE_HITS>(a, n_rays, n_spheres, n_nodes, nullptr, Nested{true, &hits}));
+    *bytes = counts > hits ? counts : hits;
+    return GRACE_OK;
+}
+
+grace_status trace_hitcounts_nested(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                                    const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                                    int* d_hit_counts, hipStream_t stream)
+{
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.out_counts = d_hit_counts;
+    return launch_trace<MODE_COUNT>(a, n_rays, n_spheres, n_nodes, stream, Nested{true, nullptr});
+}
+
+grace_status trace_hits_nested(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                               const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                               const int* d_ray_offsets, int* d_hit_indices, float* d_hit_integrals,
+                               float* d_hit_distances, hipStream_t stream)
+{
+    TraceArgs a = trace_args(d_rays, d_spheres, d_nodes, d_leaves, d_root);
+    a.offsets = d_ray_offsets;
+    a.hit_idx = d_hit_indices;
+    a.hit_integral = d_hit_integrals;
+    a.hit_dist = d_hit_distances;
+    return launch_trace<MODE_HITS>(a, n_rays, n_spheres, n_nodes, stream, Nested{true, nullptr});
 }
 } // namespace grace_hip
 

@@ -555,6 +555,77 @@ def trace_cumulative_weighted_sph(rays, spheres, tree, weights, out=None, check=
     return out
 
 
+def trace_emission_absorption_sph(rays, spheres, tree, emission, absorption, out=None, tau=None,
+                                  check=False):
+    """Depth-ordered emission-absorption integrals (an extension the reference lacks; the contract
+    is in grace_hip.h): every ray's hits ordered by (distance, sphere index), then in fp64
+    out[r, c] = sum_k emission[i_k, c] I_k phi(a_k) exp(-tau_k) with a_k = absorption[i_k] I_k,
+    tau_k the sum of the a in front of hit k and phi(a) = -expm1(-a) / a; tau[r] = sum_k a_k.
+    emission: float32 [n] or [n, C] (1 <= C <= 64), absorption: float32 [n], both in the order of
+    `spheres` (tree order); out: float32 [n_rays] or [n_rays, C] to match (allocated if None);
+    tau: float32 [n_rays], or None to skip it.  Returns out.  The rays are traced in batches
+    whose per-hit arrays fit set_ordered_budget's bytes, so the total number of hits is not
+    limited; the call synchronises the stream once."""
+    _check_rays(rays)
+    if emission.dtype != torch.float32 or absorption.dtype != torch.float32:
+        raise ValueError("emission and absorption must be float32")
+    if emission.dim() not in (1, 2) or emission.shape[0] != len(spheres):
+        raise ValueError("emission must have shape [n_spheres] or [n_spheres, C]")
+    if tuple(absorption.shape) != (len(spheres),):
+        raise ValueError("absorption must have shape [n_spheres]")
+    n_ch = 1 if emission.dim() == 1 else emission.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("emission must have 1..64 channels")
+    shape = (len(rays),) if emission.dim() == 1 else (len(rays), n_ch)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rays.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape:
+        raise ValueError("out must be float32 of shape %s" % (shape,))
+    if tau is not None and (tau.dtype != torch.float32 or tuple(tau.shape) != (len(rays),)):
+        raise ValueError("tau must be float32 of shape [%d]" % len(rays))
+    _check(_lib.grace_trace_emission_absorption_f4(*_trace_args(rays, spheres, tree), _ptr(emission),
+                                                   C.c_int(n_ch), _ptr(absorption), _ptr(out), _ptr(tau),
+                                                   _stream()))
+    if check:
+        trace_status()
+    return out
+
+
+def set_ordered_budget(n_bytes):
+    """Bytes of per-hit arrays (12 a hit) one batch of trace_emission_absorption_sph may hold
+    (process-wide; 0 restores the default).  A ray with more hits is a batch of its own."""
+    _check(_lib.grace_trace_set_ordered_budget(C.c_size_t(int(n_bytes))))
+
+
+def ordered_limits():
+    """(wave_max_hits, block_max_hits): the hit counts up to which a ray is ordered by one wave /
+    by one workgroup in LDS; longer rays are ordered in global memory."""
+    w, b = C.c_int(0), C.c_int(0)
+    _check(_lib.grace_trace_ordered_limits(C.byref(w), C.byref(b)))
+    return w.value, b.value
+
+
+class _OrderedStats(C.Structure):
+    _fields_ = [(k, C.c_ulonglong) for k in ("batches", "total_hits", "rays_wave", "rays_block",
+                                              "rays_global", "budget_bytes", "frame_bytes")] \
+        + [(k, C.c_float) for k in ("ms_count", "ms_trace", "ms_composite")]
+
+
+def ordered_enable_stats(enabled=True):
+    """Measurement hook (process-wide): trace_emission_absorption_sph times its phases,
+    synchronises before it returns and records what it did."""
+    _check(_lib.grace_trace_ordered_enable_stats(C.c_int(1 if enabled else 0)))
+
+
+def ordered_last_stats():
+    """The last trace_emission_absorption_sph call's record as a dict: batches, total_hits,
+    rays_wave / rays_block / rays_global, budget_bytes, frame_bytes, ms_count / ms_trace /
+    ms_composite."""
+    st = _OrderedStats()
+    _check(_lib.grace_trace_ordered_last_stats(C.byref(st)))
+    return {k: getattr(st, k) for k, _ in _OrderedStats._fields_}
+
+
 def _interp_outputs(n_points, n_spheres, weights, out, counts, device):
     """Checks weights / out / counts of an interpolation call and allocates what is missing."""
     if weights is None:

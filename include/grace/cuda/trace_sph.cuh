@@ -216,6 +216,49 @@ GRACE_HOST void trace_cumulative_weighted_sph(
     detail::check_trace_status();
 }
 
+// Extension (the reference has no such call): depth-ordered emission-absorption integrals --
+// grace_trace_emission_absorption_f4 (grace_hip.h has the contract).  d_emission holds n_channels
+// values per sphere, sphere-major, d_absorption one, both in the order of d_spheres (the tree's
+// sorted order).  Every ray's hits are ordered by (distance, sphere index); d_out[r * n_channels +
+// c] is the fp64 sum of emission I phi(a) exp(-tau) over them, d_tau[r] (if given) the ray's
+// optical depth.  The rays are traced in batches that fit set_ordered_budget's bytes.
+template <typename Real4>
+GRACE_HOST void trace_emission_absorption_sph(
+    const thrust::device_vector<Ray>& d_rays,
+    const thrust::device_vector<Real4>& d_spheres,
+    const Tree& d_tree,
+    const thrust::device_vector<float>& d_emission,
+    const int n_channels,
+    const thrust::device_vector<float>& d_absorption,
+    thrust::device_vector<float>& d_out,
+    thrust::device_vector<float>* d_tau = NULL)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_emission_absorption_sph: float4 spheres only (float coefficients and outputs)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("trace_emission_absorption_sph: n_channels must be 1..64");
+    if (d_emission.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_emission_absorption_sph: d_emission must hold n_channels per sphere");
+    if (d_absorption.size() != d_spheres.size())
+        throw std::invalid_argument("trace_emission_absorption_sph: d_absorption must hold one value per sphere");
+    if (d_out.size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_emission_absorption_sph: d_out must hold n_channels per ray");
+    if (d_tau && d_tau->size() != d_rays.size())
+        throw std::invalid_argument("trace_emission_absorption_sph: d_tau must hold one value per ray");
+    const detail::TreeArgs t = detail::tree_args(d_tree);
+    GRACE_STATUS_CHECK(grace_trace_emission_absorption_f4(
+        detail::raw(d_rays), d_rays.size(), reinterpret_cast<const float*>(detail::raw(d_spheres)),
+        d_spheres.size(), t.nodes, t.n_nodes, t.leaves, t.root, detail::raw(d_emission), n_channels,
+        detail::raw(d_absorption), detail::raw(d_out), d_tau ? detail::raw(*d_tau) : NULL, NULL));
+    detail::check_trace_status();
+}
+
+GRACE_HOST void set_ordered_budget(const size_t bytes)
+{
+    GRACE_STATUS_CHECK(grace_trace_set_ordered_budget(bytes));
+}
+
 // Extension (the reference has no such choice): the SPH kernel of every integrating trace --
 // column densities, weighted sums, the per-hit integrals of trace_sph / trace_with_sentinels_sph
 // (grace_trace_set_sph_kernel*, grace_hip.h).  A sphere's w is the kernel's support radius H.  A

@@ -687,6 +687,41 @@ inline void trace_cumulative_weighted_sph(const device_vector<Ray>& d_rays,
     detail::check(grace_trace_status(nullptr));
 }
 
+// Extension (the reference has no such call): depth-ordered emission-absorption integrals
+// (grace_trace_emission_absorption_f4, grace_hip.h): every ray's hits ordered by (distance, sphere
+// index), d_out[r * n_channels + c] the fp64 sum of emission I phi(a) exp(-tau) over them, d_tau[r]
+// (if given) the ray's optical depth; coefficients in tree order.
+template <typename Real4>
+inline void trace_emission_absorption_sph(const device_vector<Ray>& d_rays,
+                                          const device_vector<Real4>& d_spheres, const Tree& d_tree,
+                                          const device_vector<float>& d_emission, int n_channels,
+                                          const device_vector<float>& d_absorption,
+                                          device_vector<float>& d_out, device_vector<float>* d_tau = nullptr)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_emission_absorption_sph: float4 spheres only (float coefficients and outputs)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("trace_emission_absorption_sph: n_channels must be 1..64");
+    if (d_emission.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_emission_absorption_sph: d_emission must hold n_channels per sphere");
+    if (d_absorption.size() != d_spheres.size())
+        throw std::invalid_argument("trace_emission_absorption_sph: d_absorption must hold one value per sphere");
+    if (d_out.size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_emission_absorption_sph: d_out must hold n_channels per ray");
+    if (d_tau && d_tau->size() != d_rays.size())
+        throw std::invalid_argument("trace_emission_absorption_sph: d_tau must hold one value per ray");
+    detail::check(grace_trace_emission_absorption_f4(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                                     d_spheres.size(), &d_tree.nodes.data()->x,
+                                                     d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                                     d_tree.root_index_ptr, d_emission.data(), n_channels,
+                                                     d_absorption.data(), d_out.data(),
+                                                     d_tau ? d_tau->data() : nullptr, nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
+inline void set_ordered_budget(size_t bytes) { detail::check(grace_trace_set_ordered_budget(bytes)); }
+
 // Extension (the reference has no such call): the SPH field at points and on lattices
 // (grace_interpolate_points_f4 / _grid_f4, grace_hip.h): d_out[p * n_channels + c] = sum over spheres i
 // containing point p of fl(d_weights[i * n_channels + c] W_ip), spheres in tree order, the context's

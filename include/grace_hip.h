@@ -278,6 +278,61 @@ grace_status grace_trace_cumulative_weighted_f4(const void* d_rays, size_t n_ray
                                                 const int* d_leaves, const int* d_root,
                                                 const float* d_weights, int n_channels, float* d_out,
                                                 grace_stream stream);
+/* Depth-ordered emission-absorption integrals along rays -- an extension the reference lacks: light
+ * emitted by the spheres along the ray and absorbed by what lies in front of it, in one call and
+ * without ever holding more than a batch of hits.
+ * Inputs: rays, float4 spheres and the tree as for the other traces; d_emission [n_spheres *
+ * n_channels] fp32, 1 <= n_channels <= 64; d_absorption [n_spheres] fp32; both in tree order, read on
+ * every call.  Outputs: d_out [n_rays * n_channels] fp32; d_tau [n_rays] fp32, or null to skip it.
+ * For ray r, its hits are exactly those of grace_trace_hits_f4 on that ray: the same hit test, the
+ * same per-hit integral I (the reference's arithmetic, with the context's SPH kernel) and the same
+ * distance d, both bit for bit.  The hits are ordered ascending by (d, sphere index): d compared
+ * as fp32 (-0 == +0), ties broken by the lower index -- a total order, so the sequence does not
+ * depend on the traversal.  Then, in fp64, over the ordered hits k = 0, 1, ... with sphere i_k:
+ *   a_k      = (double)d_absorption[i_k] * (double)I_k         optical depth of hit k
+ *   tau_k    = sum over m < k of a_m                           what lies in front of it
+ *   phi(a)   = -expm1(-a) / a  for a != 0,  1 for a == 0       self-absorption of a uniform slab
+ *   d_out[r * n_channels + c] = fl32( sum_k (double)d_emission[i_k * n_channels + c] * (double)I_k * phi(a_k) * exp(-tau_k) )
+ *   d_tau[r]                  = fl32( sum_k a_k )
+ * (the formal solution of the transfer equation with each sphere a slab of constant source
+ * function).  Zero absorption gives the weighted column density; one sphere gives S (1 - e^-a)
+ * with S = emission / absorption.  Negative absorption is the caller's business: the formulas are
+ * applied as written.  A ray without hits gets zeros.  The order of the fp64 additions is a function
+ * of the ray's ordered hit list alone: results are bit-identical from run to run and do not depend
+ * on the packet width, the budget below, the other rays of the call or the ray's place among them.
+ * Against an evaluation of the formulas in another order, with another libm:
+ *   |out - ref| <= ulp32(ref) / 2 + 8 (n_r + 8) 2^-53 max(1, tau_r) sum_k |term_k|     (n_r hits).
+ * The call counts every ray's hits, cuts the rays, in array order, into batches whose per-hit
+ * arrays (12 bytes a hit) fit a byte budget, and per batch runs the per-hit walk into the context's
+ * workspace and one fused sort-and-composite kernel; it synchronises the stream once, to read the
+ * batch ends (not the per-ray counts).  The total number of hits is not limited to INT32_MAX.
+ * GRACE_INVALID_ARGUMENT for n_channels outside 1..64, null emission / absorption or null d_out
+ * (checked before any launch); zero rays: GRACE_OK, nothing written. */
+grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                                size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                                const int* d_leaves, const int* d_root,
+                                                const float* d_emission, int n_channels,
+                                                const float* d_absorption, float* d_out, float* d_tau,
+                                                grace_stream stream);
+/* The byte budget of a batch's per-hit arrays (process-wide; 0 restores the default, 1 GiB).  A
+ * target, never an error: a ray with more hits than the budget holds is a batch of its own.  The
+ * workspace grows to about the budget plus 12 bytes a ray plus the per-hit walk's own buffers. */
+grace_status grace_trace_set_ordered_budget(size_t bytes);
+/* The fused kernel's tiers: rays of up to *wave_max_hits hits are ordered by one wave in LDS, of up
+ * to *block_max_hits by a 256-thread workgroup in LDS, longer ones in global memory. */
+grace_status grace_trace_ordered_limits(int* wave_max_hits, int* block_max_hits);
+/* Measurement hook (process-wide): when enabled, every grace_trace_emission_absorption_f4 call
+ * times its phases with events, synchronises the stream before it returns and records what it did;
+ * grace_trace_ordered_last_stats returns the last call's record. */
+typedef struct grace_ordered_stats {
+    unsigned long long batches;       /* batches the rays were cut into */
+    unsigned long long total_hits;    /* hits of all rays */
+    unsigned long long rays_wave, rays_block, rays_global;   /* rays per tier (no hits: wave) */
+    unsigned long long budget_bytes, frame_bytes;            /* the budget used; workspace bytes of the call */
+    float ms_count, ms_trace, ms_composite;   /* counting walk + scan; per-hit walks; fused kernels */
+} grace_ordered_stats;
+grace_status grace_trace_ordered_enable_stats(int enabled);
+grace_status grace_trace_ordered_last_stats(grace_ordered_stats* h_stats);
 /* Per-hit outputs written from d_ray_offsets[ray] (RayEntry_from_array +
  * OnHit_sphere_individual, include/grace/cuda/functors/trace.cuh:44-60,196-235). */
 grace_status grace_trace_hits_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
