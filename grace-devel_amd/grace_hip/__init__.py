@@ -591,9 +591,51 @@ def trace_emission_absorption_sph(rays, spheres, tree, emission, absorption, out
     return out
 
 
+def trace_absorption_deposit_sph(rays, spheres, tree, luminosity, absorption, deposit=None,
+                                 transmitted=None, quantum=None, check=False):
+    """Absorbed radiation deposited on the particles (an extension the reference lacks; the
+    contract is in grace_hip.h): ray r carries luminosity[r, c]; its hits, ordered by (distance,
+    sphere index), absorb dep = L exp(-tau_k) (1 - exp(-a_k)) each with a_k = absorption[i_k, c] I_k
+    and tau_k the sum of the a in front of hit k, in fp64; deposit[i, c] is the sum over all rays
+    and transmitted[r, c] = L exp(-sum_k a_k) what escapes.  The sum over rays is made in 64-bit
+    fixed point with the quantum q_c = 2^(e_c + ceil(log2 n_rays) - 62), 2^(e_c - 1) <= max_r |L| <
+    2^e_c, so deposit is bit-identical for any order of the rays.
+    luminosity: float32 [n_rays] or [n_rays, C] (1 <= C <= 64); absorption: float32 [n] or [n, C]
+    to match, in the order of `spheres` (tree order); deposit: float64 [n] or [n, C], overwritten
+    (allocated if None); transmitted: float32 like luminosity, or None to skip it; quantum:
+    float64 [C], or None.  Returns deposit.  Batches and budget as trace_emission_absorption_sph."""
+    _check_rays(rays)
+    if luminosity.dtype != torch.float32 or absorption.dtype != torch.float32:
+        raise ValueError("luminosity and absorption must be float32")
+    if luminosity.dim() not in (1, 2) or luminosity.shape[0] != len(rays):
+        raise ValueError("luminosity must have shape [n_rays] or [n_rays, C]")
+    n_ch = 1 if luminosity.dim() == 1 else luminosity.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("luminosity must have 1..64 channels")
+    shape = (len(spheres),) if luminosity.dim() == 1 else (len(spheres), n_ch)
+    if tuple(absorption.shape) != shape:
+        raise ValueError("absorption must be float32 of shape %s" % (shape,))
+    if deposit is None:
+        deposit = torch.empty(shape, dtype=torch.float64, device=rays.device)
+    if deposit.dtype != torch.float64 or tuple(deposit.shape) != shape:
+        raise ValueError("deposit must be float64 of shape %s" % (shape,))
+    if transmitted is not None and (transmitted.dtype != torch.float32
+                                    or tuple(transmitted.shape) != tuple(luminosity.shape)):
+        raise ValueError("transmitted must be float32 of shape %s" % (tuple(luminosity.shape),))
+    if quantum is not None and (quantum.dtype != torch.float64 or tuple(quantum.shape) != (n_ch,)):
+        raise ValueError("quantum must be float64 of shape [%d]" % n_ch)
+    _check(_lib.grace_trace_absorption_deposit_f4(*_trace_args(rays, spheres, tree), _ptr(luminosity),
+                                                  _ptr(absorption), C.c_int(n_ch), _ptr(deposit),
+                                                  _ptr(transmitted), _ptr(quantum), _stream()))
+    if check:
+        trace_status()
+    return deposit
+
+
 def set_ordered_budget(n_bytes):
-    """Bytes of per-hit arrays (12 a hit) one batch of trace_emission_absorption_sph may hold
-    (process-wide; 0 restores the default).  A ray with more hits is a batch of its own."""
+    """Bytes of per-hit arrays (12 a hit) one batch of trace_emission_absorption_sph or
+    trace_absorption_deposit_sph may hold (process-wide; 0 restores the default).  A ray with
+    more hits is a batch of its own."""
     _check(_lib.grace_trace_set_ordered_budget(C.c_size_t(int(n_bytes))))
 
 
@@ -612,13 +654,14 @@ class _OrderedStats(C.Structure):
 
 
 def ordered_enable_stats(enabled=True):
-    """Measurement hook (process-wide): trace_emission_absorption_sph times its phases,
-    synchronises before it returns and records what it did."""
+    """Measurement hook (process-wide): trace_emission_absorption_sph and
+    trace_absorption_deposit_sph time their phases,
+    synchronise before they return and record what they did."""
     _check(_lib.grace_trace_ordered_enable_stats(C.c_int(1 if enabled else 0)))
 
 
 def ordered_last_stats():
-    """The last trace_emission_absorption_sph call's record as a dict: batches, total_hits,
+    """The last trace_emission_absorption_sph / trace_absorption_deposit_sph call's record as a dict: batches, total_hits,
     rays_wave / rays_block / rays_global, budget_bytes, frame_bytes, ms_count / ms_trace /
     ms_composite."""
     st = _OrderedStats()

@@ -254,6 +254,48 @@ GRACE_HOST void trace_emission_absorption_sph(
     detail::check_trace_status();
 }
 
+// Extension (the reference has no such call): absorbed radiation deposited on the particles --
+// grace_trace_absorption_deposit_f4 (grace_hip.h has the contract).  d_luminosity holds n_channels
+// values per ray, d_absorption n_channels per sphere in the order of d_spheres (the tree's sorted
+// order).  d_deposit[i * n_channels + c] is what sphere i absorbs of all rays in channel c (fp64,
+// overwritten; summed in 64-bit fixed point, so bit-identical for any order of the rays),
+// d_transmitted (if given) what every ray has left, d_quantum (if given) the channels' quanta.
+template <typename Real4>
+GRACE_HOST void trace_absorption_deposit_sph(
+    const thrust::device_vector<Ray>& d_rays,
+    const thrust::device_vector<Real4>& d_spheres,
+    const Tree& d_tree,
+    const thrust::device_vector<float>& d_luminosity,
+    const int n_channels,
+    const thrust::device_vector<float>& d_absorption,
+    thrust::device_vector<double>& d_deposit,
+    thrust::device_vector<float>* d_transmitted = NULL,
+    thrust::device_vector<double>* d_quantum = NULL)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_absorption_deposit_sph: float4 spheres only (float coefficients)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("trace_absorption_deposit_sph: n_channels must be 1..64");
+    if (d_luminosity.size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_luminosity must hold n_channels per ray");
+    if (d_absorption.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_absorption must hold n_channels per sphere");
+    if (d_deposit.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_deposit must hold n_channels per sphere");
+    if (d_transmitted && d_transmitted->size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_transmitted must hold n_channels per ray");
+    if (d_quantum && d_quantum->size() != size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_quantum must hold n_channels values");
+    const detail::TreeArgs t = detail::tree_args(d_tree);
+    GRACE_STATUS_CHECK(grace_trace_absorption_deposit_f4(
+        detail::raw(d_rays), d_rays.size(), reinterpret_cast<const float*>(detail::raw(d_spheres)),
+        d_spheres.size(), t.nodes, t.n_nodes, t.leaves, t.root, detail::raw(d_luminosity),
+        detail::raw(d_absorption), n_channels, detail::raw(d_deposit),
+        d_transmitted ? detail::raw(*d_transmitted) : NULL, d_quantum ? detail::raw(*d_quantum) : NULL, NULL));
+    detail::check_trace_status();
+}
+
 GRACE_HOST void set_ordered_budget(const size_t bytes)
 {
     GRACE_STATUS_CHECK(grace_trace_set_ordered_budget(bytes));

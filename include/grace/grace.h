@@ -720,6 +720,46 @@ inline void trace_emission_absorption_sph(const device_vector<Ray>& d_rays,
     detail::check(grace_trace_status(nullptr));
 }
 
+// Extension (the reference has no such call): absorbed radiation deposited on the particles --
+// grace_trace_absorption_deposit_f4 (grace_hip.h has the contract).  d_luminosity holds n_channels
+// values per ray, d_absorption n_channels per sphere in the order of d_spheres (the tree's sorted
+// order).  d_deposit[i * n_channels + c] is what sphere i absorbs of all rays in channel c (fp64,
+// overwritten; summed in 64-bit fixed point, so bit-identical for any order of the rays),
+// d_transmitted (if given) what every ray has left, d_quantum (if given) the channels' quanta.
+template <typename Real4>
+inline void trace_absorption_deposit_sph(const device_vector<Ray>& d_rays,
+                                         const device_vector<Real4>& d_spheres, const Tree& d_tree,
+                                         const device_vector<float>& d_luminosity, int n_channels,
+                                         const device_vector<float>& d_absorption,
+                                         device_vector<double>& d_deposit,
+                                         device_vector<float>* d_transmitted = nullptr,
+                                         device_vector<double>* d_quantum = nullptr)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_absorption_deposit_sph: float4 spheres only (float coefficients)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 64)
+        throw std::invalid_argument("trace_absorption_deposit_sph: n_channels must be 1..64");
+    if (d_luminosity.size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_luminosity must hold n_channels per ray");
+    if (d_absorption.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_absorption must hold n_channels per sphere");
+    if (d_deposit.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_deposit must hold n_channels per sphere");
+    if (d_transmitted && d_transmitted->size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_transmitted must hold n_channels per ray");
+    if (d_quantum && d_quantum->size() != size_t(n_channels))
+        throw std::invalid_argument("trace_absorption_deposit_sph: d_quantum must hold n_channels values");
+    detail::check(grace_trace_absorption_deposit_f4(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                                    d_spheres.size(), &d_tree.nodes.data()->x,
+                                                    d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                                    d_tree.root_index_ptr, d_luminosity.data(),
+                                                    d_absorption.data(), n_channels, d_deposit.data(),
+                                                    d_transmitted ? d_transmitted->data() : nullptr,
+                                                    d_quantum ? d_quantum->data() : nullptr, nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
 inline void set_ordered_budget(size_t bytes) { detail::check(grace_trace_set_ordered_budget(bytes)); }
 
 // Extension (the reference has no such call): the SPH field at points and on lattices

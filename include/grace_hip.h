@@ -314,6 +314,59 @@ grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_ray
                                                 const float* d_emission, int n_channels,
                                                 const float* d_absorption, float* d_out, float* d_tau,
                                                 grace_stream stream);
+/* Absorbed radiation deposited on the particles -- the transpose of the integral above, an extension
+ * the reference lacks (its trace_sph + sort_by_distance + weighted_exclusive_segmented_scan chain
+ * stops at the optical depth in front of every hit): rays leave a source carrying photons, and the
+ * call returns how much of every ray every particle absorbs, summed over the rays, and how much
+ * escapes.
+ * Inputs: rays, float4 spheres and the tree as for the other traces; d_luminosity [n_rays *
+ * n_channels] fp32, what ray r carries in channel c; d_absorption [n_spheres * n_channels] fp32, in
+ * tree order, per channel; 1 <= n_channels <= 64.  Outputs: d_deposit [n_spheres * n_channels] fp64,
+ * overwritten (not added to); d_transmitted [n_rays * n_channels] fp32, or null; d_quantum
+ * [n_channels] fp64, or null.
+ * For ray r its hits, their integrals I and distances d, and their order (ascending by d as fp32 with
+ * -0 == +0, then by sphere index) are those of grace_trace_emission_absorption_f4.  Then, in fp64, per
+ * channel c, over the ordered hits k with sphere i_k (C = n_channels, L = d_luminosity):
+ *   a_kc   = (double)d_absorption[i_k * C + c] * (double)I_k
+ *   tau_kc = sum over m < k of a_mc
+ *   dep_kc = (double)L[r * C + c] * exp(-tau_kc) * (-expm1(-a_kc))               absorbed by hit k
+ *   d_transmitted[r * C + c] = fl32( (double)L[r * C + c] * exp(-sum_k a_kc) )
+ * and d_deposit[i * C + c] is the sum of dep_kc over every (ray, hit) with i_k == i.  By construction
+ * sum_i deposit[i, c] + sum_r transmitted[r, c] = sum_r L[r, c] up to rounding, whatever the optical
+ * depths: the scheme conserves photons.  Rays without hits transmit L unchanged; spheres nobody hits
+ * get +0.0.
+ * The sum over rays is made in 64-bit fixed point, so it does not depend on arrival order.  Per
+ * channel, with M_c = max_r |L[r, c]|, e_c the integer with 2^(e_c - 1) <= M_c < 2^(e_c) and
+ * b = ceil(log2(n_rays)):
+ *   q_c  = 2^(e_c + b - 62)                        (d_quantum[c]; 0.0 when M_c == 0)
+ *   u_kc = round-half-even( dep_kc / q_c )         (exact scaling; a signed 64-bit integer)
+ *   d_deposit[i * C + c] = (double)( sum of u_kc ) * q_c
+ * For absorption >= 0 and finite L, |dep_kc| <= |L_rc| < 2^(e_c) and a sphere is hit by at most
+ * n_rays <= 2^b rays, so the integer sum stays below 2^62 plus at most 2^31 units of rounding: it
+ * cannot overflow.  The price: a hit that absorbs less than q_c / 2 deposits nothing, i.e. less than
+ * 2^(b - 62) of the brightest ray (2^-42 for 2^20 rays).  Integer addition is associative, so
+ * d_deposit is bit-identical from run to run, across budgets, packet widths, contexts, streams and
+ * any permutation of the rays (with L permuted alike); d_transmitted[r] depends on ray r alone.  A
+ * caller that sums deposits across devices and needs the same property sums the exact integers
+ * deposit / q_c (with one q_c for all ranks).
+ * Against an evaluation of the formulas in another order with another libm, m_i the number of rays
+ * that hit sphere i and n_r, tau_rc the hits and optical depth of ray r:
+ *   |deposit[i,c] - ref| <= m_i q_c + sum over the hits on i of 8 (n_r + 8) 2^-53 max(1, tau_rc) |dep_kc|
+ *   |transmitted - ref|  <= ulp32(ref) / 2 + 8 (n_r + 8) 2^-53 max(1, tau_rc) |ref|
+ * Outside the stated domain (negative absorption, non-finite L or absorption) the values of the
+ * affected channels are unspecified, but nothing faults: dep / q is clamped to [-2^62, 2^62], NaN
+ * to 0, before it becomes an integer.
+ * Batches, the byte budget (grace_trace_set_ordered_budget), the tiers and the stats hook are those
+ * of grace_trace_emission_absorption_f4; the int64 accumulators (8 bytes per sphere and channel) live
+ * in the workspace for the length of the call.  GRACE_INVALID_ARGUMENT for n_channels outside 1..64,
+ * null d_luminosity / d_absorption / d_deposit and counts out of range, checked before any launch;
+ * zero rays: GRACE_OK, d_deposit and d_quantum zeroed (d_luminosity may then be null). */
+grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                               size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                               const int* d_leaves, const int* d_root,
+                                               const float* d_luminosity, const float* d_absorption,
+                                               int n_channels, double* d_deposit, float* d_transmitted,
+                                               double* d_quantum, grace_stream stream);
 /* The byte budget of a batch's per-hit arrays (process-wide; 0 restores the default, 1 GiB).  A
  * target, never an error: a ray with more hits than the budget holds is a batch of its own.  The
  * workspace grows to about the budget plus 12 bytes a ray plus the per-hit walk's own buffers. */
@@ -321,8 +374,9 @@ grace_status grace_trace_set_ordered_budget(size_t bytes);
 /* The fused kernel's tiers: rays of up to *wave_max_hits hits are ordered by one wave in LDS, of up
  * to *block_max_hits by a 256-thread workgroup in LDS, longer ones in global memory. */
 grace_status grace_trace_ordered_limits(int* wave_max_hits, int* block_max_hits);
-/* Measurement hook (process-wide): when enabled, every grace_trace_emission_absorption_f4 call
- * times its phases with events, synchronises the stream before it returns and records what it did;
+/* Measurement hook (process-wide): when enabled, every grace_trace_emission_absorption_f4 and
+ * grace_trace_absorption_deposit_f4 call times its phases with events, synchronises the stream
+ * before it returns and records what it did (ms_composite: the call's own fused kernels);
  * grace_trace_ordered_last_stats returns the last call's record. */
 typedef struct grace_ordered_stats {
     unsigned long long batches;       /* batches the rays were cut into */
