@@ -1,4 +1,4 @@
-// Pieces shared by the depth-ordered traces (ordered.hip, deposit.hip): the tier limits, counts ->
+// Pieces shared by the depth-ordered traces (ordered.hip, deposit.hip, spectra.hip): the tier limits, counts ->
 // 64-bit offsets and batch ends, the load + sort of one ray's hits, and the host sequence that
 // counts, cuts and walks the batches.  The kernels and device functions have internal linkage:
 // each including translation unit gets its own copies.  The budget and the stats hook are
@@ -114,6 +114,11 @@ __device__ __forceinline__ uint32_t dist_key(const float d)
 {
     const uint32_t u = __float_as_uint(d + 0.0f);
     return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+// ... and back: the distance a key was made from (a zero comes back as +0)
+__device__ __forceinline__ float dist_from_key(const uint32_t k)
+{
+    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
 }
 
 template <int T>

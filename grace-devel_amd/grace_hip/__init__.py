@@ -632,9 +632,57 @@ def trace_absorption_deposit_sph(rays, spheres, tree, luminosity, absorption, de
     return deposit
 
 
+class _SpectrumGrid(C.Structure):
+    _fields_ = [("v0", C.c_double), ("dv", C.c_double), ("n_bins", C.c_int), ("periodic", C.c_int),
+                ("hubble", C.c_double)]
+
+
+def trace_spectra_sph(rays, spheres, tree, amount, width, velocity, v0, dv, n_bins, periodic=False,
+                      hubble=0.0, tau=None, column=None, check=False):
+    """Velocity-space absorption spectra along rays (an extension the reference lacks; the
+    contract is in grace_hip.h): every ray's hits ordered by (distance, sphere index); hit k has the
+    column N = amount[i_k, c] I_k, the velocity v = hubble d_k + velocity[i_k] . direction and the
+    Doppler parameter b = width[i_k, c], and adds N times the Gaussian of width b about v,
+    integrated over each bin [v0 + j dv, v0 + (j + 1) dv) within v -+ 6 b, to tau[r, c, j] / dv, in
+    fp64 and in a fixed order.  periodic: velocity wraps with period n_bins dv; otherwise the bins
+    are a window.  dv sum_j tau[r, c, j] = column[r, c] = sum_k N when nothing leaves the window.
+    amount, width: float32 [n] or [n, C] (1 <= C <= 16), velocity: float32 [n, 3], all in the order
+    of `spheres` (tree order); tau: float32 [n_rays, C, n_bins] (allocated if None); column: float32
+    [n_rays, C], or None to skip it.  Returns tau.  Batches and budget as
+    trace_emission_absorption_sph."""
+    _check_rays(rays)
+    if amount.dtype != torch.float32 or width.dtype != torch.float32 or velocity.dtype != torch.float32:
+        raise ValueError("amount, width and velocity must be float32")
+    if amount.dim() not in (1, 2) or amount.shape[0] != len(spheres):
+        raise ValueError("amount must have shape [n_spheres] or [n_spheres, C]")
+    n_ch = 1 if amount.dim() == 1 else amount.shape[1]
+    if not 1 <= n_ch <= 16:
+        raise ValueError("amount must have 1..16 channels")
+    if tuple(width.shape) != tuple(amount.shape):
+        raise ValueError("width must be float32 of shape %s" % (tuple(amount.shape),))
+    if tuple(velocity.shape) != (len(spheres), 3):
+        raise ValueError("velocity must be float32 of shape [n_spheres, 3]")
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 4096:
+        raise ValueError("n_bins must be 1..4096")
+    if tau is None:
+        tau = torch.empty((len(rays), n_ch, n_bins), dtype=torch.float32, device=rays.device)
+    if tau.dtype != torch.float32 or tuple(tau.shape) != (len(rays), n_ch, n_bins):
+        raise ValueError("tau must be float32 of shape %s" % ((len(rays), n_ch, n_bins),))
+    if column is not None and (column.dtype != torch.float32 or tuple(column.shape) != (len(rays), n_ch)):
+        raise ValueError("column must be float32 of shape %s" % ((len(rays), n_ch),))
+    grid = _SpectrumGrid(float(v0), float(dv), n_bins, 1 if periodic else 0, float(hubble))
+    _check(_lib.grace_trace_spectra_f4(*_trace_args(rays, spheres, tree), _ptr(amount), _ptr(width),
+                                       _ptr(velocity), C.c_int(n_ch), C.byref(grid), _ptr(tau),
+                                       _ptr(column), _stream()))
+    if check:
+        trace_status()
+    return tau
+
+
 def set_ordered_budget(n_bytes):
-    """Bytes of per-hit arrays (12 a hit) one batch of trace_emission_absorption_sph or
-    trace_absorption_deposit_sph may hold (process-wide; 0 restores the default).  A ray with
+    """Bytes of per-hit arrays (12 a hit) one batch of trace_emission_absorption_sph,
+    trace_absorption_deposit_sph or trace_spectra_sph may hold (process-wide; 0 restores the default).  A ray with
     more hits is a batch of its own."""
     _check(_lib.grace_trace_set_ordered_budget(C.c_size_t(int(n_bytes))))
 
@@ -654,14 +702,14 @@ class _OrderedStats(C.Structure):
 
 
 def ordered_enable_stats(enabled=True):
-    """Measurement hook (process-wide): trace_emission_absorption_sph and
-    trace_absorption_deposit_sph time their phases,
+    """Measurement hook (process-wide): trace_emission_absorption_sph,
+    trace_absorption_deposit_sph and trace_spectra_sph time their phases,
     synchronise before they return and record what they did."""
     _check(_lib.grace_trace_ordered_enable_stats(C.c_int(1 if enabled else 0)))
 
 
 def ordered_last_stats():
-    """The last trace_emission_absorption_sph / trace_absorption_deposit_sph call's record as a dict: batches, total_hits,
+    """The last trace_emission_absorption_sph / trace_absorption_deposit_sph / trace_spectra_sph call's record as a dict: batches, total_hits,
     rays_wave / rays_block / rays_global, budget_bytes, frame_bytes, ms_count / ms_trace /
     ms_composite."""
     st = _OrderedStats()

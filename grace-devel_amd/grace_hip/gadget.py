@@ -1,15 +1,21 @@
 """Gadget-2 (format 1) snapshot I/O for the SPH fields GRACE uses: gas positions and
-smoothing lengths, and positions and masses of any particle type (read_gadget_particles).
+smoothing lengths, positions and masses of any particle type (read_gadget_particles), and the
+velocities and gas fields a sightline spectrum needs (read_gadget_fields).
 Block layout as read by the reference's tests/helper/read_gadget.cuh: header of 256 B
 (npart[6] int32, mass[6] float64, padding) and POS, VEL, ID, [MASS], U, RHO, HSML blocks,
 every block framed by 4-byte markers.  Host-side file I/O only (numpy)."""
 import numpy as np
 
 
-def write_gadget(fname, pos, hsml, masses_in_header=True):
-    """Writes a gas-only snapshot: pos [N,3] float32, hsml [N] float32."""
+def write_gadget(fname, pos, hsml, masses_in_header=True, vel=None, u=None):
+    """Writes a gas-only snapshot: pos [N,3] float32, hsml [N] float32; vel [N,3] and u [N]
+    float32 fill the VEL and U blocks (zeros when None)."""
     pos = np.ascontiguousarray(pos, np.float32); hsml = np.ascontiguousarray(hsml, np.float32)
     n = len(pos)
+    vel = np.zeros((n, 3), np.float32) if vel is None else np.ascontiguousarray(vel, np.float32)
+    u = np.zeros(n, np.float32) if u is None else np.ascontiguousarray(u, np.float32)
+    if vel.shape != (n, 3) or u.shape != (n,):
+        raise ValueError("vel must have shape [N, 3] and u shape [N]")
     npart = np.array([n, 0, 0, 0, 0, 0], np.int32)
     mass = np.array([1.0 if masses_in_header else 0.0, 0, 0, 0, 0, 0], np.float64)
 
@@ -21,11 +27,11 @@ def write_gadget(fname, pos, hsml, masses_in_header=True):
         header = npart.tobytes() + mass.tobytes()
         block(f, header + bytes(256 - len(header)))
         block(f, pos.tobytes())                                   # POS
-        block(f, np.zeros((n, 3), np.float32).tobytes())          # VEL
+        block(f, vel.tobytes())                                   # VEL
         block(f, np.arange(n, dtype=np.int32).tobytes())          # ID
         if not masses_in_header:
             block(f, np.ones(n, np.float32).tobytes())            # MASS (only if header mass == 0)
-        block(f, np.zeros(n, np.float32).tobytes())               # U
+        block(f, u.tobytes())                                     # U
         block(f, np.ones(n, np.float32).tobytes())                # RHO
         block(f, hsml.tobytes())                                  # HSML
 
@@ -98,3 +104,36 @@ def read_gadget_particles(fname, ptype):
     m_first = sum(npart[t] for t in range(ptype) if mass[t] == 0)
     m = take_block().view(np.float32)[m_first:m_first + n].copy()
     return p, m
+
+
+def read_gadget_fields(fname, ptype):
+    """Returns a dict of float32 arrays for the particles of type ptype (0..5): "pos" [N, 3] and
+    "vel" [N, 3], and for gas (ptype 0) also "u", "rho" and "hsml" [N] -- the blocks read_gadget
+    skips.  POS and VEL hold every type in type order; U, RHO and HSML hold the gas only."""
+    if not 0 <= int(ptype) <= 5:
+        raise ValueError("ptype must be 0..5")
+    ptype = int(ptype)
+    with open(fname, "rb") as f:
+        raw = np.frombuffer(f.read(), np.uint8)
+    pos = 0
+
+    def take_block():
+        nonlocal pos
+        nbytes = int(raw[pos:pos + 4].view(np.int32)[0])
+        data = raw[pos + 4: pos + 4 + nbytes]
+        pos += 8 + nbytes
+        return data
+
+    header = take_block()
+    npart = [int(x) for x in header[:24].view(np.int32)]
+    mass = header[24:72].view(np.float64)
+    first, n = sum(npart[:ptype]), npart[ptype]
+    out = {"pos": take_block().view(np.float32).reshape(-1, 3)[first:first + n].copy(),
+           "vel": take_block().view(np.float32).reshape(-1, 3)[first:first + n].copy()}
+    if ptype == 0:
+        take_block()             # ID
+        if any(npart[t] > 0 and mass[t] == 0 for t in range(6)):
+            take_block()         # MASS
+        for name in ("u", "rho", "hsml"):
+            out[name] = take_block().view(np.float32)[:n].copy()
+    return out

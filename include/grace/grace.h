@@ -760,6 +760,48 @@ inline void trace_absorption_deposit_sph(const device_vector<Ray>& d_rays,
     detail::check(grace_trace_status(nullptr));
 }
 
+// Extension (the reference has no such call): velocity-space absorption spectra along rays --
+// grace_trace_spectra_f4 (grace_hip.h has the contract).  d_amount and d_width hold n_channels
+// values per sphere, d_velocity three, in the order of d_spheres (the tree's sorted order).
+// d_tau[(r * n_channels + c) * grid.n_bins + j] is the optical depth of ray r in channel c and
+// velocity bin j (every hit a Gaussian of Doppler parameter d_width about its line-of-sight
+// velocity, integrated over the bins, in fp64 and in a fixed order); d_column (if given) the
+// rays' columns per channel.  SpectrumGrid is the C struct: v0, dv, n_bins, periodic, hubble.
+typedef grace_spectrum_grid SpectrumGrid;
+
+template <typename Real4>
+inline void trace_spectra_sph(const device_vector<Ray>& d_rays, const device_vector<Real4>& d_spheres,
+                              const Tree& d_tree, const device_vector<float>& d_amount,
+                              const device_vector<float>& d_width, const device_vector<float>& d_velocity,
+                              int n_channels, const SpectrumGrid& grid, device_vector<float>& d_tau,
+                              device_vector<float>* d_column = nullptr)
+{
+    static_assert(std::is_same<Real4, float4>::value,
+                  "trace_spectra_sph: float4 spheres only (float coefficients)");
+    detail::check_ray_count(d_rays.size());
+    if (n_channels < 1 || n_channels > 16)
+        throw std::invalid_argument("trace_spectra_sph: n_channels must be 1..16");
+    if (grid.n_bins < 1 || grid.n_bins > 4096)
+        throw std::invalid_argument("trace_spectra_sph: grid.n_bins must be 1..4096");
+    if (d_amount.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_spectra_sph: d_amount must hold n_channels per sphere");
+    if (d_width.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_spectra_sph: d_width must hold n_channels per sphere");
+    if (d_velocity.size() != d_spheres.size() * 3)
+        throw std::invalid_argument("trace_spectra_sph: d_velocity must hold three values per sphere");
+    if (d_tau.size() != d_rays.size() * size_t(n_channels) * size_t(grid.n_bins))
+        throw std::invalid_argument("trace_spectra_sph: d_tau must hold n_channels * n_bins per ray");
+    if (d_column && d_column->size() != d_rays.size() * size_t(n_channels))
+        throw std::invalid_argument("trace_spectra_sph: d_column must hold n_channels per ray");
+    detail::check(grace_trace_spectra_f4(d_rays.data(), d_rays.size(), &d_spheres.data()->x,
+                                         d_spheres.size(), &d_tree.nodes.data()->x,
+                                         d_tree.leaves.size() - 1, &d_tree.leaves.data()->x,
+                                         d_tree.root_index_ptr, d_amount.data(), d_width.data(),
+                                         d_velocity.data(), n_channels, &grid, d_tau.data(),
+                                         d_column ? d_column->data() : nullptr, nullptr));
+    detail::check(grace_trace_status(nullptr));
+}
+
 inline void set_ordered_budget(size_t bytes) { detail::check(grace_trace_set_ordered_budget(bytes)); }
 
 // Extension (the reference has no such call): the SPH field at points and on lattices

@@ -367,6 +367,65 @@ grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays
                                                const float* d_luminosity, const float* d_absorption,
                                                int n_channels, double* d_deposit, float* d_transmitted,
                                                double* d_quantum, grace_stream stream);
+/* Velocity-space absorption spectra along rays -- an extension the reference lacks: the optical depth
+ * of an absorption line (Lyman-alpha forest, metal lines, 21 cm) as a function of velocity along each
+ * ray, every hit a thermally broadened Gaussian integrated over the velocity bins it reaches.
+ * Inputs: rays, float4 spheres and the tree as for the other traces; d_amount [n_spheres * C] fp32,
+ * what a unit of the line integral I contributes to the column of channel c (species / line);
+ * d_width [n_spheres * C] fp32, the Doppler parameter b; d_velocity [n_spheres * 3] fp32; all in tree
+ * order, read on every call; 1 <= C = n_channels <= 16.  grid: a host pointer, read before the call
+ * returns.  Outputs: d_tau [n_rays * C * n_bins] fp32, every element written; d_column [n_rays * C]
+ * fp32, or null.
+ * For ray r its hits, their integrals I and distances d (the projection of the centre on the ray), and
+ * their order (ascending by d as fp32 with -0 == +0, then by sphere index) are those of
+ * grace_trace_emission_absorption_f4.  Then, in fp64, over the ordered hits k with sphere i_k and the
+ * ray's direction (dx, dy, dz) as stored in the ray:
+ *   N_kc    = (double)d_amount[i_k * C + c] * (double)I_k                  column of hit k in channel c
+ *   v_k     = hubble * (double)d_k + (((double)vx * dx + (double)vy * dy) + (double)vz * dz)
+ *   b_kc    = (double)d_width[i_k * C + c]
+ *   e_u     = v0 + u * dv                                                   edge u, u any integer
+ *   P_kc(u) = 0.5 * ( erf((e_{u+1} - v_k) / b_kc) - erf((e_u - v_k) / b_kc) )   the Gaussian over bin u
+ *   window of hit k in channel c: u_lo = floor((v_k - 6 b_kc - v0) / dv) .. u_hi = floor((v_k + 6 b_kc - v0) / dv)
+ *   periodic == 0:  d_tau[(r * C + c) * n_bins + j] = fl32( (1 / dv) * sum_k [u_lo <= j <= u_hi] N_kc P_kc(j) )
+ *   periodic != 0:  d_tau[(r * C + c) * n_bins + j] = fl32( (1 / dv) * sum_k sum_{u in window, u mod n_bins == j} N_kc P_kc(u) )
+ *   d_column[r * C + c] = fl32( sum_k N_kc )
+ * for 0 <= j < n_bins.  The profile is integrated over the bin, not sampled at its centre: a line
+ * narrower than a bin is not lost, and dv * sum_j tau[r, c, j] equals column[r, c] up to erfc(6) =
+ * 2.2e-17 per hit and rounding -- always in periodic mode, and in window mode when no window leaves
+ * [0, n_bins).  Flux is exp(-tau), left to the caller.
+ * Per bin the terms are added hit by hit in depth order and, within one hit, in ascending u.  A ray's
+ * spectrum is therefore a function of its ordered hit list alone: bit-identical from run to run, for
+ * any budget, packet width, context and stream, and whatever the other rays of the call or the ray's
+ * place among them.
+ * A hit whose width is <= 0, NaN or infinite adds nothing to d_tau in that channel (it still counts
+ * in d_column); a hit with a non-finite v_k adds nothing to d_tau.  In periodic mode a window is
+ * clipped to n_bins bins either side of v_k's bin, so no input makes the work per hit exceed
+ * 2 n_bins + 1 bins; a width above a quarter of the period n_bins * dv is outside the domain (values
+ * unspecified), and so is |v_k - v0| / dv >= 2^52 (the hit adds nothing).  Rays without hits get zeros.
+ * Against an evaluation of the formulas in another order with another libm, with eps = 2^-53, n_r
+ * the ray's hits and V_k = |v0| + n_bins dv + |hubble d_k| + |vx dx| + |vy dy| + |vz dz|:
+ *   |tau - ref| <= ulp32(ref) / 2 + eps sum_k (|N_kc| / dv) 16 (1 + V_k / b_kc) + 8 (n_r + 8) eps sum_k |term_k|
+ * plus |N_kc| / dv * erfc(6) for every hit whose window's edge falls in another bin on the other
+ * side; d_column is within ulp32(ref) / 2 + 8 (n_r + 8) eps sum_k |N_kc|.
+ * Batches, the byte budget (grace_trace_set_ordered_budget), the tiers and the stats hook are those
+ * of grace_trace_emission_absorption_f4; the call needs no workspace of its own beyond theirs.
+ * GRACE_INVALID_ARGUMENT, before any launch, for n_channels outside 1..16, n_bins outside 1..4096, dv
+ * not a positive finite number, non-finite v0 or hubble, null grid / d_amount / d_width / d_velocity /
+ * d_tau and counts out of range; zero rays: GRACE_OK, nothing written.
+ * Not here: Voigt (damped) profiles, double4 spheres, fp64 outputs. */
+typedef struct grace_spectrum_grid {
+    double v0;        /* lower edge of bin 0 */
+    double dv;        /* bin width, > 0 */
+    int    n_bins;    /* 1 .. 4096 */
+    int    periodic;  /* 0: the bins are a window; 1: velocity wraps with period n_bins * dv */
+    double hubble;    /* velocity per unit length along the ray; 0 for none */
+} grace_spectrum_grid;
+grace_status grace_trace_spectra_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                    size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                    const int* d_leaves, const int* d_root,
+                                    const float* d_amount, const float* d_width, const float* d_velocity,
+                                    int n_channels, const grace_spectrum_grid* grid, float* d_tau,
+                                    float* d_column, grace_stream stream);
 /* The byte budget of a batch's per-hit arrays (process-wide; 0 restores the default, 1 GiB).  A
  * target, never an error: a ray with more hits than the budget holds is a batch of its own.  The
  * workspace grows to about the budget plus 12 bytes a ray plus the per-hit walk's own buffers. */
@@ -375,8 +434,8 @@ grace_status grace_trace_set_ordered_budget(size_t bytes);
  * to *block_max_hits by a 256-thread workgroup in LDS, longer ones in global memory. */
 grace_status grace_trace_ordered_limits(int* wave_max_hits, int* block_max_hits);
 /* Measurement hook (process-wide): when enabled, every grace_trace_emission_absorption_f4 and
- * grace_trace_absorption_deposit_f4 call times its phases with events, synchronises the stream
- * before it returns and records what it did (ms_composite: the call's own fused kernels);
+ * grace_trace_absorption_deposit_f4 and grace_trace_spectra_f4 call times its phases with events,
+ * synchronises the stream before it returns and records what it did (ms_composite: the call's own fused kernels);
  * grace_trace_ordered_last_stats returns the last call's record. */
 typedef struct grace_ordered_stats {
     unsigned long long batches;       /* batches the rays were cut into */
