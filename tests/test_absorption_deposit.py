@@ -31,7 +31,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_emission_absorption import _build, _build_one, _collinear_scene
+from test_emission_absorption import _build, _build_one, _collinear_scene, _spread, clustered_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "grace-devel_amd", "lib")
@@ -577,6 +577,92 @@ def test_more_hits_than_int32_can_index(gh, oracle, cuda):
         assert np.all(err <= tol), (i, dep[i], R.dep[i])
         terr = np.abs(trans[near].astype(F64) - R.trans)
         assert np.all(terr <= transmitted_bound(R))
+    # ... and what 64 rays spread over the image transmit, against the restatement
+    sub = _spread(m, 64)
+    _check_transmitted(oracle, rh[sub], sh, L[sub], k, trans[sub], "beyond int32", least=1000)
+
+
+def _check_transmitted(oracle, rays_h, sh, L, k, trans, what, least=1):
+    """transmitted of some of a call's rays against the restatement (the deposit needs all rays)."""
+    off, idx, integ, dist = oracle.brute_hits(rays_h, sh)
+    R = restate(len(rays_h), len(sh), off, idx, integ, dist, L, k)
+    assert R.n_r.min() >= least
+    terr, ttol = np.abs(trans.astype(F64) - R.trans), transmitted_bound(R)
+    print("%s: transmitted max err/tol %.3g; tau range %.3g..%.3g" % (what, float(np.max(terr / ttol)),
+                                                                      float(R.tau.min()), float(R.tau.max())))
+    assert np.all(terr <= ttol), (what, np.argwhere(~(terr <= ttol))[:5])
+
+
+@pytest.mark.gpu
+def test_more_batches_than_the_first_table_copy_holds(gh, oracle, ad_scene, cuda):
+    """Budget 1 on 72^2 = 5184 rays that all hit: more batches than the first read of the batch
+    table holds (this translation unit's copy of the sequence).  The bits of the single-batch
+    call; transmitted against the restatement on a sample."""
+    import torch
+    d, tree, sh, _ = ad_scene
+    rays = gh.orthogonal_rays_z(72, (0, 0, 0, 0), (1, 1, 1, 0), device=cuda)[0]
+    counts = torch.empty(len(rays), dtype=torch.int32, device=cuda)
+    gh.trace_hitcounts_sph(rays, d, tree, counts, check=True)
+    assert len(rays) >= 4200 and int(counts.min()) > 0
+    L, k = _coefficients(sh, len(rays), 3, 29)
+    gh.ordered_enable_stats(True)
+    base = _trace(gh, rays, d, tree, L, k)
+    assert gh.ordered_last_stats()["batches"] == 1
+    gh.set_ordered_budget(1)
+    got = _trace(gh, rays, d, tree, L, k)
+    st = gh.ordered_last_stats()
+    assert st["batches"] == len(rays) > 4088 and st["total_hits"] == int(counts.long().sum())
+    assert _same(got[0], base[0]) and _same(got[1], base[1]) and _same(got[2], base[2])
+    sub = _spread(len(rays), 128)
+    _check_transmitted(oracle, rays.cpu().numpy()[sub], sh, L[sub], k, got[1][sub], "5184 batches")
+    assert float(np.abs(got[0]).sum()) > 0
+
+
+@pytest.mark.gpu
+def test_a_call_whose_rays_hit_nothing(gh, ad_scene, cuda):
+    """No hit in the whole call: nothing deposited (+0.0), every luminosity transmitted bit for
+    bit, and the next ordinary call is what it was."""
+    d, tree, sh, sets = ad_scene
+    rays, (off, idx, _, _) = sets["healpix"]
+    L, k = _coefficients(sh, len(rays), 5, 37)
+    before = _trace(gh, rays, d, tree, L, k)
+    away = rays.clone()
+    away[:, 3:6] += 10.0                                                   # length 1, ten box lengths off
+    gh.ordered_enable_stats(True)
+    dep, trans, q = _trace(gh, away.contiguous(), d, tree, L, k)
+    st = gh.ordered_last_stats()
+    assert st["total_hits"] == 0 and st["batches"] == 1
+    assert not np.any(dep.view(np.uint64)) and _same(trans, L)
+    assert np.array_equal(q.view(np.uint64), quantum(L, len(rays)).view(np.uint64))
+    after = _trace(gh, rays, d, tree, L, k)
+    assert gh.ordered_last_stats()["total_hits"] == len(idx) > 0
+    assert _same(after[0], before[0]) and _same(after[1], before[1]) and _same(after[2], before[2])
+
+
+@pytest.mark.gpu
+def test_one_batch_of_4096_packets_on_a_clustered_scene(gh, oracle, cuda):
+    """512^2 rays in one batch: 4096 packets of 64, from where on the nested per-hit walk is the
+    one-wave variant that stages in LDS.  Transmitted against the restatement on 256 sampled
+    rays; photons conserved over the whole call within test_more_hits_than_int32_can_index's bound."""
+    d, tree = _build(gh, cuda, clustered_scene(20000, 47))
+    sh = d.cpu().numpy()
+    rays = gh.orthogonal_rays_z(512, (0, 0, 0, 0), (1, 1, 1, 0), device=cuda)[0]
+    m, n = len(rays), len(sh)
+    rng = np.random.default_rng(59)
+    L = (0.5 + rng.random((m, 2))).astype(F32)
+    k = _coefficients(sh, 1, 2, 53)[1]
+    gh.ordered_enable_stats(True)
+    dep, trans, q = _trace(gh, rays, d, tree, L, k)
+    st = gh.ordered_last_stats()
+    assert st["batches"] == 1 and m // 64 >= 4096
+    sub = _spread(m, 256)
+    _check_transmitted(oracle, rays.cpu().numpy()[sub], sh, L[sub], k, trans[sub], "4096 packets")
+    # every hit within q of its exact share and within the fp64 bound (n_r <= n = 20000, tau <= 1000:
+    # 8 * 20008 * 1000 * 2^-53 < 2e-8 relative), transmitted within 2^-24 relative
+    Lsum = L.astype(F64).sum(0)
+    err = np.abs(dep.sum(0) + trans.astype(F64).sum(0) - Lsum)
+    tol = st["total_hits"] * q + (2e-8 + 2.0 ** -24 + 3 * (n + m) * 2.0 ** -53) * Lsum
+    assert np.all(err <= tol) and np.all(dep >= 0) and np.all(dep.sum(0) > 0.05 * Lsum), (err, tol)
 
 
 @pytest.mark.gpu

@@ -20,6 +20,7 @@ delta in exp(-tau_k).  Hence, with S = sum_k |term_k|,
 the first term being the final rounding to fp32 and the second a loose bound on the fp64 error;
 tau gets the same bound with S = tau_r."""
 import ctypes
+import math
 import os
 import subprocess
 
@@ -419,9 +420,9 @@ def test_argument_checks(gh, ea_scene, cuda):
 
 
 @pytest.mark.gpu
-def test_more_hits_than_int32_can_index(gh, cuda):
+def test_more_hits_than_int32_can_index(gh, oracle, cuda):
     """1024^2 orthographic rays over 2 x 10^6 uniform particles: ~2.3e9 hits, on which trace_sph
-    raises.  No oracle at this size; three relations are the check."""
+    raises.  Three relations over the whole image, and the restatement on 64 of its rays."""
     import torch
     n = 2_000_000
     rng = np.random.default_rng(23)
@@ -453,6 +454,141 @@ def test_more_hits_than_int32_can_index(gh, cuda):
     assert torch.all((tau - col_k).abs() <= 1e-5 * col_k)
     assert torch.all(thick >= 0) and torch.all(thick <= thin * (1 + 1e-5))
     assert float(tau.max()) > 1.0 and float((thick / thin).min()) < 0.7     # absorption did something
+    # ... and 64 rays spread over the image against the restatement
+    sub = torch.from_numpy(_spread(len(rays), 64)).to(cuda)
+    off, idx, integ, dist = oracle.brute_hits(rays[sub].cpu().numpy(), sh)
+    eh, kh = e.cpu().numpy(), k.cpu().numpy()
+    ref, rtau, S, n_r = restate(64, off, idx, integ, dist, eh, kh)
+    assert n_r.min() > 1000
+    check(thick[sub].cpu().numpy(), tau[sub].cpu().numpy(), ref, rtau, S, n_r, "beyond int32, thick")
+    ref, rtau, S, n_r = restate(64, off, idx, integ, dist, eh, np.zeros(n, F32))
+    check(thin[sub].cpu().numpy(), tau0[sub].cpu().numpy(), ref, rtau, S, n_r, "beyond int32, thin")
+
+
+def _spread(n_rays, k):
+    """k ray indices spread over an image of n_rays, off the rows' starts."""
+    return (np.arange(k, dtype=np.int64) * (n_rays // k) + (n_rays // k) // 3 + 7 * np.arange(k)) % n_rays
+
+
+@pytest.mark.gpu
+def test_more_batches_than_the_first_table_copy_holds(gh, oracle, ea_scene, cuda):
+    """Budget 1 on 72^2 = 5184 rays that all hit: one batch a ray, more than the 4096 - 8 ends
+    the first read of the batch table holds.  The bits of the single-batch call, and the
+    restatement on a sample."""
+    import torch
+    d, tree, sh, _ = ea_scene
+    rays = gh.orthogonal_rays_z(72, (0, 0, 0, 0), (1, 1, 1, 0), device=cuda)[0]
+    counts = torch.empty(len(rays), dtype=torch.int32, device=cuda)
+    gh.trace_hitcounts_sph(rays, d, tree, counts, check=True)
+    assert len(rays) >= 4200 and int(counts.min()) > 0
+    e, k = _coefficients(sh, 3, 29)
+    gh.ordered_enable_stats(True)
+    gh.set_ordered_budget(1 << 32)
+    base, base_tau = _trace(gh, rays, d, tree, e, k)
+    assert gh.ordered_last_stats()["batches"] == 1
+    gh.set_ordered_budget(1)
+    got, got_tau = _trace(gh, rays, d, tree, e, k)
+    st = gh.ordered_last_stats()
+    assert st["batches"] == len(rays) > 4088 and st["total_hits"] == int(counts.long().sum())
+    assert np.array_equal(_bits(got), _bits(base)) and np.array_equal(_bits(got_tau), _bits(base_tau))
+    sub = _spread(len(rays), 128)
+    off, idx, integ, dist = oracle.brute_hits(rays.cpu().numpy()[sub], sh)
+    ref, tau, S, n_r = restate(len(sub), off, idx, integ, dist, e, k)
+    check(got[sub], got_tau[sub], ref, tau, S, n_r, "5184 batches")
+
+
+@pytest.mark.gpu
+def test_a_call_whose_rays_hit_nothing(gh, ea_scene, cuda):
+    """No hit in the whole call: the per-hit walk is not run; zeros come back, and the next
+    ordinary call is what it was."""
+    d, tree, sh, sets = ea_scene
+    rays, (off, idx, _, _) = sets["healpix"]
+    e, k = _coefficients(sh, 5, 37)
+    before = _trace(gh, rays, d, tree, e, k)
+    away = rays.clone()
+    away[:, 3:6] += 10.0                                                   # length 1, ten box lengths off
+    gh.ordered_enable_stats(True)
+    got, got_tau = _trace(gh, away.contiguous(), d, tree, e, k)
+    st = gh.ordered_last_stats()
+    assert st["total_hits"] == 0 and st["batches"] == 1 and st["rays_wave"] == len(rays)
+    assert not np.any(_bits(got)) and not np.any(_bits(got_tau))          # +0.0, every one
+    after = _trace(gh, rays, d, tree, e, k)
+    assert gh.ordered_last_stats()["total_hits"] == len(idx) > 0
+    assert np.array_equal(_bits(after[0]), _bits(before[0])) and np.array_equal(_bits(after[1]), _bits(before[1]))
+
+
+def clustered_scene(n, seed):
+    """Gaussian blobs over a uniform third, radii log-uniform over 1.5 decades (0.003 ... 0.1)."""
+    rng = np.random.default_rng(seed)
+    centre = rng.uniform(0.2, 0.8, (8, 3)); sigma = 10.0 ** rng.uniform(-1.5, -0.8, 8)
+    which = rng.integers(0, 8, n)
+    p = centre[which] + rng.normal(size=(n, 3)) * sigma[which, None]
+    free = rng.random(n) < 1.0 / 3.0
+    p[free] = rng.random((int(free.sum()), 3))
+    s = np.empty((n, 4), F32)
+    s[:, :3] = np.clip(p, 0.0, 1.0)
+    s[:, 3] = 0.003 * 10.0 ** (1.5 * rng.random(n) + math.log10(0.1 / 0.003) - 1.5)
+    return s
+
+
+@pytest.mark.gpu
+def test_one_batch_of_4096_packets_on_a_clustered_scene(gh, oracle, cuda):
+    """512^2 rays in one batch: 4096 packets of 64, from where on the nested per-hit walk is the
+    one-wave variant that stages in LDS.  The restatement on 256 sampled rays."""
+    d, tree = _build(gh, cuda, clustered_scene(20000, 47))
+    sh = d.cpu().numpy()
+    assert sh[:, 3].max() / sh[:, 3].min() > 25.0
+    rays = gh.orthogonal_rays_z(512, (0, 0, 0, 0), (1, 1, 1, 0), device=cuda)[0]
+    e, k = _coefficients(sh, 3, 53)
+    gh.ordered_enable_stats(True)
+    got, got_tau = _trace(gh, rays, d, tree, e, k)
+    st = gh.ordered_last_stats()
+    assert st["batches"] == 1 and len(rays) // 64 >= 4096
+    sub = _spread(len(rays), 256)
+    off, idx, integ, dist = oracle.brute_hits(rays.cpu().numpy()[sub], sh)
+    assert len(idx) > 10000
+    ref, tau, S, n_r = restate(len(sub), off, idx, integ, dist, e, k)
+    check(got[sub], got_tau[sub], ref, tau, S, n_r, "4096 packets")
+
+
+@pytest.mark.gpu
+def test_heavy_packets_take_the_staged_split_walk(gh, oracle, cuda):
+    """test_trace_boundaries' scene of heavy packets (100 000 spheres with h ~ 0.12, 16 packets of
+    64 rays, ~4500 hits a ray: at least 200 000 hits a packet) through the nested per-hit walk,
+    with hit staging on and off: the same bits, and the restatement on 40 rays."""
+    import torch
+    rng = np.random.default_rng(8)
+    n = 100_000
+    s = np.empty((n, 4), F32)
+    s[:, :3] = rng.random((n, 3), dtype=F32)
+    s[:, 3] = rng.uniform(0.1, 0.14, n).astype(F32)
+    side = 32
+    g = (0.35 + 0.3 * (np.arange(side) + 0.5) / side)
+    rays_h = np.zeros((side * side, 7), F32)
+    rays_h[:, 2] = 1
+    rays_h[:, 3] = np.repeat(g, side).astype(F32); rays_h[:, 4] = np.tile(g, side).astype(F32)
+    rays_h[:, 5] = -0.1; rays_h[:, 6] = 1.2
+    d, tree = _build(gh, cuda, s)
+    sh = d.cpu().numpy()
+    rays = torch.from_numpy(rays_h).to(cuda)
+    rng = np.random.default_rng(9)
+    e = (rng.random((n, 3)) * 4.0 - 2.0).astype(F32)
+    k = (2e-3 * sh[:, 3].astype(F64) ** 2 * 10.0 ** (2.0 * sh[:, 0].astype(F64)) * (0.5 + rng.random(n))).astype(F32)
+    gh.ordered_enable_stats(True)
+    try:
+        gh.set_hits_staging(True)
+        on = _trace(gh, rays, d, tree, e, k)
+        st = gh.ordered_last_stats()
+        assert st["batches"] == 1 and st["total_hits"] / (len(rays) / 64) >= 200_000, "below the staging threshold"
+        gh.set_hits_staging(False)
+        off_ = _trace(gh, rays, d, tree, e, k)
+    finally:
+        gh.set_hits_staging(True)
+    assert np.array_equal(_bits(on[0]), _bits(off_[0])) and np.array_equal(_bits(on[1]), _bits(off_[1]))
+    sub = np.sort(rng.choice(len(rays), 40, replace=False))
+    off, idx, integ, dist = oracle.brute_hits(rays_h[sub], sh)
+    ref, tau, S, n_r = restate(len(sub), off, idx, integ, dist, e, k)
+    check(on[0][sub], on[1][sub], ref, tau, S, n_r, "heavy packets")
 
 
 @pytest.mark.gpu

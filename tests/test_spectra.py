@@ -723,6 +723,29 @@ def test_the_other_ordered_traces_are_left_as_found(gh, sp_scene, cuda):
         assert st_after[key] == st_before[key], key
 
 
+@pytest.mark.gpu
+def test_a_call_whose_rays_hit_nothing(gh, sp_scene, cuda):
+    """No hit in the whole call: every bin and column is +0.0, and the next ordinary call is what
+    it was."""
+    d, tree, sh, sets = sp_scene
+    rays, hits = sets["healpix"]
+    amount, width, vel = _fields(sh, 3, 81, SPAN, signed=True)
+    v0, dv = _grid(96, True, HUBBLE)
+    run = lambda r: _trace(gh, r, d, tree, amount, width, vel, v0, dv, 96, True, HUBBLE)
+    before = run(rays)
+    assert np.count_nonzero(before[0]) > 0
+    away = rays.clone()
+    away[:, 3:6] += 10.0                                                   # length 1, ten box lengths off
+    gh.ordered_enable_stats(True)
+    got, got_col = run(away.contiguous())
+    st = gh.ordered_last_stats()
+    assert st["total_hits"] == 0 and st["batches"] == 1
+    assert not np.any(_bits(got)) and not np.any(_bits(got_col))
+    after = run(rays)
+    assert gh.ordered_last_stats()["total_hits"] == len(hits[1])
+    assert np.array_equal(_bits(after[0]), _bits(before[0])) and np.array_equal(_bits(after[1]), _bits(before[1]))
+
+
 def _fnv1a(a):
     h = 1469598103934665603
     for byte in np.ascontiguousarray(a).tobytes():
