@@ -9,95 +9,4 @@
 
 #include "grace/cuda/trace_sph.cuh"
 
-#include <stdexcept>
-#include <type_traits>
-
-namespace grace {
-
-namespace detail {
-
-template <typename PointType>
-inline int interp_point_elems()
-{
-    static_assert(sizeof(PointType) % sizeof(float) == 0 && sizeof(PointType) >= 3 * sizeof(float)
-                      && sizeof(PointType) <= 16 * sizeof(float),
-                  "interpolate_sph: points are 3..16 floats, x y z first");
-    return int(sizeof(PointType) / sizeof(float));
-}
-
-template <typename Real4>
-inline void interp_check(const thrust::device_vector<Real4>& d_spheres, const float* weights, size_t n_weights,
-                         int n_channels, size_t n_points, size_t n_out)
-{
-    static_assert(std::is_same<Real4, float4>::value, "interpolate_sph: float4 spheres only (float weights and outputs)");
-    if (weights) {
-        if (n_channels < 1 || n_channels > 64)
-            throw std::invalid_argument("interpolate_sph: n_channels must be 1..64");
-        if (n_weights != d_spheres.size() * size_t(n_channels))
-            throw std::invalid_argument("interpolate_sph: d_weights must hold n_channels per sphere");
-        if (n_out != n_points * size_t(n_channels))
-            throw std::invalid_argument("interpolate_sph: d_out must hold n_channels per point");
-    }
-}
-
-} // namespace detail
-
-// d_out[p * n_channels + c] = sum over spheres i containing d_points[p] of fl(d_weights[i * n_channels + c] W_ip).
-template <typename PointType, typename Real4>
-GRACE_HOST void interpolate_sph(const thrust::device_vector<PointType>& d_points,
-                                const thrust::device_vector<Real4>& d_spheres, const Tree& d_tree,
-                                const thrust::device_vector<float>& d_weights, const int n_channels,
-                                thrust::device_vector<float>& d_out)
-{
-    const int elems = detail::interp_point_elems<PointType>();
-    detail::interp_check(d_spheres, detail::raw(d_weights), d_weights.size(), n_channels, d_points.size(), d_out.size());
-    const detail::TreeArgs t = detail::tree_args(d_tree);
-    GRACE_STATUS_CHECK(grace_interpolate_points_f4(
-        reinterpret_cast<const float*>(detail::raw(d_points)), d_points.size(), elems,
-        reinterpret_cast<const float*>(detail::raw(d_spheres)), d_spheres.size(), t.nodes, t.n_nodes, t.leaves,
-        t.root, detail::raw(d_weights), n_channels, detail::raw(d_out), NULL, NULL));
-    detail::check_trace_status();
-}
-
-// ... and d_counts[p] = the number of spheres containing d_points[p].
-template <typename PointType, typename Real4>
-GRACE_HOST void interpolate_sph(const thrust::device_vector<PointType>& d_points,
-                                const thrust::device_vector<Real4>& d_spheres, const Tree& d_tree,
-                                const thrust::device_vector<float>& d_weights, const int n_channels,
-                                thrust::device_vector<float>& d_out, thrust::device_vector<int>& d_counts)
-{
-    const int elems = detail::interp_point_elems<PointType>();
-    detail::interp_check(d_spheres, detail::raw(d_weights), d_weights.size(), n_channels, d_points.size(), d_out.size());
-    if (d_counts.size() != d_points.size())
-        throw std::invalid_argument("interpolate_sph: d_counts must hold one count per point");
-    const detail::TreeArgs t = detail::tree_args(d_tree);
-    GRACE_STATUS_CHECK(grace_interpolate_points_f4(
-        reinterpret_cast<const float*>(detail::raw(d_points)), d_points.size(), elems,
-        reinterpret_cast<const float*>(detail::raw(d_spheres)), d_spheres.size(), t.nodes, t.n_nodes, t.leaves,
-        t.root, detail::raw(d_weights), n_channels, detail::raw(d_out), detail::raw(d_counts), NULL));
-    detail::check_trace_status();
-}
-
-// The lattice p(i, j, k) = origin + i u + j v + k w, 0 <= i < dims.x ...; outputs row-major (k slowest,
-// i fastest), d_out[p * n_channels + c].  dims.z == 1 is a slice.
-template <typename Real4>
-GRACE_HOST void interpolate_grid_sph(const float3 origin, const float3 u, const float3 v, const float3 w,
-                                     const int3 dims, const thrust::device_vector<Real4>& d_spheres,
-                                     const Tree& d_tree, const thrust::device_vector<float>& d_weights,
-                                     const int n_channels, thrust::device_vector<float>& d_out)
-{
-    if (dims.x <= 0 || dims.y <= 0 || dims.z <= 0)
-        throw std::invalid_argument("interpolate_grid_sph: dimensions must be positive");
-    const size_t n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
-    detail::interp_check(d_spheres, detail::raw(d_weights), d_weights.size(), n_channels, n, d_out.size());
-    const float o3[3] = { origin.x, origin.y, origin.z };
-    const float uvw[9] = { u.x, u.y, u.z, v.x, v.y, v.z, w.x, w.y, w.z };
-    const int d3[3] = { dims.x, dims.y, dims.z };
-    const detail::TreeArgs t = detail::tree_args(d_tree);
-    GRACE_STATUS_CHECK(grace_interpolate_grid_f4(
-        o3, uvw, d3, reinterpret_cast<const float*>(detail::raw(d_spheres)), d_spheres.size(), t.nodes, t.n_nodes,
-        t.leaves, t.root, detail::raw(d_weights), n_channels, detail::raw(d_out), NULL, NULL));
-    detail::check_trace_status();
-}
-
-} // namespace grace
+#include "grace/detail/interpolate_sph.h"   // interpolate_sph, interpolate_grid_sph

@@ -13,6 +13,7 @@
 // Any other comparator than less / greater is refused at compile time.
 #pragma once
 
+#include "grace/cuda/build_sph.cuh"
 #include "grace/cuda/nodes.h"
 #include "grace/detail/raw.h"
 #include "grace/error.h"
@@ -105,12 +106,10 @@ GRACE_HOST void compute_deltas(
     typedef typename std::iterator_traits<DeltaIter>::value_type DeltaType;
     if constexpr (std::is_same<DeltaFunc, DeltaXOR>::value && std::is_same<KeyType, uinteger32>::value
                   && std::is_same<DeltaType, uinteger32>::value) {
-        GRACE_STATUS_CHECK(grace_deltas_xor_u32(detail::raw_of(d_keys_iter), N_keys,
-                                                detail::raw_of(d_deltas_iter), NULL));
+        detail::xor_dispatch(detail::raw_of(d_keys_iter), N_keys, detail::raw_of(d_deltas_iter));
     } else if constexpr (std::is_same<DeltaFunc, DeltaXOR>::value && std::is_same<KeyType, uinteger64>::value
                          && std::is_same<DeltaType, uinteger64>::value) {
-        GRACE_STATUS_CHECK(grace_deltas_xor_u64(detail::raw_of(d_keys_iter), N_keys,
-                                                detail::raw_of(d_deltas_iter), NULL));
+        detail::xor_dispatch(detail::raw_of(d_keys_iter), N_keys, detail::raw_of(d_deltas_iter));
     } else {
         detail::deltas_kernel<<<detail::grid_for(N_keys + 1), 256>>>(d_keys_iter, N_keys,
                                                                       d_deltas_iter, delta_func);

@@ -13,6 +13,7 @@
 // over contiguous storage.
 #pragma once
 
+#include "grace/cuda/build_sph.cuh"
 #include "grace/cuda/util/extrema.cuh"
 #include "grace/detail/raw.h"
 #include "grace/error.h"
@@ -54,33 +55,9 @@ inline void compute_centroids(PrimitiveIter d_prims_iter, const size_t n, float3
     GRACE_HIP_CHECK(hipGetLastError());
 }
 
-// (bounds precision, key width) -> the library's key kernel over n float3 points
-inline void point_keys(const float3* c, size_t n, const float* b, const float* t, uinteger32* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys30_points(c, n, 0, 3, b, t, k, NULL)); }
-inline void point_keys(const float3* c, size_t n, const float* b, const float* t, uinteger64* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys63_points(c, n, 0, 3, b, t, k, NULL)); }
-inline void point_keys(const float3* c, size_t n, const double* b, const double* t, uinteger32* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys30_points_d3(c, n, 0, 3, b, t, k, NULL)); }
-inline void point_keys(const float3* c, size_t n, const double* b, const double* t, uinteger64* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys63_points_d3(c, n, 0, 3, b, t, k, NULL)); }
-
-// Spheres with the stock centroid: n records of four floats / doubles, no intermediate array.
-inline void sphere_keys(const float4* s, size_t n, const float* b, const float* t, uinteger32* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys30_f4(&s->x, n, b, t, k, NULL)); }
-inline void sphere_keys(const float4* s, size_t n, const float* b, const float* t, uinteger64* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys63_f4(&s->x, n, b, t, k, NULL)); }
-inline void sphere_keys(const float4* s, size_t n, const double* b, const double* t, uinteger32* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys30_f4_d3(&s->x, n, b, t, k, NULL)); }
-inline void sphere_keys(const float4* s, size_t n, const double* b, const double* t, uinteger64* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys63_f4_d3(&s->x, n, b, t, k, NULL)); }
-inline void sphere_keys(const double4* s, size_t n, const float* b, const float* t, uinteger32* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys30_points(s, n, 1, 4, b, t, k, NULL)); }
-inline void sphere_keys(const double4* s, size_t n, const float* b, const float* t, uinteger64* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys63_points(s, n, 1, 4, b, t, k, NULL)); }
-inline void sphere_keys(const double4* s, size_t n, const double* b, const double* t, uinteger32* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys30_points_d3(s, n, 1, 4, b, t, k, NULL)); }
-inline void sphere_keys(const double4* s, size_t n, const double* b, const double* t, uinteger64* k)
-{ GRACE_STATUS_CHECK(grace_morton_keys63_points_d3(s, n, 1, 4, b, t, k, NULL)); }
+// (point type, bounds precision, key width) -> the library's key kernel: detail::keys_dispatch of
+// build_sph.cuh, over the n float3 centroids or, for spheres with the stock centroid, over the
+// records of four floats / doubles themselves (no intermediate array).
 
 // The key type the library writes for a caller's KeyType: uinteger32 for types up to 32 bits
 // wide, uinteger64 above (morton.cuh:106-108); the caller's type must have that width.
@@ -125,11 +102,11 @@ GRACE_HOST void morton_keys(
 
     if constexpr (detail::is_stock_sphere<typename std::remove_cv<TPrimitive>::type>::value
                   && std::is_same<CentroidFunc, CentroidSphere>::value) {
-        detail::sphere_keys(detail::raw_of(d_prims_iter), N_primitives, bot, top, keys);
+        detail::keys_dispatch(detail::raw_of(d_prims_iter), N_primitives, bot, top, keys);
     } else {
         thrust::device_vector<float3> d_centroids(N_primitives);
         detail::compute_centroids(d_prims_iter, N_primitives, detail::raw(d_centroids), centroid);
-        detail::point_keys(detail::raw(d_centroids), N_primitives, bot, top, keys);
+        detail::keys_dispatch(detail::raw(d_centroids), N_primitives, bot, top, keys);
     }
 }
 
@@ -168,7 +145,7 @@ GRACE_HOST void morton_keys(
     float bot[3], top[3];
     detail::xyz(mins, bot);
     detail::xyz(maxs, top);
-    detail::point_keys(detail::raw(d_centroids), N_primitives, bot, top,
+    detail::keys_dispatch(detail::raw(d_centroids), N_primitives, bot, top,
                        reinterpret_cast<KeyWord*>(detail::raw_of(d_keys_iter)));
 
     if (bots != NULL) *bots = mins;

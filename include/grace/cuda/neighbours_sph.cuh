@@ -7,48 +7,4 @@
 
 #include "grace/cuda/trace_sph.cuh"
 
-#include <stdexcept>
-#include <type_traits>
-
-namespace grace {
-
-// d_indices[p * k + s] / d_d2[p * k + s]: the s-th nearest sphere centre of d_points[p] and its d2
-// (-1 / +inf past the number of spheres or for a non-finite point).  Points are 3..16 floats.
-template <typename PointType, typename Real4>
-GRACE_HOST void nearest_neighbours_sph(const thrust::device_vector<PointType>& d_points,
-                                       const thrust::device_vector<Real4>& d_spheres, const Tree& d_tree,
-                                       const int k, thrust::device_vector<int>& d_indices,
-                                       thrust::device_vector<float>& d_d2)
-{
-    static_assert(std::is_same<Real4, float4>::value, "nearest_neighbours_sph: float4 spheres only");
-    static_assert(sizeof(PointType) % sizeof(float) == 0 && sizeof(PointType) >= 3 * sizeof(float)
-                      && sizeof(PointType) <= 16 * sizeof(float),
-                  "nearest_neighbours_sph: points are 3..16 floats, x y z first");
-    if (k < 1 || k > 64)
-        throw std::invalid_argument("nearest_neighbours_sph: k must be 1..64");
-    if (d_indices.size() != d_points.size() * size_t(k) || d_d2.size() != d_points.size() * size_t(k))
-        throw std::invalid_argument("nearest_neighbours_sph: d_indices and d_d2 must hold k entries per point");
-    const detail::TreeArgs t = detail::tree_args(d_tree);
-    GRACE_STATUS_CHECK(grace_nearest_neighbours_f4(
-        reinterpret_cast<const float*>(detail::raw(d_points)), d_points.size(), int(sizeof(PointType) / sizeof(float)),
-        reinterpret_cast<const float*>(detail::raw(d_spheres)), d_spheres.size(), t.nodes, t.n_nodes, t.leaves,
-        t.root, k, detail::raw(d_indices), detail::raw(d_d2), NULL));
-    detail::check_trace_status();
-}
-
-// d_h[i] = fl(eta * sqrt(d2 of the k-th nearest centre of sphere i's own centre)), tree order.
-template <typename Real4>
-GRACE_HOST void smoothing_lengths_sph(const thrust::device_vector<Real4>& d_spheres, const Tree& d_tree,
-                                      const int k, const float eta, thrust::device_vector<float>& d_h)
-{
-    static_assert(std::is_same<Real4, float4>::value, "smoothing_lengths_sph: float4 spheres only");
-    if (d_h.size() != d_spheres.size())
-        throw std::invalid_argument("smoothing_lengths_sph: d_h must hold one value per sphere");
-    const detail::TreeArgs t = detail::tree_args(d_tree);
-    GRACE_STATUS_CHECK(grace_smoothing_lengths_f4(reinterpret_cast<const float*>(detail::raw(d_spheres)),
-                                                  d_spheres.size(), t.nodes, t.n_nodes, t.leaves, t.root, k, eta,
-                                                  detail::raw(d_h), NULL));
-    detail::check_trace_status();
-}
-
-} // namespace grace
+#include "grace/detail/neighbours_sph.h"   // nearest_neighbours_sph, smoothing_lengths_sph

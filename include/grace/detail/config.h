@@ -2,10 +2,17 @@
 // set (grace/types.h) and by the headers that are also usable from plain host C++
 // (grace/generic/bits.h, morton.h: the reference's host-callable morton_key).  Under hipcc the
 // qualifiers are the reference's (include/grace/types.h:14-32); under a host-only compiler they
-// reduce to `inline`.
+// reduce to `inline`.  GRACE_ASSERT is the reference's debug-build assertion (include/grace/error.h).
 #pragma once
 
+#include <assert.h>
 #include <stdint.h>
+
+#ifdef GRACE_DEBUG
+#define GRACE_ASSERT(...) { assert((__VA_ARGS__)); }
+#else
+#define GRACE_ASSERT(...)
+#endif
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>

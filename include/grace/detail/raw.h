@@ -1,7 +1,9 @@
-// grace/detail/raw.h -- helpers shared by the drop-in headers: raw device pointers of
-// thrust vectors, and compile-time tags for the (Real4, key, delta) types the C ABI covers.
+// grace/detail/raw.h -- helpers shared by the drop-in headers: the container and the raw device
+// pointers the shared API bodies are written against (grace/detail/front_end.h), and compile-time
+// tags for the (Real4, key, delta) types the C ABI covers.
 #pragma once
 
+#include "grace/detail/front_end.h"
 #include "grace/error.h"
 #include "grace/types.h"
 
@@ -9,6 +11,8 @@
 
 namespace grace {
 namespace detail {
+
+template <typename T> using dvec = thrust::device_vector<T>;
 
 template <typename T>
 inline T* raw(thrust::device_vector<T>& v) { return thrust::raw_pointer_cast(v.data()); }
@@ -28,10 +32,6 @@ template <typename Real4> struct is_float4 { static const bool value = false; };
 template <> struct is_float4<float4> { static const bool value = true; };
 template <typename Real4> struct is_double4 { static const bool value = false; };
 template <> struct is_double4<double4> { static const bool value = true; };
-
-// x y z of float3 / double3 / float4 / ... as an array of the component type.
-template <typename Real, typename Vec3>
-inline void xyz(const Vec3& v, Real* out) { out[0] = Real(v.x); out[1] = Real(v.y); out[2] = Real(v.z); }
 
 } // namespace detail
 } // namespace grace

@@ -7,16 +7,9 @@
 #include "grace/types.h"
 #include "grace_hip.h"
 
-#include <assert.h>
 #include <cstdlib>
 #include <iostream>
 #include <stdexcept>
-
-#ifdef GRACE_DEBUG
-#define GRACE_ASSERT(...) { assert((__VA_ARGS__)); }
-#else
-#define GRACE_ASSERT(...)
-#endif
 
 #define GRACE_GOT_TO() std::cerr << "At " << __FILE__ << "@" << __LINE__ << std::endl;
 
