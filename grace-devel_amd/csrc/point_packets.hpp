@@ -1,4 +1,4 @@
-// Pieces shared by the point-packet walks (interpolate.hip, neighbours.hip): Morton keys of points
+// Pieces shared by the point-packet walks (interpolate.hip, neighbours.hip, range.hip): Morton keys of points
 // against the tree's root box, packet starts cut at Morton-cell changes (kernels and the host
 // sequence that runs them), wave reductions and the correctly rounded fp32 sqrt.  Each
 // including translation unit gets its own copies (internal linkage).

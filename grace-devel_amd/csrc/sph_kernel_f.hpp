@@ -1,0 +1,47 @@
+// The built-in SPH kernels' f(q) in fp32, shared by the walks that evaluate W(r, H) = H^-3 f(r / H) at
+// points (interpolate.hip: scatter sums, range.hip: gather sums).  Each including translation unit
+// gets its own copies (internal linkage).
+#pragma once
+
+#include "common.hpp"
+
+#include <cmath>
+
+namespace {
+
+__device__ __forceinline__ float pow4(const float t)
+{
+    const float t2 = t * t;
+    return t2 * t2;
+}
+
+// K = f(q) in the fp32 operation sequence of include/grace_hip.h ("SPH interpolation at points");
+// u = max(1 - q, 0), normalisation constant last.  (-ffp-contract=off: no operation is fused.)
+template <int KIND>
+__device__ __forceinline__ float kernel_f(const float q)
+{
+    const float u = fmaxf(1.0f - q, 0.0f);
+    if constexpr (KIND == GRACE_SPH_KERNEL_CUBIC) {
+        const float inner = ((6.0f * q - 6.0f) * (q * q)) + 1.0f;
+        const float outer = 2.0f * ((u * u) * u);
+        return (q < 0.5f ? inner : outer) * float(8.0 / M_PI);
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_QUARTIC) {
+        const float t2 = fmaxf(u - 0.4f, 0.0f), t3 = fmaxf(u - 0.8f, 0.0f);
+        return ((pow4(u) - 5.0f * pow4(t2)) + 10.0f * pow4(t3)) * float(25.0 * 39.0625 / (32.0 * M_PI));
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_QUINTIC) {
+        const float t2 = fmaxf(u - float(1.0 / 3.0), 0.0f), t3 = fmaxf(u - float(2.0 / 3.0), 0.0f);
+        return ((pow4(u) * u - 6.0f * (pow4(t2) * t2)) + 15.0f * (pow4(t3) * t3))
+            * float(9.0 * 243.0 / (40.0 * M_PI));
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_WENDLAND_C2) {
+        return (pow4(u) * (4.0f * q + 1.0f)) * float(21.0 / (2.0 * M_PI));
+    } else if constexpr (KIND == GRACE_SPH_KERNEL_WENDLAND_C4) {
+        const float u6 = pow4(u) * (u * u);
+        return (u6 * (q * (q * float(35.0 / 3.0) + 6.0f) + 1.0f)) * float(495.0 / (32.0 * M_PI));
+    } else {
+        static_assert(KIND == GRACE_SPH_KERNEL_WENDLAND_C6, "built-in SPH kernels only");
+        const float u4 = pow4(u);
+        return ((u4 * u4) * (q * (q * (32.0f * q + 25.0f) + 8.0f) + 1.0f)) * float(1365.0 / (64.0 * M_PI));
+    }
+}
+
+} // namespace

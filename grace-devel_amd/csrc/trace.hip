@@ -1068,6 +1068,9 @@ grace_status grace_trace_status(grace_stream stream)
     GRACE_TRY_HIP(hipStreamSynchronize(as_stream(stream)));
     if (h != 0) {
         GRACE_TRY_HIP(hipMemsetAsync(ts.status, 0, sizeof(int), as_stream(stream)));
+        if (h == GRACE_INVALID_ARGUMENT)
+            return set_error(GRACE_INVALID_ARGUMENT, __FILE__, __LINE__,
+                             "range_neighbours: a row of d_offsets does not have the length of its list");
         return set_error(GRACE_STACK_OVERFLOW, __FILE__, __LINE__,
                          "trace: packet stack (128 entries) exhausted");
     }

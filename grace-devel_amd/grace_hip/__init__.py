@@ -867,6 +867,70 @@ def neighbours_last_stats():
 INT32_MAX = 2 ** 31 - 1
 
 
+def _range_args(points, radii):
+    """points and radii of a range query -> (points, radii tensor or None, scalar radius)."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    if torch.is_tensor(radii):
+        if radii.dtype != torch.float32 or tuple(radii.shape) != (len(points),):
+            raise ValueError("radii must be a float or float32 of shape [%d]" % len(points))
+        return points, radii.contiguous(), 0.0
+    return points, None, float(radii)
+
+
+def range_counts_sph(points, radii, spheres, tree, weights=None, counts=None, out=None, check=False):
+    """Every sphere centre within the query point's own radius (an extension the reference lacks):
+    sphere j is in range of point p iff d2 <= fl(r_p * r_p), d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz))
+    in fp32 -- inclusive; the spheres' w is ignored.  counts[p] = the number of spheres in range, and
+    with weights the gather form of the SPH sum,
+    sums[p, c] = sum over in-range j, ascending, of fl32(weights[j, c] * W(|x_p - x_j|, r_p)),
+    a plain fp32 running sum with the context's SPH kernel (set_sph_kernel; a custom table is refused),
+    0 where r_p == 0.  weights = m gives the density at the smoothing length r_p.
+    points: float32 [n, 3..16] (x y z first); radii: a float, or float32 [n] in the order of points;
+    weights: float32 [n_spheres] or [n_spheres, C] (1 <= C <= 64) in the order of `spheres` (tree order:
+    build_tree(want_perm=True)).  A point with a non-finite coordinate or a negative, NaN or infinite
+    radius gets 0.  Returns (counts int32 [n], sums float32 [n] / [n, C] or None without weights)."""
+    points, rt, rs = _range_args(points, radii)
+    n = len(points)
+    if counts is None:
+        counts = torch.empty(n, dtype=torch.int32, device=points.device)
+    n_ch, out, counts = _interp_outputs(n, len(spheres), weights, out, counts, points.device)
+    if weights is not None:
+        weights = weights.contiguous()
+    _check(_lib.grace_range_counts_f4(_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]), _ptr(rt), C.c_float(rs),
+                                      *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
+                                      _ptr(counts), _ptr(out), _stream()))
+    if check:
+        trace_status()
+    return counts, out
+
+
+def range_neighbours_sph(points, radii, spheres, tree, want_d2=True, check=False):
+    """The neighbour lists of range_counts_sph in CSR form: row p is [offsets[p], offsets[p + 1]) of
+    indices (tree indices, ascending) and d2 (their fp32 squared distances).  Counts, the library's
+    scan, then the fill; synchronises to read the total.  ValueError if the lists hold more than
+    INT32_MAX entries (split the points).  Returns (offsets int32 [n + 1], indices int32 [total],
+    d2 float32 [total] or None)."""
+    points, rt, rs = _range_args(points, radii)
+    n = len(points)
+    offsets = torch.zeros(n + 1, dtype=torch.int32, device=points.device)
+    args = (_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]), _ptr(rt), C.c_float(rs),
+            *_interp_scene(spheres, tree))
+    _check(_lib.grace_range_counts_f4(*args, _ptr(None), C.c_int(0), _ptr(offsets), _ptr(None), _stream()))
+    total = exclusive_scan(offsets, offsets)
+    if total > INT32_MAX:
+        raise ValueError("range_neighbours_sph: %d list entries exceed INT32_MAX; the int offsets cannot "
+                         "address them. Split the points into several calls." % total)
+    indices = torch.empty(total, dtype=torch.int32, device=points.device)
+    d2 = torch.empty(total, dtype=torch.float32, device=points.device) if want_d2 else None
+    if total:                  # (no list entries: every row is empty, nothing to fill)
+        _check(_lib.grace_range_neighbours_f4(*args, _ptr(offsets), _ptr(indices), _ptr(d2), _stream()))
+    if check:
+        trace_status()
+    return offsets, indices, d2
+
+
 def _offsets_from_counts(offsets, extra=0):
     """Hit counts -> exclusive offsets in place; returns the total (64-bit).  int offsets cannot
     address more than INT32_MAX per-hit slots: ValueError (std::invalid_argument in the C++

@@ -591,7 +591,8 @@ grace_status grace_trace_set_cache_auto(int enabled);
 
 /* Reads (and clears) the traversal status word: GRACE_STACK_OVERFLOW if any packet ran out
  * of its 128-entry stack since the last check (the reference only asserts this in
- * GRACE_DEBUG builds, bintree_trace.cuh:164).  Synchronises. */
+ * GRACE_DEBUG builds, bintree_trace.cuh:164); GRACE_INVALID_ARGUMENT if grace_range_neighbours_f4
+ * met a row of another length than its list.  Synchronises. */
 grace_status grace_trace_status(grace_stream stream);
 
 /* ---- scans ---------------------------------------------------------------------------
@@ -881,6 +882,68 @@ grace_status grace_smoothing_lengths_f4(const float* d_spheres, size_t n_spheres
 grace_status grace_neighbours_enable_stats(int enabled);
 grace_status grace_neighbours_last_stats(unsigned long long* h_candidate_tests, unsigned long long* h_packets,
                                          unsigned long long* h_insertion_steps);
+
+/* ---- Range queries (an extension the reference lacks) ------------------------------------------
+ * Every sphere centre within a radius that belongs to the QUERY POINT: counts, CSR neighbour lists
+ * (any length) and the gather form of the SPH sum, rho_p = sum_j m_j W(|x_p - x_j|, h_p).
+ * (grace_interpolate_points_f4 is the scatter form: the spheres whose own H contains the point.)
+ *
+ * Distance (fp32, every operation rounded, none fused), per point p and sphere j (centre x_j; its w
+ * is ignored):  d = p - x per component;  d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz))
+ * (the neighbours' sequence).
+ * Radius: r_p = d_radii[p], in the caller's point order, or `radius` for every point if d_radii is
+ * NULL;  R2_p = fl(r_p * r_p).  Sphere j is in range of point p iff d2 <= R2_p -- inclusive, so
+ * r = 0 finds coincident centres, and a query point that is a sphere centre finds itself.
+ * Off points: a point with a non-finite coordinate, or whose r_p is negative, NaN or +inf, is off:
+ * count 0, sums 0, an empty row.
+ * The result is a function of point, radius and scene only: not of the point order,
+ * elems_per_point, the spheres' w or the H the tree was built with (any H >= 0), max_per_leaf, the
+ * trace's knobs or caches; counts and lists do not depend on the SPH kernel either.
+ * Points: n_points records of elems_per_point (3..16) floats, x y z first, as for
+ * grace_interpolate_points_f4; outputs in the caller's order.
+ *
+ * grace_range_counts_f4:  d_counts[p] = the number of spheres in range (or NULL), and, if d_sums is
+ * given (needs d_weights and 1 <= n_channels <= 64; weights in tree order, read on every call),
+ *   d_sums[p * n_channels + c] = sum over the spheres j in range, ascending j, of
+ *                                fl32(d_weights[j * n_channels + c] * W_pj),
+ * a plain fp32 running sum from 0 (no summation classes), with W_pj the arithmetic of "SPH
+ * interpolation at points" above with H := r_p:  ih = fl(1 / r_p);  q = fl(sqrt_rn(d2) * ih);
+ * K = f(q) in the fp32 forms of the context's SPH kernel;  W = fl(K * fl(fl(ih * ih) * ih));
+ * term_c = fl(w_c * W).  The sums are 0 where r_p == 0.  A custom SPH kernel table is refused when
+ * sums are requested (there is no f(q)).  Channels are walked four at a time.
+ *
+ * grace_range_neighbours_f4:  row p occupies [d_offsets[p], d_offsets[p + 1]); d_offsets has
+ * n_points + 1 int entries, the exclusive scan of the counts (grace_scan_exclusive_i32 over
+ * n_points + 1 entries whose last is 0).  The row holds the spheres in range in ascending tree
+ * index in d_indices, their d2 in d_d2; either may be NULL, not both.  The fill never writes
+ * outside its row: a row whose length differs from the number of spheres found sets the status word
+ * of grace_trace_status, which then returns GRACE_INVALID_ARGUMENT (too short: the row is
+ * truncated; too long: its tail is left untouched).
+ *
+ * GRACE_INVALID_ARGUMENT, nothing written: elems_per_point outside 3..16, a bad channel count,
+ * sums without weights, no output at all, a bad scene (including n_spheres == 0), a scalar radius
+ * that is negative or non-finite when d_radii is NULL, a custom kernel table with sums.  Zero
+ * points: GRACE_OK, nothing written (elems_per_point, the channel arguments and n_points are
+ * checked first, the rest after).  The tree's leaves must cover exactly [0, n_spheres), as
+ * build_tree and build_ALBVH give; node boxes built with any H >= 0 contain the centres.  A packet
+ * that exhausts its 128-entry stack sets the status word of grace_trace_status
+ * (GRACE_STACK_OVERFLOW); nothing is written out of bounds.  Stream-ordered, no host
+ * synchronisation, no allocation (the context workspace): capturable.  grace_trace_enable_timing /
+ * grace_trace_last_kernel_ms time the walks of the last call.
+ * Not provided: symmetric criteria (max(h_p, H_j)), periodic boxes, double4 spheres, 64-bit
+ * offsets (split the points when the lists exceed INT32_MAX entries). */
+grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                   const float* d_radii, float radius,
+                                   const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                   size_t n_nodes, const int* d_leaves, const int* d_root,
+                                   const float* d_weights, int n_channels,
+                                   int* d_counts, float* d_sums, grace_stream stream);
+grace_status grace_range_neighbours_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                       const float* d_radii, float radius,
+                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                       size_t n_nodes, const int* d_leaves, const int* d_root,
+                                       const int* d_offsets, int* d_indices, float* d_d2,
+                                       grace_stream stream);
 
 #ifdef __cplusplus
 }
