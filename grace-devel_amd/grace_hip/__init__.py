@@ -931,6 +931,55 @@ def range_neighbours_sph(points, radii, spheres, tree, want_d2=True, check=False
     return offsets, indices, d2
 
 
+def fof_labels_sph(spheres, tree, linking_length, labels=None, check=False):
+    """Friends-of-friends groups (an extension the reference lacks): spheres i and j (tree order; their
+    w is ignored) are linked iff d2 <= fl(b * b), b the linking length,
+    d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in fp32 -- inclusive, so b = 0 links coincident
+    centres; groups are the connected components.  labels[i] = the smallest tree index in i's group:
+    a function of the positions and b alone, bit-identical from run to run.  A sphere with a
+    non-finite coordinate is a group of one.  Returns labels int32 [n] (tree order: map them to the
+    caller's particles with the permutation of build_tree(want_perm=True))."""
+    n = len(_spheres(spheres))
+    if labels is None:
+        labels = torch.empty(n, dtype=torch.int32, device=spheres.device)
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise ValueError("labels must be int32 of shape [%d]" % n)
+    _check(_lib.grace_fof_labels_f4(*_interp_scene(spheres, tree), C.c_float(float(linking_length)), _ptr(labels),
+                                    _stream()))
+    if check:
+        trace_status()
+    return labels
+
+
+def fof_groups_sph(labels, min_members=1, want_members=True):
+    """The catalogue of fof_labels_sph's labels: groups of at least min_members members, numbered in
+    ascending label.  group_of[i] = sphere i's group or -1; sizes[g] = its member count; with
+    want_members the CSR lists: row g is [offsets[g], offsets[g + 1]) of members, tree indices in
+    ascending order.  Ordering by size is one argsort of sizes.  Synchronises once, to read the
+    number of groups.  Returns (group_of int32 [n], sizes int32 [n_groups], offsets int32
+    [n_groups + 1], members int32 [members of kept groups]); offsets and members are None without
+    want_members."""
+    if labels.dtype != torch.int32 or labels.dim() != 1:
+        raise ValueError("labels must be int32 of shape [n]")
+    labels = labels.contiguous()
+    n = len(labels)
+    dev = labels.device
+    group_of = torch.empty(n, dtype=torch.int32, device=dev)
+    sizes = torch.empty(n, dtype=torch.int32, device=dev)
+    n_groups = torch.zeros(2, dtype=torch.int32, device=dev)     # {groups, members of kept groups}
+    _check(_lib.grace_fof_groups(_ptr(labels), C.c_size_t(n), C.c_int(int(min_members)), _ptr(group_of),
+                                 _ptr(sizes), _ptr(n_groups), _stream()))
+    ng, nm = (int(v) for v in n_groups.tolist())
+    sizes = sizes[:ng]
+    if not want_members:
+        return group_of, sizes, None, None
+    offsets = torch.zeros(ng + 1, dtype=torch.int32, device=dev)
+    members = torch.empty(nm, dtype=torch.int32, device=dev)
+    _check(_lib.grace_fof_members(_ptr(group_of), C.c_size_t(n), _ptr(sizes), C.c_size_t(ng), _ptr(offsets),
+                                  _ptr(members), _stream()))
+    return group_of, sizes, offsets, members
+
+
 def _offsets_from_counts(offsets, extra=0):
     """Hit counts -> exclusive offsets in place; returns the total (64-bit).  int offsets cannot
     address more than INT32_MAX per-hit slots: ValueError (std::invalid_argument in the C++

@@ -945,6 +945,65 @@ grace_status grace_range_neighbours_f4(const float* d_points, size_t n_points, i
                                        const int* d_offsets, int* d_indices, float* d_d2,
                                        grace_stream stream);
 
+/* ---- Friends-of-friends groups (an extension the reference lacks) ------------------------------
+ * Which spheres form a clump: the connected components of the graph that links every two sphere
+ * centres within one linking length, as a label per sphere, and a catalogue (group numbers, sizes,
+ * member lists) built from the labels.  The pair list is never formed: each link is consumed by a
+ * concurrent union-find as the walk of the range queries finds it (4 n bytes in all: the labels).
+ *
+ * Link: spheres i and j, in tree order (centres x; their w is ignored), are linked iff d2(i, j) <= B2,
+ * B2 = fl(b * b), b = linking_length, with the range queries' fp32 distance
+ * d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), d = x_i - x_j per component -- inclusive, so b = 0
+ * links coincident centres.  d2 is symmetric: fp32 subtraction is exactly antisymmetric and the rest
+ * is the same operations on equal squares, so the link graph is undirected.  A sphere with a
+ * non-finite coordinate links to nothing and is a group of one.
+ * Groups are the connected components of that graph.
+ *
+ * grace_fof_labels_f4 (the reference has no counterpart):  d_labels[i] = the smallest tree index in
+ * i's group (n_spheres ints), so labels[i] <= i and labels[labels[i]] == labels[i].  The labelling
+ * is a function of the positions and b alone: not of the H the tree was built with (any H >= 0), of
+ * max_per_leaf, of the packets or of which wave won which race of the union-find; every output of
+ * these three functions is bit-identical from run to run.
+ * GRACE_INVALID_ARGUMENT, nothing written: a negative, NaN or infinite linking_length, more than
+ * INT32_MAX spheres, null d_labels or a bad scene (checked in this order, before any launch).
+ * n_spheres == 0: GRACE_OK, nothing written (checked after the linking length).  The tree's leaves
+ * must cover exactly [0, n_spheres), as build_tree and build_ALBVH give.  A packet that exhausts
+ * its 128-entry stack sets the status word of grace_trace_status (GRACE_STACK_OVERFLOW).
+ * grace_trace_enable_timing / grace_trace_last_kernel_ms time the link and flatten kernels.
+ *
+ * grace_fof_groups (the reference has no counterpart):  the catalogue of labels as above (n ints;
+ * a label outside [0, n) belongs to no group).  Kept groups are those with at least min_members
+ * members (min_members >= 1), numbered 0 .. n_groups - 1 in ascending label.
+ *   d_group_of[i] = the number of i's group, or -1 in a group that was not kept (n ints);
+ *   d_sizes[g]    = the member count of group g (capacity n; entries from n_groups on are untouched);
+ *   d_n_groups    = two device ints: {n_groups, the number of spheres in kept groups}.
+ * GRACE_INVALID_ARGUMENT, nothing written: min_members < 1, n > INT32_MAX, a null pointer.
+ * n == 0: GRACE_OK, nothing written.
+ *
+ * grace_fof_members (the reference has no counterpart):  the member lists in CSR form from
+ * d_group_of and the first n_groups entries of d_sizes (the host's copy of the count):
+ *   d_offsets[0 .. n_groups] = the exclusive scan of the sizes and their total;
+ *   d_members: row g is [d_offsets[g], d_offsets[g + 1]), the tree indices of group g's members in
+ *   ascending order; it needs d_offsets[n_groups] entries, the second word of d_n_groups (n always
+ *   suffices).  The stable grace_sort_pairs_u32 order of the indices keyed on group_of, over the
+ *   bits n_groups needs.
+ * GRACE_INVALID_ARGUMENT, nothing written: n > INT32_MAX, n_groups > n, a null pointer (d_sizes and
+ * d_members may be null when n_groups == 0, which writes d_offsets[0] = 0 only).  n == 0: GRACE_OK,
+ * nothing written.
+ *
+ * All three are stream-ordered, without host synchronisation or allocation (the context
+ * workspace): capturable.
+ * Not provided: periodic boxes, per-particle linking lengths, double4 spheres, more than INT32_MAX
+ * spheres, unbinding or sub-halo finding, groups ordered by size (one argsort of d_sizes by the
+ * caller). */
+grace_status grace_fof_labels_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                 size_t n_nodes, const int* d_leaves, const int* d_root,
+                                 float linking_length, int* d_labels, grace_stream stream);
+grace_status grace_fof_groups(const int* d_labels, size_t n, int min_members, int* d_group_of,
+                              int* d_sizes, int* d_n_groups, grace_stream stream);
+grace_status grace_fof_members(const int* d_group_of, size_t n, const int* d_sizes, size_t n_groups,
+                               int* d_offsets, int* d_members, grace_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
