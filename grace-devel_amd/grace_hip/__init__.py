@@ -980,6 +980,74 @@ def fof_groups_sph(labels, min_members=1, want_members=True):
     return group_of, sizes, offsets, members
 
 
+def _pair_edges(edges):
+    """The edges of a pair count -> a host float32 array (the library checks their values)."""
+    if torch.is_tensor(edges):
+        edges = edges.detach().cpu().numpy()
+    edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float32).reshape(-1))
+    if not 1 <= len(edges) <= 64:
+        raise ValueError("edges must hold 1..64 values")
+    return edges
+
+
+def _pair_call(points, edges, spheres, tree, weights, n_ch, totals, counts, sums, check):
+    _check(_lib.grace_pair_counts_f4(_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
+                                     edges.ctypes.data_as(C.c_void_p), C.c_int(len(edges)),
+                                     *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
+                                     _ptr(totals), _ptr(counts), _ptr(sums), _stream()))
+    if check:
+        trace_status()
+
+
+def pair_counts_sph(points, edges, spheres, tree, check=False):
+    """Pair counts in separation bins (an extension the reference lacks): totals[k] = the number of
+    (point, sphere) pairs whose d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) (fp32) falls in bin k,
+    the smallest k with d2 <= fl(e_k * e_k) -- bin 0 holds d2 <= fl(e_0 e_0) (with e_0 = 0 the
+    coincident and self pairs), bin k >= 1 holds fl(e_{k-1} e_{k-1}) < d2 <= fl(e_k e_k), pairs beyond
+    the last edge are in no bin; the spheres' w is ignored.  One walk at the last edge, exact 64-bit
+    integer totals.  Pairs are ordered: with the sphere centres as points every unordered pair is
+    counted twice and every self pair once, so DD = (totals - [n, 0, 0, ...]) // 2.
+    points: float32 [n, 3..16] (x y z first); edges: 1..64 floats (a sequence, array or tensor; read on
+    the host), finite, not negative, strictly ascending.  A point with a non-finite coordinate is in
+    no pair.  Returns totals uint64 [n_edges]."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    edges = _pair_edges(edges)
+    totals = torch.empty(len(edges), dtype=torch.uint64, device=points.device)
+    _pair_call(points, edges, spheres, tree, None, 0, totals, None, None, check)
+    return totals
+
+
+def radial_profiles_sph(points, edges, spheres, tree, weights=None, check=False):
+    """The per-point form of pair_counts_sph: counts[p, k] = the number of sphere centres in bin k of
+    point p, and with weights sums[p, k, c] = the sum of weights[j, c] over those spheres in ascending
+    tree index j, a plain fp32 running sum (no SPH kernel): counts and mass in shells around each point;
+    the cumulative profile is a cumsum over k.  counts.cumsum(1)[:, k] is range_counts_sph at radius
+    e_k.  weights: float32 [n_spheres] or [n_spheres, C], 1 <= C <= 4 and n_edges * C <= 64, in the
+    order of `spheres` (tree order: build_tree(want_perm=True)).  A point with a non-finite coordinate
+    gets zeros.  Returns (counts int32 [n, n_edges], sums float32 [n, n_edges] / [n, n_edges, C] or None
+    without weights)."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    edges = _pair_edges(edges)
+    n, ne = len(points), len(edges)
+    counts = torch.empty((n, ne), dtype=torch.int32, device=points.device)
+    n_ch, sums = 0, None
+    if weights is not None:
+        if weights.dtype != torch.float32 or weights.dim() not in (1, 2) or len(weights) != len(spheres):
+            raise ValueError("weights must be float32 of shape [n_spheres] or [n_spheres, C]")
+        n_ch = 1 if weights.dim() == 1 else int(weights.shape[1])
+        if not 1 <= n_ch <= 4 or ne * n_ch > 64:
+            raise ValueError("weights must hold 1..4 channels and n_edges * channels must not exceed 64")
+        weights = weights.contiguous()
+        sums = torch.empty((n, ne) if weights.dim() == 1 else (n, ne, n_ch), dtype=torch.float32,
+                           device=points.device)
+    _pair_call(points, edges, spheres, tree, weights, n_ch, None, counts, sums, check)
+    return counts, sums
+
+
 def _offsets_from_counts(offsets, extra=0):
     """Hit counts -> exclusive offsets in place; returns the total (64-bit).  int offsets cannot
     address more than INT32_MAX per-hit slots: ValueError (std::invalid_argument in the C++

@@ -1004,6 +1004,64 @@ grace_status grace_fof_groups(const int* d_labels, size_t n, int min_members, in
 grace_status grace_fof_members(const int* d_group_of, size_t n, const int* d_sizes, size_t n_groups,
                                int* d_offsets, int* d_members, grace_stream stream);
 
+/* ---- Pair counts in separation bins and radial profiles (an extension the reference lacks) -----
+ * How many sphere centres lie in each shell of separation around each query point: the totals over
+ * all points (the pair counts DD(r) behind a two-point correlation function), the per-point
+ * histograms, and the per-point sums of weights per shell (counts and mass in shells around chosen
+ * centres, such as those of the groups grace_fof_groups has found).  One walk of the range queries
+ * at the outermost edge; each pair is binned where the walk finds it, no list is formed.
+ *
+ * Distance: the range queries' fp32 sequence d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)),
+ * d = p - x per component, every operation rounded, none fused; the spheres' w is ignored.
+ * Points: n_points records of elems_per_point (3..16) floats, x y z first, as for
+ * grace_range_counts_f4; outputs in the caller's point order.
+ * Edges: h_edges is a HOST array of n_edges floats, 1 <= n_edges <= 64, every edge finite and >= 0,
+ * strictly ascending.  It is read at call time and travels in the kernel arguments: no device copy,
+ * no host synchronisation.  E2_k = fl(e_k * e_k).
+ * Bin: the bin of a pair is the smallest k with d2 <= E2_k; a pair with d2 > E2_{n_edges-1}, or a
+ * NaN d2, is in no bin.  So bin 0 holds d2 <= E2_0 -- with e_0 = 0 exactly the coincident and self
+ * pairs -- and bin k >= 1 holds E2_{k-1} < d2 <= E2_k.  The sum over bins 0..k is the count of
+ * grace_range_counts_f4 at radius e_k, by construction.  Where E2_{k-1} == E2_k (small edges whose
+ * squares underflow) bin k is empty.
+ * Off points: a point with a non-finite coordinate is in no pair; its rows are 0.
+ *
+ * Outputs, each may be NULL, not all of them:
+ *   d_totals[k]  (n_edges 64-bit unsigned): the number of (point, sphere) pairs in bin k over all
+ *     points.  Overwritten by the call; accumulated with 64-bit integer atomics only, so exact and
+ *     independent of order.  Pairs are ORDERED pairs: when the points are the sphere centres
+ *     themselves every unordered pair is counted twice and every self pair once (d2 = 0: bin 0), so
+ *     DD_k = (d_totals[k] - (k == 0 ? n : 0)) / 2.
+ *   d_counts[p * n_edges + k]  (int): point p's histogram.
+ *   d_sums[(p * n_edges + k) * n_channels + c]  (float): the sum of d_weights[j * n_channels + c] over
+ *     the spheres j of point p in bin k, in ascending tree index j, a plain fp32 running sum from 0
+ *     (no SPH kernel in it): the mass in each shell; the cumulative profile is the caller's prefix
+ *     sum.  Needs d_weights (tree order, read on every call), 1 <= n_channels <= 4 and
+ *     n_edges * n_channels <= 64.
+ * The result is a function of the points, the edges, the centres and the weights only: not of the
+ * point order, elems_per_point, the H the tree was built with (any H >= 0), max_per_leaf, the SPH
+ * kernel or the trace's knobs; every output is bit-identical from run to run.
+ *
+ * GRACE_INVALID_ARGUMENT, nothing written: elems_per_point outside 3..16, n_edges outside 1..64, a
+ * null h_edges, an edge that is negative, non-finite or not above the one before it, sums with a
+ * channel count outside 1..4, with n_edges * n_channels > 64 or without weights, no output at all,
+ * a bad scene (including n_spheres == 0).  Zero points: GRACE_OK, and d_totals, if given, is zeroed
+ * (elems_per_point, n_points, the edges and the channel arguments are checked first, the rest
+ * after).  The tree's leaves must cover exactly [0, n_spheres), as build_tree and build_ALBVH give.
+ * A packet that exhausts its 128-entry stack sets the status word of grace_trace_status
+ * (GRACE_STACK_OVERFLOW); nothing is written out of bounds.  Stream-ordered, no host
+ * synchronisation, no allocation (the context workspace): capturable.  grace_trace_enable_timing /
+ * grace_trace_last_kernel_ms time the walk of the last call.
+ * Not provided: periodic boxes, double4 spheres, weighted totals (sum d_sums in fp64), halving the
+ * work for auto-pairs (points that are the centres are walked from both ends), estimators
+ * (Landy-Szalay, xi(r)), per-point edge lists. */
+grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                  const float* h_edges, int n_edges,
+                                  const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                  size_t n_nodes, const int* d_leaves, const int* d_root,
+                                  const float* d_weights, int n_channels,
+                                  unsigned long long* d_totals, int* d_counts, float* d_sums,
+                                  grace_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
