@@ -923,13 +923,23 @@ void trace_kernel(const TraceArgs a)
             // node count, no gain each time (2.91 vs 2.92 ms).  The ~100 node tests per packet are a
             // chain of dependent loads; their vector work is not what the walk waits for.)
             bool hit_l, hit_r;
-            if constexpr (fp64(MODE)) {
+            if constexpr (fp64(MODE) || MODE == MODE_TRI) {
                 // The fp64 tests accept spheres the float node boxes need not contain: double4
                 // centres +- radii are narrowed to the nearest float (the corner can move inward by
                 // half an ulp: a tangent hit of a sphere with h ~ ulp(|c|) falls outside its box),
                 // and the fp64 test of float4 spheres admits |s - o| up to h (1 + 2^-23) per
                 // co-ordinate.  Both lie within 2^-21 (|lo| + |hi|) of the box (>= 2^-21 max(|c|, h)),
                 // the cluster boxes' slack.
+                // Triangles: TriangleAABB's corners are the FLOAT sums fl(v + e1), fl(v + e2), up to
+                // half an ulp inside the corners v + e of the triangle Moeller-Trumbore tests (it works
+                // on v, e1, e2 themselves), and the test accepts u, v, u + v that ROUND to 0 or 1,
+                // i.e. points up to 2^-24 |e| beyond an edge.  A ray in the plane of a box face, or
+                // that little outside it, passes the triangle test and failed the slab test (found
+                // by tests/test_triangle_boundaries.py: an axis-aligned ray along the edge u + v = 1,
+                // the walk alone deciding).  Both effects are below 2^-23 (|lo| + |hi|) per
+                // co-ordinate (|e_k| <= hi_k - lo_k); the same 2^-21 keeps a factor of four.
+                // (Not covered, here as in the reference: the error of o - v for an origin much
+                // farther from the box than the box is from zero, which the slab products share.)
                 auto widen = [](const float4 b) {   // {lo, hi, lo, hi}
                     const float s0 = (fabsf(b.x) + fabsf(b.y)) * 4.76837158203125e-07f;   // 2^-21
                     const float s1 = (fabsf(b.z) + fabsf(b.w)) * 4.76837158203125e-07f;

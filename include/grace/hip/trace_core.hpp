@@ -24,6 +24,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -69,15 +70,24 @@ __device__ __forceinline__ int AABBs_hit(const float ix, const float iy, const f
     const float bzL = (Z.x - oz) * iz, tzL = (Z.y - oz) * iz;
     const float bxR = (R.x - ox) * ix, txR = (R.y - ox) * ix, byR = (R.z - oy) * iy, tyR = (R.w - oy) * iy;
     const float bzR = (Z.z - oz) * iz, tzR = (Z.w - oz) * iz;
+    // A ray in the plane of a slab's face (zero direction component: 1/d = +-inf; face == origin)
+    // makes that face's product 0 * inf = NaN; the reference's min / max then keep the other face's
+    // +-inf and reject a box the ray touches, although the primitive inside it can still be hit
+    // (a ray along a shared edge or through a vertex of an axis-aligned mesh: found by
+    // tests/test_triangle_boundaries.py).  Such a ray lies in the closed slab, so a NaN counts as
+    // -inf for the entry and +inf for the exit, as in the library's own walk (conservative: more
+    // node visits at most; every hit is still decided by the caller's intersect functor).
+    auto en = [](const float t) { return t != t ? -INFINITY : t; };
+    auto ex = [](const float t) { return t != t ? INFINITY : t; };
     const int zero = __float_as_int(0.0f), il = __float_as_int(len);
-    const int tminL = imax_(imax_(__float_as_int(fminf(bxL, txL)), __float_as_int(fminf(byL, tyL))),
-                            imax_(imin_(__float_as_int(bzL), __float_as_int(tzL)), zero));
-    const int tmaxL = imin_(imin_(__float_as_int(fmaxf(bxL, txL)), __float_as_int(fmaxf(byL, tyL))),
-                            imin_(imax_(__float_as_int(bzL), __float_as_int(tzL)), il));
-    const int tminR = imax_(imax_(__float_as_int(fminf(bxR, txR)), __float_as_int(fminf(byR, tyR))),
-                            imax_(imin_(__float_as_int(bzR), __float_as_int(tzR)), zero));
-    const int tmaxR = imin_(imin_(__float_as_int(fmaxf(bxR, txR)), __float_as_int(fmaxf(byR, tyR))),
-                            imin_(imax_(__float_as_int(bzR), __float_as_int(tzR)), il));
+    const int tminL = imax_(imax_(__float_as_int(fminf(en(bxL), en(txL))), __float_as_int(fminf(en(byL), en(tyL)))),
+                            imax_(imin_(__float_as_int(en(bzL)), __float_as_int(en(tzL))), zero));
+    const int tmaxL = imin_(imin_(__float_as_int(fmaxf(ex(bxL), ex(txL))), __float_as_int(fmaxf(ex(byL), ex(tyL)))),
+                            imin_(imax_(__float_as_int(ex(bzL)), __float_as_int(ex(tzL))), il));
+    const int tminR = imax_(imax_(__float_as_int(fminf(en(bxR), en(txR))), __float_as_int(fminf(en(byR), en(tyR)))),
+                            imax_(imin_(__float_as_int(en(bzR)), __float_as_int(en(tzR))), zero));
+    const int tmaxR = imin_(imin_(__float_as_int(fmaxf(ex(bxR), ex(txR))), __float_as_int(fmaxf(ex(byR), ex(tyR)))),
+                            imin_(imax_(__float_as_int(ex(bzR)), __float_as_int(ex(tzR))), il));
     return int(__int_as_float(tmaxR) >= __int_as_float(tminR))
          + 2 * int(__int_as_float(tmaxL) >= __int_as_float(tminL));
 }

@@ -926,6 +926,34 @@ static inline int tri_intersect(const go_ray* ray, const go_tri* tri, float* t)
 
 int go_tri_intersect(const go_ray* ray, const go_tri* tri, float* t) { return tri_intersect(ray, tri, t); }
 
+/* tri_intersect on n (ray, triangle) PAIRS, with its intermediates: the accept flag and det, u, v,
+ * t exactly as tri_intersect computes them; a value after the early return that rejects the pair
+ * is NaN (tri_intersect never computes it). */
+void go_tri_intersect_pairs(const go_ray* rays, const go_tri* tris, size_t n, int* hit, float* det_out,
+                            float* u_out, float* v_out, float* t_out)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const go_ray* ray = &rays[i]; const go_tri* tri = &tris[i];
+        hit[i] = 0; det_out[i] = u_out[i] = v_out[i] = t_out[i] = NAN;
+        const float dir[3] = { ray->dx, ray->dy, ray->dz };
+        float P[3]; tri_cross(dir, tri->e2, P);
+        float det = (float)tri_dot(tri->e1, P);
+        det_out[i] = det;
+        if (det < GO_TRIANGLE_EPSILON) continue;
+        float inv_det = (float)(1. / det);
+        const float OV[3] = { ray->ox - tri->v[0], ray->oy - tri->v[1], ray->oz - tri->v[2] };
+        float u = (float)(tri_dot(OV, P) * inv_det);
+        u_out[i] = u;
+        if (u < 0.f || u > 1.f) continue;
+        float Q[3]; tri_cross(OV, tri->e1, Q);
+        float v = (float)(tri_dot(dir, Q) * inv_det);
+        v_out[i] = v;
+        if (v < 0.f || u + v > 1.f) continue;
+        t_out[i] = (float)(tri_dot(tri->e2, Q) * inv_det);
+        hit[i] = 1;
+    }
+}
+
 /* trace_closest_tri (tris_trace.cu:43-62) by brute force: RayEntry_tri, RayIntersect_tri,
  * OnHit_tri (tris_trace.cuh:11-73) applied to every triangle in index order -- what the
  * packet traversal computes when it is conservative. */

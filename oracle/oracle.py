@@ -323,6 +323,18 @@ def brute_closest_tri(rays, tris):
     return out, t
 
 
+def tri_intersect_pairs(rays, tris):
+    """The oracle's tri_intersect on (rays[i], tris[i]) pairs.  Returns (accept bool, det, u, v, t)
+    as float32; a value behind the early return that rejected the pair is NaN."""
+    rays = _rays(rays); tris = _tris(tris)
+    assert len(rays) == len(tris)
+    n = len(rays)
+    hit = np.empty(n, np.int32)
+    det, u, v, t = (np.empty(n, np.float32) for _ in range(4))
+    lib().go_tri_intersect_pairs(_p(rays), _p(tris), C.c_size_t(n), _p(hit), _p(det), _p(u), _p(v), _p(t))
+    return hit.astype(bool), det, u, v, t
+
+
 def pinhole_rays(res_x, res_y, cam, look_at, up, fovy, length):
     rays = np.empty(res_x * res_y, RAY_DTYPE)
     f = lambda v: np.asarray(v, np.float32)
