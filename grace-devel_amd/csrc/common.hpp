@@ -78,6 +78,10 @@ struct Context {
     volatile uint32_t* sort_overflow_host = nullptr;
     uint32_t* sort_overflow_dev = nullptr;      // the device's view of the same word
     uint32_t sort_hint_skips = 0;
+    // what the last sort on this context planned (grace_sort_last_stats): the bucket digit (0: index
+    // sort), the bucket tile, whether the hint skipped the plan, whether the bucket kernels were enqueued
+    int sort_last_msd_bits = 0, sort_last_tile = 0;
+    bool sort_last_hint_skipped = false, sort_last_bucketed = false;
     // traversal state, owned by the trace translation units
     TraceState* trace = nullptr;
 };

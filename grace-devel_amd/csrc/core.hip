@@ -85,6 +85,8 @@ static grace_status context_clear(Context& c)
     c.sort_overflow_host = nullptr;
     c.sort_overflow_dev = nullptr;
     c.sort_hint_skips = 0;
+    c.sort_last_msd_bits = c.sort_last_tile = 0;
+    c.sort_last_hint_skipped = c.sort_last_bucketed = false;
     return GRACE_OK;
 }
 

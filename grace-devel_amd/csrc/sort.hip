@@ -900,6 +900,16 @@ grace_status copy_gated(const void* in, void* out, size_t bytes, const uint32_t*
     return GRACE_OK;
 }
 
+// grace_sort_last_stats: two integers and two flags per call, on the host
+void record_plan(Context* ctx, int msd_bits, int tile, bool hint_skipped, bool bucketed)
+{
+    if (!ctx) return;
+    ctx->sort_last_msd_bits = msd_bits;
+    ctx->sort_last_tile = tile;
+    ctx->sort_last_hint_skipped = hint_skipped;
+    ctx->sort_last_bucketed = bucketed;
+}
+
 template <typename Key>
 grace_status sort_pairs(Key* d_keys, void* d_values, size_t n, int value_bytes, int begin_bit,
                         int end_bit, uint32_t* d_perm_out, hipStream_t stream, bool nested = false,
@@ -922,7 +932,10 @@ grace_status sort_pairs(Key* d_keys, void* d_values, size_t n, int value_bytes, 
         GRACE_TRY(scene_invalidate_if_written(d_values));
         GRACE_TRY(rays_invalidate_if_written(d_values));
     }
+    const int stats_tile = local_tile(int(sizeof(Key)), d_values ? value_bytes / 4 : 0);
     if (n <= 1) {
+        Context* ctx = Workspace::frame_context();
+        if (ctx || current_context(&ctx) == GRACE_OK) record_plan(ctx, 0, stats_tile, false, false);
         if (n == 1 && d_perm_out) GRACE_TRY_HIP(hipMemsetAsync(d_perm_out, 0, 4, stream));
         return GRACE_OK;
     }
@@ -946,6 +959,7 @@ grace_status sort_pairs(Key* d_keys, void* d_values, size_t n, int value_bytes, 
     side_guard.call_stream = stream;
     int msd_bits = 0;
     bool try_buckets = !run_if && bucket_plan<Key>(n, end_bit - begin_bit, d_values ? value_bytes / 4 : 0, msd_bits);
+    const bool planned = try_buckets;
     if (try_buckets) {
         // the hint of the last large sort on this context (see Context::sort_overflow_host)
         Context* ctx = nullptr;
@@ -955,6 +969,7 @@ grace_status sort_pairs(Key* d_keys, void* d_values, size_t n, int value_bytes, 
             else ctx->sort_hint_skips = 0;               // every 8th time: look again
         }
     }
+    record_plan(Workspace::frame_context(), planned ? msd_bits : 0, stats_tile, planned && !try_buckets, try_buckets);
     if (try_buckets) {
         hipStream_t side = nullptr;
         const grace_status st = sort_pairs_bucketed<Key>(d_keys, d_values, n, value_bytes, begin_bit, end_bit,
@@ -1037,6 +1052,18 @@ grace_status grace_sort_pairs_u32(uint32_t* d_keys, void* d_values, size_t n, in
 grace_status grace_sort_set_overflow_hint(int enabled)
 {
     g_overflow_hint_on = enabled != 0;
+    return GRACE_OK;
+}
+
+grace_status grace_sort_last_stats(grace_sort_stats* h_stats)
+{
+    GRACE_REQUIRE(h_stats, "sort_last_stats: null output");
+    Context* ctx = nullptr;
+    GRACE_TRY(current_context(&ctx));
+    h_stats->msd_bits = ctx->sort_last_msd_bits;
+    h_stats->tile = ctx->sort_last_tile;
+    h_stats->hint_skipped = ctx->sort_last_hint_skipped ? 1 : 0;
+    h_stats->overflowed = ctx->sort_last_bucketed && ctx->sort_overflow_host ? int(*ctx->sort_overflow_host) : -1;
     return GRACE_OK;
 }
 

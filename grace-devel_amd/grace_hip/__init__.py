@@ -165,6 +165,19 @@ def set_sort_overflow_hint(enabled):
     _check(_lib.grace_sort_set_overflow_hint(C.c_int(1 if enabled else 0)))
 
 
+class _SortStats(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("msd_bits", "tile", "hint_skipped", "overflowed")]
+
+
+def sort_last_stats():
+    """grace_sort_last_stats: what the last sort of the calling thread's context planned, as a dict:
+    msd_bits (0: index sort), tile, hint_skipped, overflowed (valid after a synchronise; -1: no
+    bucket sort was enqueued or its flag word is unavailable)."""
+    st = _SortStats()
+    _check(_lib.grace_sort_last_stats(C.byref(st)))
+    return {k: getattr(st, k) for k, _ in _SortStats._fields_}
+
+
 def morton_keys30_sort_sph(spheres, bot=None, top=None):
     """build_sph.cuh:41-58: keys + stable sort of the spheres by key, in place."""
     keys = torch.empty(len(spheres), dtype=torch.int32, device=spheres.device)

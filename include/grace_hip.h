@@ -164,6 +164,19 @@ grace_status grace_sort_pairs_u64(uint64_t* d_keys, void* d_values, size_t n, in
  * and then goes straight to the index sort, looking again every 8th time.  0 switches the memory
  * off (every large sort tries the buckets); the choice is between two paths with identical results. */
 grace_status grace_sort_set_overflow_hint(int enabled);
+/* Which sort the last grace_sort_pairs_* call of the calling thread's context took (the sorts made
+ * inside other entry points, e.g. the composite-key sort of grace_sort_by_distance_f32, record
+ * too).  Recorded on the host when the call is made: no launch, no synchronisation. */
+typedef struct grace_sort_stats {
+    int msd_bits;       /* bits of the bucket digit the call planned; 0: the index sort */
+    int tile;           /* records per bucket tile / bucket capacity for the key and payload: 4096 or 8192 */
+    int hint_skipped;   /* 1: a bucket plan was made but the overflow hint sent the call to the index sort */
+    int overflowed;     /* the word the bucket sort's flag kernel writes: 1 if a bucket was above the capacity
+                           (the gated index sort did the work), 0 if the bucket kernels did; valid once the
+                           call's stream is synchronised.  -1: no bucket sort was enqueued by that call, or the
+                           pinned word could not be allocated */
+} grace_sort_stats;
+grace_status grace_sort_last_stats(grace_sort_stats* h_stats);
 
 /* ---- deltas: grace::compute_deltas (include/grace/cuda/kernels/albvh.cuh:33-47,949-978)
  *      with DeltaEuclidean / DeltaSurfaceArea / DeltaXOR
