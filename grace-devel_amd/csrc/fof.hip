@@ -138,7 +138,8 @@ struct LinkVisitor {
     __device__ __forceinline__ void finish(const uint32_t) const {}
 };
 
-__global__ __launch_bounds__(RG_BLOCK) void fof_link_kernel(const FofArgs a)
+template <typename Args>
+__global__ __launch_bounds__(RG_BLOCK) void fof_link_kernel(const Args a)
 {
     __shared__ float4 s_rec[RG_WAVES][64];
     __shared__ int s_par[RG_WAVES][64];
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(RG_BLOCK) void fof_link_kernel(const FofArgs a)
     const int packet = blockIdx.x * RG_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
     if (packet < int(*a.n_starts)) {
         LinkVisitor v(a.parent, s_par[wv]);
-        walk_packet(a, packet, lane, s_rec[wv], v);
+        walk(a, packet, lane, s_rec[wv], v);
     }
 }
 
@@ -219,20 +220,19 @@ __global__ __launch_bounds__(256) void fof_members_kernel(const uint32_t* __rest
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) members[i] = int(perm[i]);
 }
 
-} // namespace
-
-extern "C" {
-
-grace_status grace_fof_labels_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes, size_t n_nodes,
-                                 const int* d_leaves, const int* d_root, float linking_length, int* d_labels,
-                                 grace_stream stream)
+// grace_fof_labels_f4 and its periodic form (Periodic<FofArgs>: the link kernel over the walk's
+// periodic variant; the visitor, the union-find and the flatten are the same): `a` is zero but for
+// a period.
+template <typename Args>
+grace_status fof_labels(Args a, const float* d_spheres, size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                        const int* d_leaves, const int* d_root, float linking_length, int* d_labels,
+                        grace_stream stream)
 {
     GRACE_REQUIRE(std::isfinite(linking_length) && linking_length >= 0.0f,
                   "fof_labels: the linking length must be finite and not negative");
     GRACE_REQUIRE(n_spheres < (size_t(1) << 31), "fof_labels: more than INT32_MAX spheres");
     if (n_spheres == 0) return GRACE_OK;   // (before the pointer checks: a caller's empty arrays may be null)
     GRACE_REQUIRE(d_labels, "fof_labels: null labels");
-    FofArgs a = {};
     GRACE_TRY(walk_scene(a, nullptr, linking_length, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root));
     a.parent = d_labels;
     TraceState* ts = nullptr;
@@ -241,13 +241,35 @@ grace_status grace_fof_labels_f4(const float* d_spheres, size_t n_spheres, const
     const int n = int(n_spheres);
     fof_init_kernel<<<stream_grid(n_spheres, 256), 256, 0, stream_>>>(d_labels, n);
     GRACE_CHECK_LAUNCH();
-    return walk_run(a, *ts, d_spheres, n_spheres, 4, stream_, [&](const FofArgs& w, size_t waves) -> grace_status {
+    return walk_run(a, *ts, d_spheres, n_spheres, 4, stream_, [&](const Args& w, size_t waves) -> grace_status {
         fof_link_kernel<<<ceil_div(waves, RG_WAVES), RG_BLOCK, 0, stream_>>>(w);
         GRACE_CHECK_LAUNCH();
         fof_flatten_kernel<<<stream_grid(n_spheres, 256), 256, 0, stream_>>>(w.parent, n);
         GRACE_CHECK_LAUNCH();
         return GRACE_OK;
     });
+}
+
+} // namespace
+
+extern "C" {
+
+grace_status grace_fof_labels_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                 const int* d_leaves, const int* d_root, float linking_length, int* d_labels,
+                                 grace_stream stream)
+{
+    return fof_labels(FofArgs(), d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, linking_length, d_labels,
+                      stream);
+}
+
+grace_status grace_fof_labels_periodic_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                          size_t n_nodes, const int* d_leaves, const int* d_root,
+                                          float linking_length, int* d_labels, const float* h_period3,
+                                          grace_stream stream)
+{
+    Periodic<FofArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, &linking_length));
+    return fof_labels(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, linking_length, d_labels, stream);
 }
 
 grace_status grace_fof_groups(const int* d_labels, size_t n, int min_members, int* d_group_of, int* d_sizes,

@@ -123,8 +123,8 @@ struct PairVisitor {
     }
 };
 
-template <int BT, int NW>
-__global__ __launch_bounds__(RG_BLOCK) void pair_kernel(const PairArgs a)
+template <int BT, int NW, typename Args>
+__global__ __launch_bounds__(RG_BLOCK) void pair_kernel(const Args a)
 {
     constexpr int NS = NW > 0 ? NW : 1;
     constexpr int SR = sums_rows(BT, NW);
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(RG_BLOCK) void pair_kernel(const PairArgs a)
     const int packet = blockIdx.x * RG_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
     if (packet >= int(*a.n_starts)) return;
     PairVisitor<BT, NW> v(a, &s_cnt[wv][0][lane], &s_sum[wv][0][SR > 0 ? lane : 0], s_w[wv], s_e2);
-    walk_packet(a, packet, lane, s_rec[wv], v);
+    walk(a, packet, lane, s_rec[wv], v);
     if (!a.totals) return;
     // all 64 lanes again: bin `lane` over the wave's columns
     wave_sync();
@@ -155,8 +155,8 @@ __global__ __launch_bounds__(RG_BLOCK) void pair_kernel(const PairArgs a)
     }
 }
 
-template <int BT>
-void launch_tier(const PairArgs& a, int nw, int blocks, hipStream_t stream)
+template <int BT, typename Args>
+void launch_tier(const Args& a, int nw, int blocks, hipStream_t stream)
 {
     switch (nw) {
     case 0: pair_kernel<BT, 0><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
@@ -167,7 +167,8 @@ void launch_tier(const PairArgs& a, int nw, int blocks, hipStream_t stream)
     }
 }
 
-grace_status launch_pairs(const PairArgs& a, int nw, size_t waves, hipStream_t stream)
+template <typename Args>
+grace_status launch_pairs(const Args& a, int nw, size_t waves, hipStream_t stream)
 {
     const int blocks = ceil_div(waves, RG_WAVES);
     if (a.n_edges <= 8) launch_tier<8>(a, nw, blocks, stream);
@@ -176,6 +177,54 @@ grace_status launch_pairs(const PairArgs& a, int nw, size_t waves, hipStream_t s
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
 }
+
+// grace_pair_counts_f4 and its periodic form (Periodic<PairArgs>: the same visitor over the walk's
+// periodic variant): `a` is zero.  h_period3: the periodic form's period, checked together with the
+// last edge once the edges are known to be good.
+template <typename Args>
+grace_status pair_counts(Args a, const float* d_points, size_t n_points, int elems_per_point,
+                         const float* h_edges, int n_edges, const float* d_spheres, size_t n_spheres,
+                         const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                         const float* d_weights, int n_channels, unsigned long long* d_totals, int* d_counts,
+                         float* d_sums, const float* h_period3, grace_stream stream)
+{
+    GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "pair_counts: elements per point must be 3..16");
+    GRACE_REQUIRE(n_points < (size_t(1) << 31), "pair_counts: too many points");
+    GRACE_REQUIRE(n_edges >= 1 && n_edges <= PC_MAX_EDGES, "pair_counts: the number of edges must be 1..64");
+    GRACE_REQUIRE(h_edges, "pair_counts: null edges");
+    for (int k = 0; k < n_edges; ++k)
+        GRACE_REQUIRE(std::isfinite(h_edges[k]) && h_edges[k] >= 0.0f && (k == 0 || h_edges[k] > h_edges[k - 1]),
+                      "pair_counts: the edges must be finite, not negative and strictly ascending");
+    if constexpr (is_periodic<Args>::value) GRACE_TRY(walk_period(a.per, h_period3, h_edges + n_edges - 1));
+    if (d_sums) {
+        GRACE_REQUIRE(n_channels >= 1 && n_channels <= PC_MAX_CHANNELS, "pair_counts: channels must be 1..4");
+        GRACE_REQUIRE(n_edges * n_channels <= PC_MAX_CELLS, "pair_counts: edges times channels must not exceed 64");
+        GRACE_REQUIRE(d_weights, "pair_counts: sums need weights");
+    }
+    const hipStream_t stream_ = as_stream(stream);
+    if (n_points == 0) {                  // (before the output checks: a caller's empty arrays may be null)
+        if (d_totals) GRACE_TRY_HIP(hipMemsetAsync(d_totals, 0, size_t(n_edges) * sizeof(unsigned long long), stream_));
+        return GRACE_OK;
+    }
+    GRACE_REQUIRE(d_totals || d_counts || d_sums, "pair_counts: no output");
+    GRACE_REQUIRE(d_points, "pair_counts: null points");
+    GRACE_TRY(walk_scene(a, nullptr, h_edges[n_edges - 1], d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root));
+    TraceState* ts = nullptr;
+    GRACE_TRY(trace_state(&ts));
+    for (int k = 0; k < PC_MAX_EDGES; ++k)
+        a.e2[k] = k < n_edges - 1 ? h_edges[k] * h_edges[k] : std::numeric_limits<float>::infinity();
+    a.n_edges = n_edges;
+    a.weights = d_weights;
+    a.totals = d_totals;
+    a.counts = d_counts;
+    a.sums = d_sums;
+    if (d_totals) GRACE_TRY_HIP(hipMemsetAsync(d_totals, 0, size_t(n_edges) * sizeof(unsigned long long), stream_));
+    return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
+                    [&](const Args& w, size_t waves) -> grace_status {
+        return launch_pairs(w, d_sums ? n_channels : 0, waves, stream_);
+    });
+}
+
 
 } // namespace
 
@@ -189,41 +238,20 @@ grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int el
                                   unsigned long long* d_totals, int* d_counts, float* d_sums,
                                   grace_stream stream)
 {
-    GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "pair_counts: elements per point must be 3..16");
-    GRACE_REQUIRE(n_points < (size_t(1) << 31), "pair_counts: too many points");
-    GRACE_REQUIRE(n_edges >= 1 && n_edges <= PC_MAX_EDGES, "pair_counts: the number of edges must be 1..64");
-    GRACE_REQUIRE(h_edges, "pair_counts: null edges");
-    for (int k = 0; k < n_edges; ++k)
-        GRACE_REQUIRE(std::isfinite(h_edges[k]) && h_edges[k] >= 0.0f && (k == 0 || h_edges[k] > h_edges[k - 1]),
-                      "pair_counts: the edges must be finite, not negative and strictly ascending");
-    if (d_sums) {
-        GRACE_REQUIRE(n_channels >= 1 && n_channels <= PC_MAX_CHANNELS, "pair_counts: channels must be 1..4");
-        GRACE_REQUIRE(n_edges * n_channels <= PC_MAX_CELLS, "pair_counts: edges times channels must not exceed 64");
-        GRACE_REQUIRE(d_weights, "pair_counts: sums need weights");
-    }
-    const hipStream_t stream_ = as_stream(stream);
-    if (n_points == 0) {                  // (before the output checks: a caller's empty arrays may be null)
-        if (d_totals) GRACE_TRY_HIP(hipMemsetAsync(d_totals, 0, size_t(n_edges) * sizeof(unsigned long long), stream_));
-        return GRACE_OK;
-    }
-    GRACE_REQUIRE(d_totals || d_counts || d_sums, "pair_counts: no output");
-    GRACE_REQUIRE(d_points, "pair_counts: null points");
-    PairArgs a = {};
-    GRACE_TRY(walk_scene(a, nullptr, h_edges[n_edges - 1], d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root));
-    TraceState* ts = nullptr;
-    GRACE_TRY(trace_state(&ts));
-    for (int k = 0; k < PC_MAX_EDGES; ++k)
-        a.e2[k] = k < n_edges - 1 ? h_edges[k] * h_edges[k] : std::numeric_limits<float>::infinity();
-    a.n_edges = n_edges;
-    a.weights = d_weights;
-    a.totals = d_totals;
-    a.counts = d_counts;
-    a.sums = d_sums;
-    if (d_totals) GRACE_TRY_HIP(hipMemsetAsync(d_totals, 0, size_t(n_edges) * sizeof(unsigned long long), stream_));
-    return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                    [&](const PairArgs& w, size_t waves) -> grace_status {
-        return launch_pairs(w, d_sums ? n_channels : 0, waves, stream_);
-    });
+    return pair_counts(PairArgs(), d_points, n_points, elems_per_point, h_edges, n_edges, d_spheres, n_spheres,
+                       d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels, d_totals, d_counts, d_sums, nullptr, stream);
+}
+
+grace_status grace_pair_counts_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                           const float* h_edges, int n_edges,
+                                           const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                           size_t n_nodes, const int* d_leaves, const int* d_root,
+                                           const float* d_weights, int n_channels,
+                                           unsigned long long* d_totals, int* d_counts, float* d_sums,
+                                           const float* h_period3, grace_stream stream)
+{
+    return pair_counts(Periodic<PairArgs>(), d_points, n_points, elems_per_point, h_edges, n_edges, d_spheres, n_spheres,
+                       d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels, d_totals, d_counts, d_sums, h_period3, stream);
 }
 
 } // extern "C"

@@ -14,6 +14,9 @@
 // holds what a lane does with a centre in range: one compare, then a count, an append or the kernel
 // and one multiply-add pair per channel.  The survivors' <= 4 weights of a sums walk are staged in
 // LDS beside their records.
+//
+// The periodic entry points run the same visitors over the walk's periodic variant: the kernels are
+// instantiated a second time with Periodic<RangeArgs> arguments.
 #include "range_walk.hpp"
 #include "sph_kernel_f.hpp"
 
@@ -106,8 +109,8 @@ struct RangeVisitor {
     }
 };
 
-template <int MODE, int KIND, int NW>
-__global__ __launch_bounds__(RG_BLOCK) void range_kernel(const RangeArgs a)
+template <int MODE, int KIND, int NW, typename Args>
+__global__ __launch_bounds__(RG_BLOCK) void range_kernel(const Args a)
 {
     __shared__ float4 s_rec[RG_WAVES][64];
     __shared__ float s_w[RG_WAVES][NW > 0 ? 64 : 1][NW > 0 ? NW : 1];
@@ -116,12 +119,12 @@ __global__ __launch_bounds__(RG_BLOCK) void range_kernel(const RangeArgs a)
     const int packet = blockIdx.x * RG_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
     if (packet < int(*a.n_starts)) {
         RangeVisitor<MODE, KIND, NW> v(a, s_w[wv]);
-        walk_packet(a, packet, lane, s_rec[wv], v);
+        walk(a, packet, lane, s_rec[wv], v);
     }
 }
 
-template <int KIND>
-void launch_sums(const RangeArgs& a, int nw, int blocks, hipStream_t stream)
+template <int KIND, typename Args>
+void launch_sums(const Args& a, int nw, int blocks, hipStream_t stream)
 {
     switch (nw) {
     case 1: range_kernel<RG_SUMS, KIND, 1><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
@@ -132,7 +135,8 @@ void launch_sums(const RangeArgs& a, int nw, int blocks, hipStream_t stream)
 }
 
 // One walk: mode RG_COUNT / RG_FILL, or RG_SUMS over nw channels with the built-in kernel `kind`.
-grace_status launch_walk(const RangeArgs& a, int mode, int kind, int nw, size_t waves, hipStream_t stream)
+template <typename Args>
+grace_status launch_walk(const Args& a, int mode, int kind, int nw, size_t waves, hipStream_t stream)
 {
     const int blocks = ceil_div(waves, RG_WAVES);
     if (mode == RG_COUNT) {
@@ -164,16 +168,12 @@ grace_status range_common(RangeArgs& a, const float* d_points, size_t n_points,
     return walk_scene(a, d_radii, radius, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
 }
 
-} // namespace
-
-extern "C" {
-
-grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int elems_per_point,
-                                   const float* d_radii, float radius,
-                                   const float* d_spheres, size_t n_spheres, const int* d_nodes,
-                                   size_t n_nodes, const int* d_leaves, const int* d_root,
-                                   const float* d_weights, int n_channels,
-                                   int* d_counts, float* d_sums, grace_stream stream)
+// grace_range_counts_f4 and its periodic form: `a` is zero but for a period.
+template <typename Args>
+grace_status range_counts(Args a, const float* d_points, size_t n_points, int elems_per_point,
+                          const float* d_radii, float radius, const float* d_spheres, size_t n_spheres,
+                          const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                          const float* d_weights, int n_channels, int* d_counts, float* d_sums, grace_stream stream)
 {
     GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "range_counts: elements per point must be 3..16");
     GRACE_REQUIRE(n_points < (size_t(1) << 31), "range_counts: too many points");
@@ -183,7 +183,6 @@ grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int e
     }
     if (n_points == 0) return GRACE_OK;   // (before the output checks: a caller's empty arrays may be null)
     GRACE_REQUIRE(d_counts || d_sums, "range_counts: no output");
-    RangeArgs a = {};
     GRACE_TRY(range_common(a, d_points, n_points, d_radii, radius, d_spheres, n_spheres, d_nodes,
                            n_nodes, d_leaves, d_root));
     TraceState* ts = nullptr;
@@ -195,7 +194,7 @@ grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int e
     a.w_stride = n_channels;
     const hipStream_t stream_ = as_stream(stream);
     return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                     [&](RangeArgs w, size_t waves) -> grace_status {
+                     [&](Args w, size_t waves) -> grace_status {
         if (!d_sums) {
             w.counts = d_counts;
             return launch_walk(w, RG_COUNT, kind, 0, waves, stream_);
@@ -211,19 +210,18 @@ grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int e
     });
 }
 
-grace_status grace_range_neighbours_f4(const float* d_points, size_t n_points, int elems_per_point,
-                                       const float* d_radii, float radius,
-                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
-                                       size_t n_nodes, const int* d_leaves, const int* d_root,
-                                       const int* d_offsets, int* d_indices, float* d_d2,
-                                       grace_stream stream)
+// grace_range_neighbours_f4 and its periodic form.
+template <typename Args>
+grace_status range_neighbours(Args a, const float* d_points, size_t n_points, int elems_per_point,
+                              const float* d_radii, float radius, const float* d_spheres, size_t n_spheres,
+                              const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                              const int* d_offsets, int* d_indices, float* d_d2, grace_stream stream)
 {
     GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "range_neighbours: elements per point must be 3..16");
     GRACE_REQUIRE(n_points < (size_t(1) << 31), "range_neighbours: too many points");
     if (n_points == 0) return GRACE_OK;   // (before the output checks: a caller's empty arrays may be null)
     GRACE_REQUIRE(d_offsets, "range_neighbours: null offsets");
     GRACE_REQUIRE(d_indices || d_d2, "range_neighbours: no output");
-    RangeArgs a = {};
     GRACE_TRY(range_common(a, d_points, n_points, d_radii, radius, d_spheres, n_spheres,
                            d_nodes, n_nodes, d_leaves, d_root));
     TraceState* ts = nullptr;
@@ -233,9 +231,62 @@ grace_status grace_range_neighbours_f4(const float* d_points, size_t n_points, i
     a.d2 = d_d2;
     const hipStream_t stream_ = as_stream(stream);
     return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                     [&](RangeArgs w, size_t waves) -> grace_status {
+                     [&](const Args& w, size_t waves) -> grace_status {
         return launch_walk(w, RG_FILL, GRACE_SPH_KERNEL_CUBIC, 0, waves, stream_);
     });
+}
+
+} // namespace
+
+extern "C" {
+
+grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                   const float* d_radii, float radius,
+                                   const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                   size_t n_nodes, const int* d_leaves, const int* d_root,
+                                   const float* d_weights, int n_channels,
+                                   int* d_counts, float* d_sums, grace_stream stream)
+{
+    return range_counts(RangeArgs(), d_points, n_points, elems_per_point, d_radii, radius, d_spheres, n_spheres,
+                        d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels, d_counts, d_sums, stream);
+}
+
+grace_status grace_range_neighbours_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                       const float* d_radii, float radius,
+                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                       size_t n_nodes, const int* d_leaves, const int* d_root,
+                                       const int* d_offsets, int* d_indices, float* d_d2,
+                                       grace_stream stream)
+{
+    return range_neighbours(RangeArgs(), d_points, n_points, elems_per_point, d_radii, radius, d_spheres, n_spheres,
+                            d_nodes, n_nodes, d_leaves, d_root, d_offsets, d_indices, d_d2, stream);
+}
+
+grace_status grace_range_counts_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                            const float* d_radii, float radius,
+                                            const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                            size_t n_nodes, const int* d_leaves, const int* d_root,
+                                            const float* d_weights, int n_channels,
+                                            int* d_counts, float* d_sums, const float* h_period3,
+                                            grace_stream stream)
+{
+    Periodic<RangeArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, d_radii ? nullptr : &radius));
+    return range_counts(a, d_points, n_points, elems_per_point, d_radii, radius, d_spheres, n_spheres,
+                        d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels, d_counts, d_sums, stream);
+}
+
+grace_status grace_range_neighbours_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                const float* d_radii, float radius,
+                                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                const int* d_offsets, int* d_indices, float* d_d2,
+                                                const float* h_period3, grace_stream stream)
+{
+    Periodic<RangeArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, d_radii ? nullptr : &radius));
+    return range_neighbours(a, d_points, n_points, elems_per_point, d_radii, radius, d_spheres, n_spheres,
+                            d_nodes, n_nodes, d_leaves, d_root, d_offsets, d_indices, d_d2, stream);
 }
 
 } // extern "C"

@@ -31,6 +31,36 @@
 // have an empty box and NaN in place of their coordinates and R2: no lane widens for them, and
 // no compare is ever true.
 //
+// Periodic boxes (walk_packet<Visitor, true>, a WalkPeriod: per axis the period L and h = fl(0.5 L),
+// exact; an open axis has L = 0 and h = +inf, which no |d| exceeds and no radius, so it needs no
+// case of its own).  The pair test wraps each component once, d = fl(p - x); d > h: d = fl(d - L);
+// else d < -h: d = fl(d + L), and a lane whose r exceeds h on some axis is off.  Each centre is
+// still tested once per lane: the union box stays one box, and per axis a node or a centre passes
+// if it meets the box, the box shifted by -L or the box shifted by +L (both rounded outward, once
+// per packet, in SGPRs like the box itself).
+//   Widening, wrapped.  Let rho = sqrt(D) (1 + 2^-22) < r' as above; a centre in range has a
+// wrapped component |dw| <= rho.  No wrap: dw = fl(p - x) and x is in [p - r', p + r'] as before.
+// d0 = fl(p - x) > h: if d0 > 2 L then fl(d0 - L) >= L >= 2 r and the square is above D (an on lane
+// has r <= h); else d0 is in [L / 2, 2 L] and d0 - L is exact (Sterbenz), so |d0 - L| <= rho and
+// d0 <= L + rho < 1.51 L.  The exact p - x is d0 / (1 + e), |e| <= 2^-24, within 1.51 L 2^-24
+// (1 + 2^-23) < 2^-23 L of d0, so |x - (p - L)| <= rho + 2^-23 L.  d0 < -h is the mirror image
+// about p + L.  That error is absolute in L and may exceed a small r, so on a periodic axis the
+// lane's radius is r'' = fl(r' + L 2^-22) (the product is exact; the sum's rounding is below
+// 2^-25 L, so r'' > r' + 2^-23 L), and x lies in [p - r'', p + r''] shifted by -+L.  The lane's
+// rounded bounds are moved out by 2^-20 of themselves as before; the union's bounds u -+ L are
+// rounded once more (2^-24 of the result) and moved out by 2^-20 of the result.  So pruning still
+// only drops centres whose wrapped d2 is strictly above the lane's R2.  Over-inclusion costs tests
+// only: a centre that passes through an image it is not in range of fails d2 <= R2.
+//   Skipping the wrap.  Every on lane's p is inside the union box.  If on every axis the box is no
+// wider than h (fl(fl(uhi - ulo) (1 + 2^-20)) <= h, which bounds the exact width) and a cluster's
+// survivors all passed through the unshifted box, then |p - x| <= h exactly, rounding is monotone and
+// h is a float, so |fl(p - x)| <= h and neither wrap can fire: that cluster is tested without the
+// wrap, a wave-uniform branch with the same bits either way.
+//   Skipping the images.  The root's box holds every node box and every centre.  A packet whose
+// shifted boxes do not meet it on any axis can pass nothing through an image: it tests nodes and
+// centres against the box itself, as the open walk does (wave-uniform; most packets of a box that
+// the data fills are away from its faces).
+//
 // A Visitor provides
 //   void begin(bool in_range, bool on, uint32_t src, float r)   before the walk: the lane's point
 //        (src: its index in the caller's order; off lanes and lanes beyond the packet too)
@@ -42,6 +72,10 @@
 #pragma once
 
 #include "point_packets.hpp"
+
+#include <cmath>
+#include <limits>
+#include <type_traits>
 
 namespace {
 
@@ -68,6 +102,20 @@ struct WalkArgs {
     int* status;
 };
 
+// A periodic box: per axis the period L (0: open) and h = fl(0.5 L) (open: +inf).
+struct WalkPeriod {
+    float L[3];
+    float h[3];
+};
+
+// Args with a period beside them: what the periodic kernels take (walk() below picks the walk).
+template <typename Base>
+struct Periodic : Base {
+    WalkPeriod per;
+};
+template <typename T> struct is_periodic : std::false_type {};
+template <typename Base> struct is_periodic<Periodic<Base>> : std::true_type {};
+
 // The lane's query box on one axis, widened as stated above (off lanes: empty, +inf / -inf).
 __device__ __forceinline__ void query_bounds(const float p, const float r, const bool on, float& lo, float& hi)
 {
@@ -81,10 +129,42 @@ __device__ __forceinline__ bool overlaps(const float lo, const float hi, const f
     return lo <= uhi && hi >= ulo;
 }
 
-// One packet.  s_rec: the wave's 64 survivor records.
-template <typename Visitor>
+// The union box on one axis and its images shifted by -L and +L, rounded outward (wave-uniform).
+struct AxisImages {
+    float lo, hi, mlo, mhi, plo, phi;
+    __device__ __forceinline__ bool meets(const float blo, const float bhi) const
+    {
+        return overlaps(blo, bhi, lo, hi) || overlaps(blo, bhi, mlo, mhi) || overlaps(blo, bhi, plo, phi);
+    }
+    __device__ __forceinline__ bool direct(const float x) const { return x >= lo && x <= hi; }
+    __device__ __forceinline__ bool holds(const float x) const
+    {
+        return direct(x) || (x >= mlo && x <= mhi) || (x >= plo && x <= phi);
+    }
+};
+
+__device__ __forceinline__ float uniform(const float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+__device__ __forceinline__ AxisImages axis_images(const float ulo, const float uhi, const float L)
+{
+    const float ml = ulo - L, mh = uhi - L, pl = ulo + L, ph = uhi + L;
+    return { ulo, uhi, uniform(ml - fabsf(ml) * RG_SLACK), uniform(mh + fabsf(mh) * RG_SLACK),
+             uniform(pl - fabsf(pl) * RG_SLACK), uniform(ph + fabsf(ph) * RG_SLACK) };
+}
+
+// One component of the periodic separation: at most one wrap (open axis: h = +inf, none).
+__device__ __forceinline__ float wrap_sep(const float d, const float L, const float h)
+{
+    return d > h ? d - L : (d < -h ? d + L : d);
+}
+
+// One packet.  s_rec: the wave's 64 survivor records.  PERIODIC: the separation wraps by `per`.
+template <typename Visitor, bool PERIODIC = false>
 __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet, const int lane, float4* s_rec,
-                                            Visitor& v)
+                                            Visitor& v, const WalkPeriod& per = WalkPeriod())
 {
     // ---- the packet's points ----
     const uint32_t first = a.starts[packet], end = a.starts[packet + 1];
@@ -94,8 +174,9 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
     const float* q = a.points + size_t(src) * a.stride;
     float px = q[0], py = q[1], pz = q[2];
     const float r = a.radii ? a.radii[src] : a.radius;
-    const bool on = in_range && isfinite(px) && isfinite(py) && isfinite(pz) && r >= 0.0f
+    bool on = in_range && isfinite(px) && isfinite(py) && isfinite(pz) && r >= 0.0f
         && r < __int_as_float(0x7f800000);
+    if constexpr (PERIODIC) on = on && !(r > per.h[0] || r > per.h[1] || r > per.h[2]);
     if (!on) px = py = pz = __int_as_float(0x7fc00000);
     const float R2 = on ? r * r : __int_as_float(0x7fc00000);   // NaN: no d2 <= R2
 
@@ -104,9 +185,37 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
     {
         const float rw = __builtin_amdgcn_sqrtf(R2) * (1.0f + RG_SLACK) + RG_FLOOR;   // R2 = +inf: +inf
         float lo, hi;
-        query_bounds(px, rw, on, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
-        query_bounds(py, rw, on, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
-        query_bounds(pz, rw, on, lo, hi); ulo_z = wave_min(lo); uhi_z = wave_max(hi);
+        if constexpr (PERIODIC) {
+            query_bounds(px, rw + per.L[0] * 0.25f * RG_SLACK, on, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
+            query_bounds(py, rw + per.L[1] * 0.25f * RG_SLACK, on, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
+            query_bounds(pz, rw + per.L[2] * 0.25f * RG_SLACK, on, lo, hi); ulo_z = wave_min(lo); uhi_z = wave_max(hi);
+        } else {
+            query_bounds(px, rw, on, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
+            query_bounds(py, rw, on, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
+            query_bounds(pz, rw, on, lo, hi); ulo_z = wave_min(lo); uhi_z = wave_max(hi);
+        }
+    }
+    // periodic: the box's images, and whether it is narrow enough for a cluster to skip the wrap
+    AxisImages bx = {}, by = {}, bz = {};
+    bool narrow = false, images = true;
+    if constexpr (PERIODIC) {
+        bx = axis_images(ulo_x, uhi_x, per.L[0]);
+        by = axis_images(ulo_y, uhi_y, per.L[1]);
+        bz = axis_images(ulo_z, uhi_z, per.L[2]);
+        narrow = (uhi_x - ulo_x) * (1.0f + RG_SLACK) <= per.h[0] && (uhi_y - ulo_y) * (1.0f + RG_SLACK) <= per.h[1]
+            && (uhi_z - ulo_z) * (1.0f + RG_SLACK) <= per.h[2];
+        // the root's box (the union of its children's) holds every node box and centre: a packet none
+        // of whose images meets it needs the box itself only (a root that is a leaf has no box: images)
+        const int rt = *a.root;
+        if (rt >= 0 && rt < a.n_nodes) {
+            const float4* np = a.nodes + 4 * size_t(rt);
+            const float4 L = np[1], R = np[2], Z = np[3];
+            const float dlo_x = fminf(L.x, R.x), dhi_x = fmaxf(L.y, R.y), dlo_y = fminf(L.z, R.z), dhi_y = fmaxf(L.w, R.w);
+            const float dlo_z = fminf(Z.x, Z.z), dhi_z = fmaxf(Z.y, Z.w);
+            images = overlaps(dlo_x, dhi_x, bx.mlo, bx.mhi) || overlaps(dlo_x, dhi_x, bx.plo, bx.phi)
+                || overlaps(dlo_y, dhi_y, by.mlo, by.mhi) || overlaps(dlo_y, dhi_y, by.plo, by.phi)
+                || overlaps(dlo_z, dhi_z, bz.mlo, bz.mhi) || overlaps(dlo_z, dhi_z, bz.plo, bz.phi);
+        }
     }
 
     v.begin(in_range, on, src, r);
@@ -149,10 +258,16 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
         if (n_prims == 0) {
             const float4* np = a.nodes + 4 * size_t(idx);
             const float4 n0 = np[0], L = np[1], R = np[2], Z = np[3];
-            const bool hit_l = overlaps(L.x, L.y, ulo_x, uhi_x) && overlaps(L.z, L.w, ulo_y, uhi_y)
-                && overlaps(Z.x, Z.y, ulo_z, uhi_z);
-            const bool hit_r = overlaps(R.x, R.y, ulo_x, uhi_x) && overlaps(R.z, R.w, ulo_y, uhi_y)
-                && overlaps(Z.z, Z.w, ulo_z, uhi_z);
+            bool hit_l, hit_r;
+            if (PERIODIC && images) {
+                hit_l = bx.meets(L.x, L.y) && by.meets(L.z, L.w) && bz.meets(Z.x, Z.y);
+                hit_r = bx.meets(R.x, R.y) && by.meets(R.z, R.w) && bz.meets(Z.z, Z.w);
+            } else {
+                hit_l = overlaps(L.x, L.y, ulo_x, uhi_x) && overlaps(L.z, L.w, ulo_y, uhi_y)
+                    && overlaps(Z.x, Z.y, ulo_z, uhi_z);
+                hit_r = overlaps(R.x, R.y, ulo_x, uhi_x) && overlaps(R.z, R.w, ulo_y, uhi_y)
+                    && overlaps(Z.z, Z.w, ulo_z, uhi_z);
+            }
             if (hit_r) push(__float_as_int(n0.y));
             if (hit_l) push(__float_as_int(n0.x));       // popped first: ascending primitive order
             continue;
@@ -164,8 +279,16 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
             const bool in = pj >= r_lo && pj < r_hi;
             const int pc = min(max(pj, r_lo), r_hi - 1);
             const float4 s = a.spheres[pc];
-            const bool keep = in && s.x >= ulo_x && s.x <= uhi_x && s.y >= ulo_y && s.y <= uhi_y
-                && s.z >= ulo_z && s.z <= uhi_z;
+            bool keep, plain = true;
+            if (PERIODIC && images) {
+                keep = in && bx.holds(s.x) && by.holds(s.y) && bz.holds(s.z);
+                const bool image = keep && !(bx.direct(s.x) && by.direct(s.y) && bz.direct(s.z));
+                plain = narrow && __builtin_amdgcn_ballot_w64(image) == 0ull;
+            } else {
+                keep = in && s.x >= ulo_x && s.x <= uhi_x && s.y >= ulo_y && s.y <= uhi_y
+                    && s.z >= ulo_z && s.z <= uhi_z;
+                if constexpr (PERIODIC) plain = narrow;
+            }
             const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
             if (mask == 0ull) continue;
             const int n_surv = __builtin_popcountll(mask);
@@ -175,11 +298,22 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
                 v.stage(pos, pc);
             }
             wave_sync();
-            for (int j = 0; j < n_surv; ++j) {
-                const float4 rec = s_rec[j];
-                const float dx = px - rec.x, dy = py - rec.y, dz = pz - rec.z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                if (d2 <= R2) v.hit(j, rec, d2);
+            if (!PERIODIC || plain) {
+                for (int j = 0; j < n_surv; ++j) {
+                    const float4 rec = s_rec[j];
+                    const float dx = px - rec.x, dy = py - rec.y, dz = pz - rec.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 <= R2) v.hit(j, rec, d2);
+                }
+            } else {
+                for (int j = 0; j < n_surv; ++j) {
+                    const float4 rec = s_rec[j];
+                    const float dx = wrap_sep(px - rec.x, per.L[0], per.h[0]);
+                    const float dy = wrap_sep(py - rec.y, per.L[1], per.h[1]);
+                    const float dz = wrap_sep(pz - rec.z, per.L[2], per.h[2]);
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 <= R2) v.hit(j, rec, d2);
+                }
             }
             wave_sync();
         }
@@ -188,6 +322,30 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
     if (overflow && lane == 0) atomicMax(a.status, int(GRACE_STACK_OVERFLOW));
     if (!in_range) return;
     v.finish(src);
+}
+
+// The walk the kernel's arguments ask for: Periodic<...> the periodic one, anything else the open one.
+template <typename Args, typename Visitor>
+__device__ __forceinline__ void walk(const Args& a, const int packet, const int lane, float4* s_rec, Visitor& v)
+{
+    if constexpr (is_periodic<Args>::value) walk_packet<Visitor, true>(a, packet, lane, s_rec, v, a.per);
+    else walk_packet(a, packet, lane, s_rec, v);
+}
+
+// A caller's period (three host floats) as the walk takes it, checked before anything is enqueued.
+// radius: the call's host radius, which must not exceed half a period (NULL: the radii are per point
+// and the walk switches such points off).
+grace_status walk_period(WalkPeriod& per, const float* h_period3, const float* radius)
+{
+    GRACE_REQUIRE(h_period3, "periodic query: null period");
+    for (int d = 0; d < 3; ++d) {
+        const float L = h_period3[d];
+        GRACE_REQUIRE(std::isfinite(L) && L >= 0.0f, "periodic query: a period must be finite and not negative (0: open)");
+        per.L[d] = L > 0.0f ? L : 0.0f;
+        per.h[d] = L > 0.0f ? 0.5f * L : std::numeric_limits<float>::infinity();
+        GRACE_REQUIRE(!radius || !(*radius > per.h[d]), "periodic query: the radius exceeds half a period");
+    }
+    return GRACE_OK;
 }
 
 // The checks every entry point over this walk shares (before anything is enqueued), and the

@@ -892,7 +892,22 @@ def _range_args(points, radii):
     return points, None, float(radii)
 
 
-def range_counts_sph(points, radii, spheres, tree, weights=None, counts=None, out=None, check=False):
+def _period(period):
+    """A period of a periodic query -> three host floats (the library checks their values)."""
+    if torch.is_tensor(period):
+        period = period.detach().cpu().numpy()
+    period = np.ascontiguousarray(np.asarray(period, dtype=np.float32).reshape(-1))
+    if len(period) != 3:
+        raise ValueError("period must hold three values (Lx, Ly, Lz); 0 leaves an axis open")
+    return period
+
+
+def _period_tail(period):
+    """The arguments that follow the outputs: (period,) stream."""
+    return (period.ctypes.data_as(C.c_void_p), _stream())
+
+
+def range_counts_sph(points, radii, spheres, tree, weights=None, counts=None, out=None, check=False, period=None):
     """Every sphere centre within the query point's own radius (an extension the reference lacks):
     sphere j is in range of point p iff d2 <= fl(r_p * r_p), d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz))
     in fp32 -- inclusive; the spheres' w is ignored.  counts[p] = the number of spheres in range, and
@@ -903,7 +918,10 @@ def range_counts_sph(points, radii, spheres, tree, weights=None, counts=None, ou
     points: float32 [n, 3..16] (x y z first); radii: a float, or float32 [n] in the order of points;
     weights: float32 [n_spheres] or [n_spheres, C] (1 <= C <= 64) in the order of `spheres` (tree order:
     build_tree(want_perm=True)).  A point with a non-finite coordinate or a negative, NaN or infinite
-    radius gets 0.  Returns (counts int32 [n], sums float32 [n] / [n, C] or None without weights)."""
+    radius gets 0.  period: None, or (Lx, Ly, Lz) for a periodic box (0 leaves an axis open): every
+    component of p - x is wrapped once into [-L/2, L/2] before it is squared (include/grace_hip.h states
+    the arithmetic), a point whose radius exceeds half a period gets 0, and a scalar radius that does is
+    refused.  Returns (counts int32 [n], sums float32 [n] / [n, C] or None without weights)."""
     points, rt, rs = _range_args(points, radii)
     n = len(points)
     if counts is None:
@@ -911,26 +929,36 @@ def range_counts_sph(points, radii, spheres, tree, weights=None, counts=None, ou
     n_ch, out, counts = _interp_outputs(n, len(spheres), weights, out, counts, points.device)
     if weights is not None:
         weights = weights.contiguous()
-    _check(_lib.grace_range_counts_f4(_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]), _ptr(rt), C.c_float(rs),
-                                      *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
-                                      _ptr(counts), _ptr(out), _stream()))
+    args = (_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]), _ptr(rt), C.c_float(rs),
+            *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch), _ptr(counts), _ptr(out))
+    if period is None:
+        _check(_lib.grace_range_counts_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_range_counts_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
     return counts, out
 
 
-def range_neighbours_sph(points, radii, spheres, tree, want_d2=True, check=False):
+def range_neighbours_sph(points, radii, spheres, tree, want_d2=True, check=False, period=None):
     """The neighbour lists of range_counts_sph in CSR form: row p is [offsets[p], offsets[p + 1]) of
     indices (tree indices, ascending) and d2 (their fp32 squared distances).  Counts, the library's
     scan, then the fill; synchronises to read the total.  ValueError if the lists hold more than
-    INT32_MAX entries (split the points).  Returns (offsets int32 [n + 1], indices int32 [total],
-    d2 float32 [total] or None)."""
+    INT32_MAX entries (split the points).  period: as for range_counts_sph; d2 is the wrapped one.
+    Returns (offsets int32 [n + 1], indices int32 [total], d2 float32 [total] or None)."""
     points, rt, rs = _range_args(points, radii)
     n = len(points)
     offsets = torch.zeros(n + 1, dtype=torch.int32, device=points.device)
     args = (_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]), _ptr(rt), C.c_float(rs),
             *_interp_scene(spheres, tree))
-    _check(_lib.grace_range_counts_f4(*args, _ptr(None), C.c_int(0), _ptr(offsets), _ptr(None), _stream()))
+    if period is None:
+        count_fn, fill_fn, tail = _lib.grace_range_counts_f4, _lib.grace_range_neighbours_f4, (_stream(),)
+    else:
+        period = _period(period)
+        count_fn, fill_fn = _lib.grace_range_counts_periodic_f4, _lib.grace_range_neighbours_periodic_f4
+        tail = _period_tail(period)
+    _check(count_fn(*args, _ptr(None), C.c_int(0), _ptr(offsets), _ptr(None), *tail))
     total = exclusive_scan(offsets, offsets)
     if total > INT32_MAX:
         raise ValueError("range_neighbours_sph: %d list entries exceed INT32_MAX; the int offsets cannot "
@@ -938,27 +966,33 @@ def range_neighbours_sph(points, radii, spheres, tree, want_d2=True, check=False
     indices = torch.empty(total, dtype=torch.int32, device=points.device)
     d2 = torch.empty(total, dtype=torch.float32, device=points.device) if want_d2 else None
     if total:                  # (no list entries: every row is empty, nothing to fill)
-        _check(_lib.grace_range_neighbours_f4(*args, _ptr(offsets), _ptr(indices), _ptr(d2), _stream()))
+        _check(fill_fn(*args, _ptr(offsets), _ptr(indices), _ptr(d2), *tail))
     if check:
         trace_status()
     return offsets, indices, d2
 
 
-def fof_labels_sph(spheres, tree, linking_length, labels=None, check=False):
+def fof_labels_sph(spheres, tree, linking_length, labels=None, check=False, period=None):
     """Friends-of-friends groups (an extension the reference lacks): spheres i and j (tree order; their
     w is ignored) are linked iff d2 <= fl(b * b), b the linking length,
     d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in fp32 -- inclusive, so b = 0 links coincident
     centres; groups are the connected components.  labels[i] = the smallest tree index in i's group:
     a function of the positions and b alone, bit-identical from run to run.  A sphere with a
-    non-finite coordinate is a group of one.  Returns labels int32 [n] (tree order: map them to the
-    caller's particles with the permutation of build_tree(want_perm=True))."""
+    non-finite coordinate is a group of one.  period: None, or (Lx, Ly, Lz) for a periodic box (0 leaves
+    an axis open): d is wrapped once per component as for range_counts_sph, so a group that straddles
+    a face is one group; a linking length above half a period is refused.  Returns labels int32 [n]
+    (tree order: map them to the caller's particles with the permutation of build_tree(want_perm=True))."""
     n = len(_spheres(spheres))
     if labels is None:
         labels = torch.empty(n, dtype=torch.int32, device=spheres.device)
     if labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
         raise ValueError("labels must be int32 of shape [%d]" % n)
-    _check(_lib.grace_fof_labels_f4(*_interp_scene(spheres, tree), C.c_float(float(linking_length)), _ptr(labels),
-                                    _stream()))
+    args = (*_interp_scene(spheres, tree), C.c_float(float(linking_length)), _ptr(labels))
+    if period is None:
+        _check(_lib.grace_fof_labels_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_fof_labels_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
     return labels
@@ -1003,16 +1037,21 @@ def _pair_edges(edges):
     return edges
 
 
-def _pair_call(points, edges, spheres, tree, weights, n_ch, totals, counts, sums, check):
-    _check(_lib.grace_pair_counts_f4(_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
-                                     edges.ctypes.data_as(C.c_void_p), C.c_int(len(edges)),
-                                     *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
-                                     _ptr(totals), _ptr(counts), _ptr(sums), _stream()))
+def _pair_call(points, edges, spheres, tree, weights, n_ch, totals, counts, sums, check, period=None):
+    args = (_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
+            edges.ctypes.data_as(C.c_void_p), C.c_int(len(edges)),
+            *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
+            _ptr(totals), _ptr(counts), _ptr(sums))
+    if period is None:
+        _check(_lib.grace_pair_counts_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_pair_counts_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
 
 
-def pair_counts_sph(points, edges, spheres, tree, check=False):
+def pair_counts_sph(points, edges, spheres, tree, check=False, period=None):
     """Pair counts in separation bins (an extension the reference lacks): totals[k] = the number of
     (point, sphere) pairs whose d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) (fp32) falls in bin k,
     the smallest k with d2 <= fl(e_k * e_k) -- bin 0 holds d2 <= fl(e_0 e_0) (with e_0 = 0 the
@@ -1022,25 +1061,28 @@ def pair_counts_sph(points, edges, spheres, tree, check=False):
     counted twice and every self pair once, so DD = (totals - [n, 0, 0, ...]) // 2.
     points: float32 [n, 3..16] (x y z first); edges: 1..64 floats (a sequence, array or tensor; read on
     the host), finite, not negative, strictly ascending.  A point with a non-finite coordinate is in
-    no pair.  Returns totals uint64 [n_edges]."""
+    no pair.  period: None, or (Lx, Ly, Lz) for a periodic box (0 leaves an axis open): d is wrapped
+    once per component as for range_counts_sph, each pair is still counted once, and a last edge above
+    half a period is refused -- the DD(r) on the torus that an analytic RR goes with.
+    Returns totals uint64 [n_edges]."""
     if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
         raise ValueError("points must be float32 of shape [n, 3..16]")
     points = points.contiguous()
     edges = _pair_edges(edges)
     totals = torch.empty(len(edges), dtype=torch.uint64, device=points.device)
-    _pair_call(points, edges, spheres, tree, None, 0, totals, None, None, check)
+    _pair_call(points, edges, spheres, tree, None, 0, totals, None, None, check, period)
     return totals
 
 
-def radial_profiles_sph(points, edges, spheres, tree, weights=None, check=False):
+def radial_profiles_sph(points, edges, spheres, tree, weights=None, check=False, period=None):
     """The per-point form of pair_counts_sph: counts[p, k] = the number of sphere centres in bin k of
     point p, and with weights sums[p, k, c] = the sum of weights[j, c] over those spheres in ascending
     tree index j, a plain fp32 running sum (no SPH kernel): counts and mass in shells around each point;
     the cumulative profile is a cumsum over k.  counts.cumsum(1)[:, k] is range_counts_sph at radius
     e_k.  weights: float32 [n_spheres] or [n_spheres, C], 1 <= C <= 4 and n_edges * C <= 64, in the
     order of `spheres` (tree order: build_tree(want_perm=True)).  A point with a non-finite coordinate
-    gets zeros.  Returns (counts int32 [n, n_edges], sums float32 [n, n_edges] / [n, n_edges, C] or None
-    without weights)."""
+    gets zeros.  period: as for pair_counts_sph.  Returns (counts int32 [n, n_edges], sums float32
+    [n, n_edges] / [n, n_edges, C] or None without weights)."""
     if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
         raise ValueError("points must be float32 of shape [n, 3..16]")
     points = points.contiguous()
@@ -1057,7 +1099,7 @@ def radial_profiles_sph(points, edges, spheres, tree, weights=None, check=False)
         weights = weights.contiguous()
         sums = torch.empty((n, ne) if weights.dim() == 1 else (n, ne, n_ch), dtype=torch.float32,
                            device=points.device)
-    _pair_call(points, edges, spheres, tree, weights, n_ch, None, counts, sums, check)
+    _pair_call(points, edges, spheres, tree, weights, n_ch, None, counts, sums, check, period)
     return counts, sums
 
 

@@ -1,15 +1,19 @@
 """Gadget-2 (format 1) snapshot I/O for the SPH fields GRACE uses: gas positions and
 smoothing lengths, positions and masses of any particle type (read_gadget_particles), and the
-velocities and gas fields a sightline spectrum needs (read_gadget_fields).
+velocities and gas fields a sightline spectrum needs (read_gadget_fields), and the header's
+fields (read_gadget_header: the particle counts, the masses, the time, the redshift and the box
+size a periodic query needs).
 Block layout as read by the reference's tests/helper/read_gadget.cuh: header of 256 B
-(npart[6] int32, mass[6] float64, padding) and POS, VEL, ID, [MASS], U, RHO, HSML blocks,
+(npart[6] int32, mass[6] float64, time and redshift float64, ..., BoxSize float64 at byte 128,
+..., padding) and POS, VEL, ID, [MASS], U, RHO, HSML blocks,
 every block framed by 4-byte markers.  Host-side file I/O only (numpy)."""
 import numpy as np
 
 
-def write_gadget(fname, pos, hsml, masses_in_header=True, vel=None, u=None):
+def write_gadget(fname, pos, hsml, masses_in_header=True, vel=None, u=None, box_size=0.0):
     """Writes a gas-only snapshot: pos [N,3] float32, hsml [N] float32; vel [N,3] and u [N]
-    float32 fill the VEL and U blocks (zeros when None)."""
+    float32 fill the VEL and U blocks (zeros when None); box_size is the header's BoxSize (0: the
+    zero bytes of a header without one)."""
     pos = np.ascontiguousarray(pos, np.float32); hsml = np.ascontiguousarray(hsml, np.float32)
     n = len(pos)
     vel = np.zeros((n, 3), np.float32) if vel is None else np.ascontiguousarray(vel, np.float32)
@@ -25,6 +29,7 @@ def write_gadget(fname, pos, hsml, masses_in_header=True, vel=None, u=None):
 
     with open(fname, "wb") as f:
         header = npart.tobytes() + mass.tobytes()
+        header = header + bytes(128 - len(header)) + np.array([box_size], np.float64).tobytes()
         block(f, header + bytes(256 - len(header)))
         block(f, pos.tobytes())                                   # POS
         block(f, vel.tobytes())                                   # VEL
@@ -34,6 +39,27 @@ def write_gadget(fname, pos, hsml, masses_in_header=True, vel=None, u=None):
         block(f, u.tobytes())                                     # U
         block(f, np.ones(n, np.float32).tobytes())                # RHO
         block(f, hsml.tobytes())                                  # HSML
+
+
+def read_gadget_header(fname):
+    """Returns the header's fields as a dict: "npart" (6 ints) and "mass" (6 floats), "time" and
+    "redshift" (the float64 at bytes 72 and 80), "flag_sfr" and "flag_feedback" (int32 at 88 and
+    92), "npart_total" (6 ints at 96), "flag_cooling" and "num_files" (int32 at 120 and 124) and
+    "box_size", "omega0", "omega_lambda" and "hubble_param" (float64 at 128, 136, 144 and 152).
+    box_size is the period of a periodic snapshot, in the units of the positions."""
+    with open(fname, "rb") as f:
+        raw = f.read(4 + 256)
+    if len(raw) < 260 or int(np.frombuffer(raw[:4], np.int32)[0]) != 256:
+        raise RuntimeError("Gadget file %s does not start with a 256-byte header block" % fname)
+    h = np.frombuffer(raw[4:], np.uint8)
+    f64 = lambda at: float(h[at:at + 8].view(np.float64)[0])
+    i32 = lambda at: int(h[at:at + 4].view(np.int32)[0])
+    return {"npart": [int(x) for x in h[:24].view(np.int32)],
+            "mass": [float(x) for x in h[24:72].view(np.float64)],
+            "time": f64(72), "redshift": f64(80), "flag_sfr": i32(88), "flag_feedback": i32(92),
+            "npart_total": [int(x) for x in h[96:120].view(np.uint32)],
+            "flag_cooling": i32(120), "num_files": i32(124),
+            "box_size": f64(128), "omega0": f64(136), "omega_lambda": f64(144), "hubble_param": f64(152)}
 
 
 def read_gadget(fname):

@@ -5,11 +5,15 @@
 // catalogue built from them -- grace_fof_labels_f4 / grace_fof_groups / grace_fof_members
 // (grace_hip.h states the fp32 distance, the inclusive test d2 <= fl(b b), the labels and the
 // catalogue's order).  Spheres in tree order; their w is ignored.  float4 spheres only.  A stack
-// overflow is reported as by the traces.  Not provided: periodic boxes, per-particle linking
-// lengths, double4 spheres, more than INT32_MAX spheres, unbinding or sub-halo finding, groups
-// ordered by size (one argsort of d_sizes by the caller).
+// overflow is reported as by the traces.  fof_labels_sph has an overload with a trailing
+// grace::PeriodicBox (grace/detail/periodic_box.h): the separation wraps once per component, so a
+// group that straddles a face of the box is one group (grace_fof_labels_periodic_f4); a linking
+// length above half a period is refused.  Not provided: per-particle linking lengths, double4
+// spheres, more than INT32_MAX spheres, unbinding or sub-halo finding, groups ordered by size (one
+// argsort of d_sizes by the caller).
 #pragma once
 
+#include "grace/detail/periodic_box.h"
 #include "grace/detail/trace_sph.h"
 
 namespace grace {
@@ -24,6 +28,20 @@ GRACE_HOST void fof_labels_sph(const detail::dvec<Real4>& d_spheres, const Tree&
     d_labels.resize(d_spheres.size());
     const detail::SceneArgs<Real4> a = detail::scene_args(d_spheres, d_tree);
     GRACE_STATUS_CHECK(grace_fof_labels_f4(GRACE_SCENE(a), linking_length, detail::raw(d_labels), NULL));
+    detail::check_trace_status();
+}
+
+// ... in a periodic box.
+template <typename Real4>
+GRACE_HOST void fof_labels_sph(const detail::dvec<Real4>& d_spheres, const Tree& d_tree, const float linking_length,
+                               detail::dvec<int>& d_labels, const PeriodicBox& box)
+{
+    static_assert(std::is_same<Real4, float4>::value, "friends-of-friends: float4 spheres only (float distances)");
+    d_labels.resize(d_spheres.size());
+    const detail::SceneArgs<Real4> a = detail::scene_args(d_spheres, d_tree);
+    const float period[3] = { box.lx, box.ly, box.lz };
+    GRACE_STATUS_CHECK(grace_fof_labels_periodic_f4(GRACE_SCENE(a), linking_length, detail::raw(d_labels), period,
+                                                    NULL));
     detail::check_trace_status();
 }
 

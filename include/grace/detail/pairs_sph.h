@@ -9,10 +9,15 @@
 // n_channels (1..4, n_edges * n_channels <= 64) weights per sphere, sphere-major, in the order of
 // d_spheres; d_counts[p * n_edges + k]; d_sums[(p * n_edges + k) * n_channels + c].  float4 spheres
 // only; points are 3..16 floats, x y z first.  Size mismatches throw std::invalid_argument; a stack
-// overflow is reported as by the traces.  Not provided: periodic boxes, double4 spheres, weighted
-// totals, halving the work for auto-pairs, estimators (Landy-Szalay, xi(r)), per-point edge lists.
+// overflow is reported as by the traces.  Every function has an overload with a trailing
+// grace::PeriodicBox (grace/detail/periodic_box.h): the separation wraps once per component and each
+// pair is still counted once -- the DD(r) on the torus that an analytic RR goes with
+// (grace_pair_counts_periodic_f4); a last edge above half a period is refused.  Not provided:
+// double4 spheres, weighted totals, halving the work for auto-pairs, estimators (Landy-Szalay,
+// xi(r)), per-point edge lists.
 #pragma once
 
+#include "grace/detail/periodic_box.h"
 #include "grace/detail/trace_sph.h"
 
 #include <stdexcept>
@@ -22,21 +27,31 @@ namespace grace {
 
 namespace detail {
 
-// The one call of grace_pair_counts_f4; any of totals / counts / sums may be NULL.
+// The one call of grace_pair_counts_f4 (box NULL) or grace_pair_counts_periodic_f4; any of totals /
+// counts / sums may be NULL.
 template <typename PointType, typename Real4>
 inline void pair_counts_call(const dvec<PointType>& d_points, const std::vector<float>& edges,
                              const dvec<Real4>& d_spheres, const Tree& d_tree, const float* weights,
-                             const int n_channels, unsigned long long* totals, int* counts, float* sums)
+                             const int n_channels, unsigned long long* totals, int* counts, float* sums,
+                             const PeriodicBox* box = NULL)
 {
     static_assert(std::is_same<Real4, float4>::value, "pair counts: float4 spheres only (float edges, distances and sums)");
     static_assert(sizeof(PointType) % sizeof(float) == 0 && sizeof(PointType) >= 3 * sizeof(float)
                       && sizeof(PointType) <= 16 * sizeof(float),
                   "pair counts: points are 3..16 floats, x y z first");
     const SceneArgs<Real4> a = scene_args(d_spheres, d_tree);
-    GRACE_STATUS_CHECK(grace_pair_counts_f4(
-        reinterpret_cast<const float*>(raw(d_points)), d_points.size(), int(sizeof(PointType) / sizeof(float)),
-        edges.empty() ? NULL : &edges[0], int(edges.size()), GRACE_SCENE(a), weights, n_channels, totals, counts,
-        sums, NULL));
+    if (box) {
+        const float period[3] = { box->lx, box->ly, box->lz };
+        GRACE_STATUS_CHECK(grace_pair_counts_periodic_f4(
+            reinterpret_cast<const float*>(raw(d_points)), d_points.size(), int(sizeof(PointType) / sizeof(float)),
+            edges.empty() ? NULL : &edges[0], int(edges.size()), GRACE_SCENE(a), weights, n_channels, totals, counts,
+            sums, period, NULL));
+    } else {
+        GRACE_STATUS_CHECK(grace_pair_counts_f4(
+            reinterpret_cast<const float*>(raw(d_points)), d_points.size(), int(sizeof(PointType) / sizeof(float)),
+            edges.empty() ? NULL : &edges[0], int(edges.size()), GRACE_SCENE(a), weights, n_channels, totals, counts,
+            sums, NULL));
+    }
     check_trace_status();
 }
 
@@ -82,6 +97,43 @@ GRACE_HOST void radial_profiles_sph(const detail::dvec<PointType>& d_points, con
     d_sums.resize(d_points.size() * edges.size() * size_t(n_channels));
     detail::pair_counts_call(d_points, edges, d_spheres, d_tree, detail::raw(d_weights), n_channels,
                              (unsigned long long*)NULL, detail::raw(d_counts), detail::raw(d_sums));
+}
+
+// ---- the same in a periodic box: the separation wraps once per component ----
+template <typename PointType, typename Real4>
+GRACE_HOST void pair_counts_sph(const detail::dvec<PointType>& d_points, const std::vector<float>& edges,
+                                const detail::dvec<Real4>& d_spheres, const Tree& d_tree,
+                                detail::dvec<unsigned long long>& d_totals, const PeriodicBox& box)
+{
+    d_totals.resize(edges.size());
+    detail::pair_counts_call(d_points, edges, d_spheres, d_tree, (const float*)NULL, 0, detail::raw(d_totals),
+                             (int*)NULL, (float*)NULL, &box);
+}
+
+template <typename PointType, typename Real4>
+GRACE_HOST void radial_profiles_sph(const detail::dvec<PointType>& d_points, const std::vector<float>& edges,
+                                    const detail::dvec<Real4>& d_spheres, const Tree& d_tree,
+                                    detail::dvec<int>& d_counts, const PeriodicBox& box)
+{
+    d_counts.resize(d_points.size() * edges.size());
+    detail::pair_counts_call(d_points, edges, d_spheres, d_tree, (const float*)NULL, 0, (unsigned long long*)NULL,
+                             detail::raw(d_counts), (float*)NULL, &box);
+}
+
+template <typename PointType, typename Real4>
+GRACE_HOST void radial_profiles_sph(const detail::dvec<PointType>& d_points, const std::vector<float>& edges,
+                                    const detail::dvec<Real4>& d_spheres, const Tree& d_tree,
+                                    detail::dvec<int>& d_counts, const detail::dvec<float>& d_weights,
+                                    const int n_channels, detail::dvec<float>& d_sums, const PeriodicBox& box)
+{
+    if (n_channels < 1 || n_channels > 4 || edges.size() * size_t(n_channels) > 64)
+        throw std::invalid_argument("radial_profiles_sph: n_channels must be 1..4 and n_edges * n_channels <= 64");
+    if (d_weights.size() != d_spheres.size() * size_t(n_channels))
+        throw std::invalid_argument("radial_profiles_sph: d_weights must hold n_channels per sphere");
+    d_counts.resize(d_points.size() * edges.size());
+    d_sums.resize(d_points.size() * edges.size() * size_t(n_channels));
+    detail::pair_counts_call(d_points, edges, d_spheres, d_tree, detail::raw(d_weights), n_channels,
+                             (unsigned long long*)NULL, detail::raw(d_counts), detail::raw(d_sums), &box);
 }
 
 } // namespace grace

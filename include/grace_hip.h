@@ -943,8 +943,9 @@ grace_status grace_neighbours_last_stats(unsigned long long* h_candidate_tests, 
  * (GRACE_STACK_OVERFLOW); nothing is written out of bounds.  Stream-ordered, no host
  * synchronisation, no allocation (the context workspace): capturable.  grace_trace_enable_timing /
  * grace_trace_last_kernel_ms time the walks of the last call.
- * Not provided: symmetric criteria (max(h_p, H_j)), periodic boxes, double4 spheres, 64-bit
- * offsets (split the points when the lists exceed INT32_MAX entries). */
+ * Periodic boxes: grace_range_counts_periodic_f4 / grace_range_neighbours_periodic_f4 below.
+ * Not provided: symmetric criteria (max(h_p, H_j)), double4 spheres, 64-bit offsets (split the
+ * points when the lists exceed INT32_MAX entries). */
 grace_status grace_range_counts_f4(const float* d_points, size_t n_points, int elems_per_point,
                                    const float* d_radii, float radius,
                                    const float* d_spheres, size_t n_spheres, const int* d_nodes,
@@ -1006,9 +1007,9 @@ grace_status grace_range_neighbours_f4(const float* d_points, size_t n_points, i
  *
  * All three are stream-ordered, without host synchronisation or allocation (the context
  * workspace): capturable.
- * Not provided: periodic boxes, per-particle linking lengths, double4 spheres, more than INT32_MAX
- * spheres, unbinding or sub-halo finding, groups ordered by size (one argsort of d_sizes by the
- * caller). */
+ * Periodic boxes: grace_fof_labels_periodic_f4 below; the catalogue is the same.
+ * Not provided: per-particle linking lengths, double4 spheres, more than INT32_MAX spheres,
+ * unbinding or sub-halo finding, groups ordered by size (one argsort of d_sizes by the caller). */
 grace_status grace_fof_labels_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
                                  size_t n_nodes, const int* d_leaves, const int* d_root,
                                  float linking_length, int* d_labels, grace_stream stream);
@@ -1064,9 +1065,10 @@ grace_status grace_fof_members(const int* d_group_of, size_t n, const int* d_siz
  * (GRACE_STACK_OVERFLOW); nothing is written out of bounds.  Stream-ordered, no host
  * synchronisation, no allocation (the context workspace): capturable.  grace_trace_enable_timing /
  * grace_trace_last_kernel_ms time the walk of the last call.
- * Not provided: periodic boxes, double4 spheres, weighted totals (sum d_sums in fp64), halving the
- * work for auto-pairs (points that are the centres are walked from both ends), estimators
- * (Landy-Szalay, xi(r)), per-point edge lists. */
+ * Periodic boxes: grace_pair_counts_periodic_f4 below.
+ * Not provided: double4 spheres, weighted totals (sum d_sums in fp64), halving the work for
+ * auto-pairs (points that are the centres are walked from both ends), estimators (Landy-Szalay,
+ * xi(r)), per-point edge lists. */
 grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int elems_per_point,
                                   const float* h_edges, int n_edges,
                                   const float* d_spheres, size_t n_spheres, const int* d_nodes,
@@ -1074,6 +1076,75 @@ grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int el
                                   const float* d_weights, int n_channels,
                                   unsigned long long* d_totals, int* d_counts, float* d_sums,
                                   grace_stream stream);
+
+/* ---- Periodic boxes for the range queries, friends-of-friends and pair counts -------------------
+ * (an extension the reference lacks)
+ * The three families above on a torus: a cosmological snapshot is a periodic box, and a halo that
+ * straddles a face, the pairs across it and the neighbours beyond it belong to the answer.  Each
+ * function below takes the arguments of its open counterpart plus h_period3 before the stream, and
+ * is that counterpart in everything this block does not restate: arguments, outputs, order, off
+ * points, status word, stream ordering, timing.
+ *
+ * Period: h_period3 is a HOST array of three floats L = (Lx, Ly, Lz), read at call time (it travels in
+ * the kernel arguments: no device copy, no host synchronisation).  L_a == 0: the axis is open, no
+ * wrapping on it.  Any L_a that is negative, NaN or infinite: GRACE_INVALID_ARGUMENT before
+ * anything is enqueued.  No box origin is needed: the arithmetic below is defined for any
+ * coordinates.
+ *
+ * Separation (fp32, every operation rounded, none fused, each component on its own):
+ * d = fl(p - x);  h = fl(0.5 * L_a) (exact).  If d > h: d = fl(d - L_a); otherwise, if d < -h:
+ * d = fl(d + L_a).  At most one wrap; an open axis gets none.  Then
+ * d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), as above.  Everything downstream uses this d2
+ * unchanged: membership d2 <= fl(r r), the d2 returned in lists, the bin of a pair (the smallest k
+ * with d2 <= fl(e_k e_k)), W(sqrt(d2), r_p) in the gather sums, the link d2 <= fl(b b).  The
+ * separation is antisymmetric bit for bit -- fl(p - x) = -fl(x - p), the two wraps mirror each other
+ * and fl(d - L) = -fl(-d + L) -- so d2 is symmetric and a link is still seen once, from its upper
+ * index.
+ * Each centre is tested once per point, not once per image: a pair appears at most once in a list,
+ * a count or a bin, pairs at exactly half a period included (d == h and d == -h are not wrapped).
+ *
+ * Radius: a query point is additionally OFF if r_p > fl(0.5 * L_a) on any periodic axis: an empty
+ * row, count 0, sums 0, no bins -- the treatment r = +inf gets above.  Where the radius is a host
+ * scalar (`radius` with d_radii NULL, the linking length, the last edge), a value above
+ * fl(0.5 * L_a) on a periodic axis is GRACE_INVALID_ARGUMENT, nothing written.
+ *
+ * Identities, bit for bit: L = (0, 0, 0) gives the open function's output; so does any finite L larger
+ * than twice the extent of points and centres together on every axis (no |d| exceeds h).  Lists and
+ * running sums are in ascending tree index, as above.  The result is a function of the points, the
+ * radii (edges, linking length), the centres, the weights and L only: not of the H the tree was
+ * built with (any H >= 0), of max_per_leaf, of the packets or of the stream.
+ *
+ * GRACE_INVALID_ARGUMENT, nothing written: a NULL h_period3, a bad period, a host radius above half
+ * a period, and whatever the open counterpart refuses.  (The period is checked first by the range
+ * queries and friends-of-friends, after the edges by the pair counts.)  Zero points or spheres: as
+ * the open counterpart, after the period's check.
+ * Not provided: periodic ray traces, interpolation (grace_interpolate_*) and nearest neighbours
+ * (grace_nearest_neighbours_f4 / grace_smoothing_lengths_f4); a box origin (none is needed);
+ * radii above half a period (more than one image of a centre in range). */
+grace_status grace_range_counts_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                            const float* d_radii, float radius,
+                                            const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                            size_t n_nodes, const int* d_leaves, const int* d_root,
+                                            const float* d_weights, int n_channels,
+                                            int* d_counts, float* d_sums, const float* h_period3,
+                                            grace_stream stream);
+grace_status grace_range_neighbours_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                const float* d_radii, float radius,
+                                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                const int* d_offsets, int* d_indices, float* d_d2,
+                                                const float* h_period3, grace_stream stream);
+grace_status grace_fof_labels_periodic_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                          size_t n_nodes, const int* d_leaves, const int* d_root,
+                                          float linking_length, int* d_labels, const float* h_period3,
+                                          grace_stream stream);
+grace_status grace_pair_counts_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                           const float* h_edges, int n_edges,
+                                           const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                           size_t n_nodes, const int* d_leaves, const int* d_root,
+                                           const float* d_weights, int n_channels,
+                                           unsigned long long* d_totals, int* d_counts, float* d_sums,
+                                           const float* h_period3, grace_stream stream);
 
 #ifdef __cplusplus
 }
