@@ -36,6 +36,16 @@ struct Interleave<uint64_t> {
     }
 };
 
+// Host-side scale of one axis in Real3 precision, integer span (morton.cuh:104-113).  An axis
+// the box does not extend along (top == bot, any planar scene) has scale 0: every primitive
+// inside the box then falls in cell 0 of that axis, instead of span / 0 * 0 = NaN cast to an
+// integer.
+template <typename Real>
+inline Real key_scale(int span, Real bot, Real top)
+{
+    return top == bot ? Real(0) : span / (top - bot);
+}
+
 // Real is the precision of the bounds (Real3 in the reference): scale * (centre - min) is
 // evaluated in Real, the float centre being promoted when Real = double.
 template <typename Key, typename Real>
@@ -142,11 +152,10 @@ grace_status morton_keys(const float* d_spheres, size_t n, const Real* bot, cons
 {
     GRACE_REQUIRE(d_spheres && d_keys && bot && top, "morton_keys: null pointer");
     if (n == 0) return GRACE_OK;
-    // Host-side scale in Real3 precision, integer span (morton.cuh:104-113).
     const int span = sizeof(Key) > 4 ? (1u << 21) - 1 : (1u << 10) - 1;
-    const Real sx = span / (top[0] - bot[0]);
-    const Real sy = span / (top[1] - bot[1]);
-    const Real sz = span / (top[2] - bot[2]);
+    const Real sx = key_scale(span, bot[0], top[0]);
+    const Real sy = key_scale(span, bot[1], top[1]);
+    const Real sz = key_scale(span, bot[2], top[2]);
     morton_keys_kernel<Key, Real><<<stream_grid(n, 256), 256, 0, stream>>>(
         reinterpret_cast<const float4*>(d_spheres), n, bot[0], bot[1], bot[2], sx, sy, sz,
         d_keys);
@@ -186,9 +195,9 @@ grace_status morton_keys_points(const void* d_points, size_t n, int is_double, i
     GRACE_REQUIRE(stride >= 3 && stride <= 16, "morton_keys (points): elements per point must be 3..16");
     if (n == 0) return GRACE_OK;
     const int span = sizeof(Key) > 4 ? (1u << 21) - 1 : (1u << 10) - 1;
-    const Real sx = span / (top[0] - bot[0]);
-    const Real sy = span / (top[1] - bot[1]);
-    const Real sz = span / (top[2] - bot[2]);
+    const Real sx = key_scale(span, bot[0], top[0]);
+    const Real sy = key_scale(span, bot[1], top[1]);
+    const Real sz = key_scale(span, bot[2], top[2]);
     if (is_double)
         morton_keys_points_kernel<Key, double, Real><<<stream_grid(n, 256), 256, 0, stream>>>(
             static_cast<const double*>(d_points), n, stride, bot[0], bot[1], bot[2], sx, sy, sz,
@@ -332,9 +341,9 @@ grace_status grace_morton_keys30_tri(const float* d_tris, size_t n, const float*
     GRACE_REQUIRE(d_tris && d_keys && h_bot && h_top, "morton_keys_tri: null pointer");
     if (n == 0) return GRACE_OK;
     const int span = (1u << 10) - 1;
-    const float sx = span / (h_top[0] - h_bot[0]);
-    const float sy = span / (h_top[1] - h_bot[1]);
-    const float sz = span / (h_top[2] - h_bot[2]);
+    const float sx = key_scale(span, h_bot[0], h_top[0]);
+    const float sy = key_scale(span, h_bot[1], h_top[1]);
+    const float sz = key_scale(span, h_bot[2], h_top[2]);
     morton_keys_tri_kernel<<<stream_grid(n, 256), 256, 0, as_stream(stream)>>>(
         d_tris, n, h_bot[0], h_bot[1], h_bot[2], sx, sy, sz, d_keys);
     GRACE_CHECK_LAUNCH();

@@ -26,13 +26,14 @@ __global__ __launch_bounds__(256) void ortho_z_kernel(int n_side, float cam_x, f
                                                       float cam_z, float vx, float uy,
                                                       float length, float* __restrict__ rays)
 {
-    const int n = n_side * n_side;
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        const int i = t % n_side, j = t / n_side;
+    const size_t n = size_t(n_side) * n_side;
+    for (size_t t = blockIdx.x * size_t(blockDim.x) + threadIdx.x; t < n;
+         t += size_t(gridDim.x) * blockDim.x) {
+        const int i = int(t % size_t(n_side)), j = int(t / size_t(n_side));
         // image_plane_coord, gen_rays.cuh:76-97 (+0.5 = pixel centres), aspect ratio 1.
         const float x = (2 * ((i + 0.5f) / n_side) - 1) * 1.0f;
         const float y = 1 - 2 * ((j + 0.5f) / n_side);
-        float* r = rays + 7 * size_t(t);
+        float* r = rays + 7 * t;
         r[0] = 0.f; r[1] = 0.f; r[2] = -1.f;
         r[3] = cam_x + x * vx;
         r[4] = cam_y + y * uy;
@@ -92,16 +93,17 @@ __global__ __launch_bounds__(256) void pinhole_kernel(int res_x, int res_y, floa
                                                       float uz, float nx, float ny, float nz,
                                                       float length, float* __restrict__ rays)
 {
-    const int n = res_x * res_y;
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        const int i = t % res_x, j = t / res_x;
+    const size_t n = size_t(res_x) * res_y;
+    for (size_t t = blockIdx.x * size_t(blockDim.x) + threadIdx.x; t < n;
+         t += size_t(gridDim.x) * blockDim.x) {
+        const int i = int(t % size_t(res_x)), j = int(t / size_t(res_x));
         const float x = (2 * ((i + 0.5f) / res_x) - 1) * aspect;
         const float y = 1 - 2 * ((j + 0.5f) / res_y);
         const float dx = x * vx + y * ux + 1.f * nx;
         const float dy = x * vy + y * uy + 1.f * ny;
         const float dz = x * vz + y * uz + 1.f * nz;
         const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-        float* r = rays + 7 * size_t(t);
+        float* r = rays + 7 * t;
         r[0] = dx * inv; r[1] = dy * inv; r[2] = dz * inv;
         r[3] = cx; r[4] = cy; r[5] = cz; r[6] = length;
     }
@@ -316,6 +318,7 @@ grace_status grace_rays_pinhole(int res_x, int res_y, const float* h_camera, con
 {
     GRACE_REQUIRE(res_x > 0 && res_y > 0 && h_camera && h_look_at && h_view_up && d_rays,
                   "pinhole rays: bad argument");
+    GRACE_REQUIRE(size_t(res_x) * res_y < (size_t(1) << 31), "pinhole rays: too many rays");
     GRACE_TRY(rays_invalidate_if_written(d_rays));   // a prepared ray batch over this array is stale
     // pinhole_camera_rays, gen_rays.cuh:727-789 (Real = float; normalize3 in fp64 on the host)
     const float* c = h_camera;

@@ -100,7 +100,14 @@ grace_status grace_minmax_components(const void* d_data, size_t n, int elem_type
                                      size_t stride_bytes, void* h_mins, void* h_maxs,
                                      grace_stream stream);
 /* grace::morton_keys(prims, N, bot, top, keys, CentroidSphere) with uinteger32 keys and
- * Real3 = float3 (include/grace/cuda/kernels/morton.cuh:97-119,30-55; build_sph.cuh:27-35). */
+ * Real3 = float3 (include/grace/cuda/kernels/morton.cuh:97-119,30-55; build_sph.cuh:27-35).
+ * Per axis the cell is KeyType(scale * (centre - bot)), scale = span / (top - bot) rounded once
+ * on the host, span = 2^10 - 1 (2^21 - 1 for 63-bit keys).  In the unit box a centre at `top`
+ * falls in cell `span` exactly, so the key of the point at `top` on all three axes is all ones
+ * (in other boxes the rounded scale may leave it in cell span - 1).  An axis with top == bot (a
+ * planar scene through the bounds-free overloads) has scale 0, so every primitive gets cell 0 on
+ * it.  Centres outside [bot, top] are unspecified, as in the reference.  This holds for every
+ * grace_morton_keys* entry point below. */
 grace_status grace_morton_keys30_f4(const float* d_spheres, size_t n, const float* h_bot,
                                     const float* h_top, uint32_t* d_keys, grace_stream stream);
 /* Same with uinteger64 keys (63 bits); float3 and double3 bounds. */
@@ -659,7 +666,9 @@ grace_status grace_sort_by_distance_f64(double* d_distances, const int* d_ray_of
  * (tests/helper/rays.cuh:55-79; kernels/gen_rays.cuh:319-360,667-725). mins4/maxs4 host. */
 grace_status grace_rays_orthogonal_z(int n_side, const float* h_mins4, const float* h_maxs4,
                                      void* d_rays, float* h_area, grace_stream stream);
-/* pinhole_camera_rays (kernels/gen_rays.cuh:362-395,727-789), Real = float; fovy in radians. */
+/* pinhole_camera_rays (kernels/gen_rays.cuh:362-395,727-789), Real = float; fovy in radians.
+ * res_x * res_y must be below 2^31, as for orthogonal_z and plane_parallel_random: more is
+ * GRACE_INVALID_ARGUMENT and d_rays is not written. */
 grace_status grace_rays_pinhole(int res_x, int res_y, const float* h_camera, const float* h_look_at,
                                 const float* h_view_up, float fovy, float length, void* d_rays,
                                 grace_stream stream);

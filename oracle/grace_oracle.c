@@ -98,13 +98,17 @@ uint64_t go_morton_key63_unit(double x, double y, double z)
  * (include/grace/cuda/kernels/morton.cuh:107-113), key coordinate =
  * KeyType(scale * (centre - min)) per axis (morton.cuh:43-50); the centroid of a
  * sphere is its float3 centre (generic/functors/centroid.h:40-48). */
+/* An axis with top == bot has scale 0 (every centre inside the box falls in cell 0 of it)
+ * rather than span / 0; grace-devel_amd/csrc/morton.hip key_scale. */
+#define GO_KEY_SCALE(span, bot, top) ((top) == (bot) ? 0 : (span) / ((top) - (bot)))
+
 void go_morton_keys30_f4(const go_f4* prims, size_t n, const float* bot,
                          const float* top, uint32_t* keys)
 {
     const int span = (1u << 10) - 1;
-    float sx = span / (top[0] - bot[0]);
-    float sy = span / (top[1] - bot[1]);
-    float sz = span / (top[2] - bot[2]);
+    float sx = GO_KEY_SCALE(span, bot[0], top[0]);
+    float sy = GO_KEY_SCALE(span, bot[1], top[1]);
+    float sz = GO_KEY_SCALE(span, bot[2], top[2]);
     for (size_t i = 0; i < n; ++i) {
         uint32_t x = (uint32_t)(sx * (prims[i].x - bot[0]));
         uint32_t y = (uint32_t)(sy * (prims[i].y - bot[1]));
@@ -119,9 +123,9 @@ void go_morton_keys30_f4_omp(const go_f4* prims, size_t n, const float* bot,
                              const float* top, uint32_t* keys)
 {
     const int span = (1u << 10) - 1;
-    float sx = span / (top[0] - bot[0]);
-    float sy = span / (top[1] - bot[1]);
-    float sz = span / (top[2] - bot[2]);
+    float sx = GO_KEY_SCALE(span, bot[0], top[0]);
+    float sy = GO_KEY_SCALE(span, bot[1], top[1]);
+    float sz = GO_KEY_SCALE(span, bot[2], top[2]);
     #pragma omp parallel for schedule(static)
     for (size_t i = 0; i < n; ++i) {
         uint32_t x = (uint32_t)(sx * (prims[i].x - bot[0]));
@@ -136,9 +140,9 @@ void go_morton_keys63_f4(const go_f4* prims, size_t n, const float* bot,
                          const float* top, uint64_t* keys)
 {
     const int span = (1u << 21) - 1;
-    float sx = span / (top[0] - bot[0]);
-    float sy = span / (top[1] - bot[1]);
-    float sz = span / (top[2] - bot[2]);
+    float sx = GO_KEY_SCALE(span, bot[0], top[0]);
+    float sy = GO_KEY_SCALE(span, bot[1], top[1]);
+    float sz = GO_KEY_SCALE(span, bot[2], top[2]);
     for (size_t i = 0; i < n; ++i) {
         uint64_t x = (uint64_t)(sx * (prims[i].x - bot[0]));
         uint64_t y = (uint64_t)(sy * (prims[i].y - bot[1]));
@@ -152,15 +156,80 @@ void go_morton_keys63_f4_d3(const go_f4* prims, size_t n, const double* bot,
                             const double* top, uint64_t* keys)
 {
     const int span = (1u << 21) - 1;
-    double sx = span / (top[0] - bot[0]);
-    double sy = span / (top[1] - bot[1]);
-    double sz = span / (top[2] - bot[2]);
+    double sx = GO_KEY_SCALE(span, bot[0], top[0]);
+    double sy = GO_KEY_SCALE(span, bot[1], top[1]);
+    double sz = GO_KEY_SCALE(span, bot[2], top[2]);
     for (size_t i = 0; i < n; ++i) {
         uint64_t x = (uint64_t)(sx * (prims[i].x - bot[0]));
         uint64_t y = (uint64_t)(sy * (prims[i].y - bot[1]));
         uint64_t z = (uint64_t)(sz * (prims[i].z - bot[2]));
         keys[i] = go_morton_key63(x, y, z);
     }
+}
+
+/* 30-bit keys, Real3 = double3 bounds. */
+void go_morton_keys30_f4_d3(const go_f4* prims, size_t n, const double* bot,
+                            const double* top, uint32_t* keys)
+{
+    const int span = (1u << 10) - 1;
+    double sx = GO_KEY_SCALE(span, bot[0], top[0]);
+    double sy = GO_KEY_SCALE(span, bot[1], top[1]);
+    double sz = GO_KEY_SCALE(span, bot[2], top[2]);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t x = (uint32_t)(sx * (prims[i].x - bot[0]));
+        uint32_t y = (uint32_t)(sy * (prims[i].y - bot[1]));
+        uint32_t z = (uint32_t)(sz * (prims[i].z - bot[2]));
+        keys[i] = go_morton_key30(x, y, z);
+    }
+}
+
+/* Generic points: n records of `stride` floats (is_double 0) or doubles (1), x y z first.
+ * CentroidSphere narrows each co-ordinate to float before the key arithmetic
+ * (generic/functors/centroid.h:33-40); the rest is the loops above.  bits63 selects uint64
+ * keys, double_bounds the type behind bot / top. */
+static inline float point_coord(const void* pts, int is_double, size_t stride, size_t i, int k)
+{
+    return is_double ? (float)((const double*)pts)[i * stride + k]
+                     : ((const float*)pts)[i * stride + k];
+}
+
+void go_morton_keys_points(const void* pts, int is_double, int stride, size_t n, int bits63,
+                           int double_bounds, const void* bot, const void* top, void* keys)
+{
+    const int span = bits63 ? (1u << 21) - 1 : (1u << 10) - 1;
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t cell[3];
+        for (int k = 0; k < 3; ++k) {
+            const float c = point_coord(pts, is_double, (size_t)stride, i, k);
+            if (double_bounds) {
+                const double b = ((const double*)bot)[k], t = ((const double*)top)[k];
+                const double s = GO_KEY_SCALE(span, b, t);
+                const double v = s * (c - b);
+                cell[k] = bits63 ? (uint64_t)v : (uint64_t)(uint32_t)v;
+            } else {
+                const float b = ((const float*)bot)[k], t = ((const float*)top)[k];
+                const float s = GO_KEY_SCALE(span, b, t);
+                const float v = s * (c - b);
+                cell[k] = bits63 ? (uint64_t)v : (uint64_t)(uint32_t)v;
+            }
+        }
+        if (bits63) ((uint64_t*)keys)[i] = go_morton_key63(cell[0], cell[1], cell[2]);
+        else ((uint32_t*)keys)[i] = go_morton_key30((uint32_t)cell[0], (uint32_t)cell[1], (uint32_t)cell[2]);
+    }
+}
+
+/* min / max of the float-narrowed x y z of generic points (compute_centroids + min_vec3 /
+ * max_vec3 with CentroidSphere, kernels/morton.cuh:139-174). */
+void go_centroid_bounds_points(const void* pts, int is_double, int stride, size_t n, float* bot,
+                               float* top)
+{
+    for (int k = 0; k < 3; ++k) { bot[k] = INFINITY; top[k] = -INFINITY; }
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const float c = point_coord(pts, is_double, (size_t)stride, i, k);
+            if (c < bot[k]) bot[k] = c;
+            if (c > top[k]) top[k] = c;
+        }
 }
 
 /* Component-wise min/max of centroids: include/grace/cuda/kernels/morton.cuh:153-164
@@ -806,11 +875,23 @@ void go_healpix_pix2vec_nest(long nside, long ipix, double* vec)
     vec[0] = st * cos(phi); vec[1] = st * sin(phi); vec[2] = z;
 }
 
+/* Every pixel centre of one resolution: out[12 nside^2][3]. */
+void go_healpix_pix2vec_nest_all(long nside, double* out)
+{
+    const long npix = 12 * nside * nside;
+    for (long i = 0; i < npix; ++i) go_healpix_pix2vec_nest(nside, i, out + 3 * i);
+}
+
 /* 30-bit direction key used to order isotropic rays
  * (include/grace/cuda/kernels/gen_rays.cuh:38-43). */
 uint32_t go_ray_dir_morton_key(const go_ray* r)
 {
     return go_morton_key30_unit((r->dx + 1) / 2.f, (r->dy + 1) / 2.f, (r->dz + 1) / 2.f);
+}
+
+void go_ray_dir_morton_keys(const go_ray* rays, size_t n, uint32_t* keys)
+{
+    for (size_t i = 0; i < n; ++i) keys[i] = go_ray_dir_morton_key(&rays[i]);
 }
 
 /* orthographic_projection_rays (include/grace/cuda/kernels/gen_rays.cuh:319-360 and
@@ -880,7 +961,7 @@ void go_morton_keys30_tri(const go_tri* tris, size_t n, const float* bot, const 
                           uint32_t* keys)
 {
     const int span = (1u << 10) - 1;
-    float sx = span / (top[0] - bot[0]), sy = span / (top[1] - bot[1]), sz = span / (top[2] - bot[2]);
+    float sx = GO_KEY_SCALE(span, bot[0], top[0]), sy = GO_KEY_SCALE(span, bot[1], top[1]), sz = GO_KEY_SCALE(span, bot[2], top[2]);
     for (size_t i = 0; i < n; ++i) {
         float c[3]; tri_centroid(&tris[i], c);
         keys[i] = go_morton_key30((uint32_t)(sx * (c[0] - bot[0])), (uint32_t)(sy * (c[1] - bot[1])),
@@ -1081,6 +1162,42 @@ void go_deltas_euclid_d4(const double* s, size_t n, float* out)
         out[i + 1] = (float)((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1])
                              + (a[2] - b[2]) * (a[2] - b[2]));
     }
+}
+
+/* DeltaSurfaceArea on double4 (generic/functors/albvh.h:84-126): AABBSphere forms centre -+
+ * radius in double and narrows the corners to float3 (generic/functors/aabb.h:9-26); the merged
+ * extents and the area are fp32. */
+void go_deltas_area_d4(const double* s, size_t n, float* out)
+{
+    out[0] = INFINITY; out[n] = INFINITY;
+    for (size_t i = 0; i + 1 < n; ++i) {
+        const double* a = s + 4 * i; const double* b = s + 4 * (i + 1);
+        float L[3];
+        for (int k = 0; k < 3; ++k) {
+            const float bi = (float)(a[k] - a[3]), ti = (float)(a[k] + a[3]);
+            const float bj = (float)(b[k] - b[3]), tj = (float)(b[k] + b[3]);
+            L[k] = fmaxf(ti, tj) - fminf(bi, bj);
+        }
+        out[i + 1] = (L[0] * L[1]) + (L[0] * L[2]) + (L[1] * L[2]);
+    }
+}
+
+/* A device_vector<double> of deltas (build_tree<double4>, tests/helper/tree.cuh:20-24): the
+ * float the functor returns, widened. */
+void go_deltas_euclid_d4_f64(const double* s, size_t n, double* out)
+{
+    float* f = (float*)malloc((n + 1) * sizeof(float));
+    go_deltas_euclid_d4(s, n, f);
+    for (size_t i = 0; i <= n; ++i) out[i] = f[i];
+    free(f);
+}
+
+void go_deltas_area_d4_f64(const double* s, size_t n, double* out)
+{
+    float* f = (float*)malloc((n + 1) * sizeof(float));
+    go_deltas_area_d4(s, n, f);
+    for (size_t i = 0; i <= n; ++i) out[i] = f[i];
+    free(f);
 }
 
 /* sphere_hit<double4, double> (generic/intersect.h:9-55): ray members are float, everything

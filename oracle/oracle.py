@@ -99,6 +99,42 @@ def morton_keys30(prims, bot, top, all_threads=False, out=None):
     return keys
 
 
+def morton_keys30_d3(prims, bot, top):
+    """30-bit keys with Real3 = double3 bounds."""
+    prims = _f4(prims)
+    keys = np.empty(len(prims), np.uint32)
+    b = np.asarray(bot, np.float64); t = np.asarray(top, np.float64)
+    lib().go_morton_keys30_f4_d3(_p(prims), C.c_size_t(len(prims)), _p(b), _p(t), _p(keys))
+    return keys
+
+
+def _pts(points):
+    points = np.ascontiguousarray(points)
+    assert points.dtype in (np.float32, np.float64) and points.ndim == 2 and points.shape[1] >= 3
+    return points
+
+
+def morton_keys_points(points, bot, top, bits=30, double_bounds=False):
+    """Keys of generic points [n, k >= 3] float32 / float64 (narrowed to float first)."""
+    points = _pts(points)
+    keys = np.empty(len(points), np.uint64 if bits == 63 else np.uint32)
+    bt = np.float64 if double_bounds else np.float32
+    b = np.asarray(bot, bt); t = np.asarray(top, bt)
+    lib().go_morton_keys_points(_p(points), C.c_int(int(points.dtype == np.float64)),
+                                C.c_int(points.shape[1]), C.c_size_t(len(points)),
+                                C.c_int(int(bits == 63)), C.c_int(int(double_bounds)), _p(b), _p(t),
+                                _p(keys))
+    return keys
+
+
+def centroid_bounds_points(points):
+    points = _pts(points)
+    b = np.empty(3, np.float32); t = np.empty(3, np.float32)
+    lib().go_centroid_bounds_points(_p(points), C.c_int(int(points.dtype == np.float64)),
+                                    C.c_int(points.shape[1]), C.c_size_t(len(points)), _p(b), _p(t))
+    return b, t
+
+
 def morton_keys63(prims, bot, top, double_bounds=False):
     prims = _f4(prims)
     keys = np.empty(len(prims), np.uint64)
@@ -276,6 +312,27 @@ def healpix_dirs(nside):
     return out
 
 
+def healpix_dirs_all(nside):
+    """healpix_dirs in one call (go_healpix_pix2vec_nest_all)."""
+    out = np.empty((12 * nside * nside, 3), np.float64)
+    lib().go_healpix_pix2vec_nest_all(C.c_long(nside), _p(out))
+    return out
+
+
+def ref_healpix_dirs(nside, pixels=None):
+    """The reference's own pix2vec_nest (oracle/_ref) on `pixels` (default: all), or None."""
+    r = ref_healpix()
+    if r is None:
+        return None
+    pixels = range(12 * nside * nside) if pixels is None else pixels
+    v = (C.c_double * 3)()
+    out = np.empty((len(pixels), 3), np.float64)
+    for k, i in enumerate(pixels):
+        r.pix2vec_nest(nside, int(i), v)
+        out[k] = v[0], v[1], v[2]
+    return out
+
+
 def orthogonal_rays_z(n_side, mins4, maxs4):
     rays = np.empty(n_side * n_side, RAY_DTYPE)
     area = C.c_float(0)
@@ -290,6 +347,14 @@ def ray_dir_keys(rays):
     f.restype = C.c_uint32
     f.argtypes = [C.c_void_p]
     return np.array([f(rays[i:i + 1].ctypes.data) for i in range(len(rays))], np.uint32)
+
+
+def ray_dir_keys_all(rays):
+    """ray_dir_keys in one call (go_ray_dir_morton_keys)."""
+    rays = _rays(rays)
+    keys = np.empty(len(rays), np.uint32)
+    lib().go_ray_dir_morton_keys(_p(rays), C.c_size_t(len(rays)), _p(keys))
+    return keys
 
 
 # -- triangles (tests/profile_trace_triangle) -------------------------------------------
@@ -371,6 +436,21 @@ def deltas_euclid_d4(prims):
     prims = np.ascontiguousarray(prims, np.float64)
     out = np.empty(len(prims) + 1, np.float32)
     lib().go_deltas_euclid_d4(_p(prims), C.c_size_t(len(prims)), _p(out))
+    return out
+
+
+def deltas_euclid_d4_f64(prims):
+    prims = np.ascontiguousarray(prims, np.float64)
+    out = np.empty(len(prims) + 1, np.float64)
+    lib().go_deltas_euclid_d4_f64(_p(prims), C.c_size_t(len(prims)), _p(out))
+    return out
+
+
+def deltas_area_d4(prims, double_out=False):
+    prims = np.ascontiguousarray(prims, np.float64)
+    out = np.empty(len(prims) + 1, np.float64 if double_out else np.float32)
+    fn = lib().go_deltas_area_d4_f64 if double_out else lib().go_deltas_area_d4
+    fn(_p(prims), C.c_size_t(len(prims)), _p(out))
     return out
 
 

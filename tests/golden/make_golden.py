@@ -5,6 +5,9 @@ What each file pins, and where its numbers come from:
   healpix_nside4_ref.npy   192 pixel-centre vectors printed by the REFERENCE's own
                            chealpix.c (pix2vec_nest), compiled as it lies into
                            oracle/_ref/libchealpix_ref.so -- output of the reference itself.
+  healpix_nside{1,2,8,16}_ref.npy   the same for every pixel of four more resolutions:
+                           degenerate caps and belt (1, 2), and both parities of the belt's
+                           ring shift at sizes with inner cap rings (8, 16).
   kat.json                 known-answer values copied from the reference's tests
                            (tests/morton_key/30bit_key.cu:20-26, 63bit_key.cu:20-26) and the
                            three generator outputs recorded in SURVEY.md section 8c.
@@ -23,7 +26,17 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle as O  # noqa: E402
+from front_end_cases import HEALPIX_FIXTURES  # noqa: E402
+
+
+def healpix_fixtures():
+    """pix2vec_nest of the reference's chealpix.c on every pixel of HEALPIX_FIXTURES (needs
+    oracle/_ref, which main() has checked)."""
+    for nside in HEALPIX_FIXTURES:
+        dirs = O.ref_healpix_dirs(nside)
+        np.save(os.path.join(HERE, "healpix_nside%d_ref.npy" % nside), dirs)
 
 
 def main():
@@ -32,6 +45,7 @@ def main():
     ref = O.ref_healpix()
     if ref is None:
         raise SystemExit("oracle/_ref is not built: /root/reference is required")
+    healpix_fixtures()
     import ctypes as C
     v = (C.c_double * 3)()
     dirs = np.empty((192, 3), np.float64)

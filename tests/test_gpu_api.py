@@ -61,6 +61,8 @@ def test_golden_pipeline_on_gpu(gh, cuda, integral_mode):
     assert np.array_equal(out.cpu().numpy(), g["seg_result"])
 
 
+# (superseded by test_front_end_boundaries.py::test_healpix_rays_at_every_resolution_class[4], which
+# makes the same comparison on a pre-filled buffer; kept as the first use of the fixture)
 def test_healpix_rays_against_reference_run(gh, cuda):
     ref = np.load(os.path.join(GOLD, "healpix_nside4_ref.npy"))     # reference chealpix output
     rays = gh.healpix_rays(4, (0.5, 0.25, 0.125), 3.0, device=cuda).cpu().numpy()
