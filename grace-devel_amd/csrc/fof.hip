@@ -139,16 +139,14 @@ struct LinkVisitor {
 };
 
 template <typename Args>
-__global__ __launch_bounds__(RG_BLOCK) void fof_link_kernel(const Args a)
+__global__ __launch_bounds__(PW_BLOCK) void fof_link_kernel(const Args a)
 {
-    __shared__ float4 s_rec[RG_WAVES][64];
-    __shared__ int s_par[RG_WAVES][64];
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int packet = blockIdx.x * RG_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
-    if (packet < int(*a.n_starts)) {
-        LinkVisitor v(a.parent, s_par[wv]);
-        walk(a, packet, lane, s_rec[wv], v);
+    __shared__ float4 s_rec[PW_WAVES][64];
+    __shared__ int s_par[PW_WAVES][64];
+    const PacketWave w = packet_wave();
+    if (w.packet < int(*a.n_starts)) {
+        LinkVisitor v(a.parent, s_par[w.wv]);
+        walk(a, w.packet, w.lane, s_rec[w.wv], v);
     }
 }
 
@@ -241,8 +239,8 @@ grace_status fof_labels(Args a, const float* d_spheres, size_t n_spheres, const 
     const int n = int(n_spheres);
     fof_init_kernel<<<stream_grid(n_spheres, 256), 256, 0, stream_>>>(d_labels, n);
     GRACE_CHECK_LAUNCH();
-    return walk_run(a, *ts, d_spheres, n_spheres, 4, stream_, [&](const Args& w, size_t waves) -> grace_status {
-        fof_link_kernel<<<ceil_div(waves, RG_WAVES), RG_BLOCK, 0, stream_>>>(w);
+    return packet_run(a, *ts, d_spheres, n_spheres, 4, stream_, [&](const Args& w, size_t waves) -> grace_status {
+        fof_link_kernel<<<ceil_div(waves, PW_WAVES), PW_BLOCK, 0, stream_>>>(w);
         GRACE_CHECK_LAUNCH();
         fof_flatten_kernel<<<stream_grid(n_spheres, 256), 256, 0, stream_>>>(w.parent, n);
         GRACE_CHECK_LAUNCH();

@@ -13,81 +13,56 @@
 // Packets start every 64 sorted points and wherever the cell changes (a scan on the device; the
 // grid is launched for the upper bound n / 64 + cells, surplus waves exit).
 //
-// The packet's box is reduced across the wave, and the wave walks the ALBVH against it: wave-uniform node loads and tests, a 128-entry packet stack held one
-// entry per lane (the trace's convention, overflow reported through the status word), left child
-// first, so leaves come in ascending primitive order.  A leaf's primitives are swept in culling
-// rounds of 64-aligned clusters: each lane loads one candidate and tests its box against the
-// packet's box (conservatively: the boxes are widened by 2^-20 of their bounds, far more than the
-// half ulp by which fl(x - H) can move inward); a ballot compacts the survivors into LDS as
-// {x, y, z, H^2}, {1/H, 1/H^3} and the walk's <= 4 weights, and every lane then runs the survivor
-// list in ascending order against its own point.  A cluster never straddles a granule of 1024
-// primitives, so a round is one summation class: the running sum of the current class stays in
-// VGPRs and is swapped with a per-class LDS slot when the class changes -- each class sum is the
-// fp32 sum in ascending index order -- and the epilogue adds the 8 class sums pairwise.
+// The packet's box is reduced across the wave, and the wave walks the ALBVH against it with
+// packet_walk.hpp's stack and cluster sweep: left child first, so leaves (pushed as node indices)
+// come in ascending primitive order.  The cull tests each candidate's box against the packet's box
+// (conservatively: the boxes are widened by 2^-20 of their bounds, far more than the half ulp by
+// which fl(x - H) can move inward); the survivors go into LDS as {x, y, z, H^2}, {1/H, 1/H^3} and
+// the walk's <= 4 weights, and every lane then runs the survivor list in ascending order against
+// its own point.  A cluster never straddles a granule of 1024 primitives, so a round is one
+// summation class: the running sum of the current class stays in VGPRs and is swapped with a
+// per-class LDS slot when the class changes -- each class sum is the fp32 sum in ascending index
+// order -- and the epilogue adds the 8 class sums pairwise.
 //
 // Containment d2 < fl(H^2) with d2 formed in fp32 is never true for a point outside the exact box
 // [x - H, x + H] of a sphere (|dx| >= H there, and every fp32 step is monotonic), so the widened
 // box tests drop no contained sphere: results are a function of the point and the scene only.
-#include "point_packets.hpp"
+#include "packet_walk.hpp"
 #include "sph_kernel_f.hpp"
 
 using namespace grace_hip;
 
 namespace {
 
-constexpr int IP_BLOCK = 256;
-constexpr int IP_WAVES = IP_BLOCK / 64;
-constexpr int IP_STACK = 128;
 constexpr int IP_CHANNELS = 4;     // channels per walk
-constexpr float IP_SLACK = 9.5367431640625e-07f;   // 2^-20
 
-struct InterpArgs {
-    // points entry point: n_points records of `stride` floats, visited in the order `perm`
-    const float* points;
-    int stride;
-    const uint32_t* perm;
-    int n_points;
-    const uint32_t* starts;      // packet p: sorted points [starts[p], starts[p + 1])
-    const uint32_t* n_starts;    // number of packets (device)
-    // grid entry point (points == nullptr): p(i, j, k) = org + i u + j v + k w
+// points entry point: PacketPoints.  Grid entry point (points == nullptr): p(i, j, k) = org + i u + j v + k w
+struct InterpArgs : PacketPoints, PacketScene {
     float org[3], eu[3], ev[3], ew[3];
     int dims[3];
     int brick[3];          // lattice points per packet along i, j, k
     int nb[2];             // packets along i, j
     int n_packets;
-    const float4* spheres;
-    const float4* nodes;
-    int n_nodes;
-    const int4* leaves;
-    const int* root;
     const float* weights;  // this walk's first channel; sphere i's channel c at weights[i w_stride + c]
     int w_stride;
     float* out;            // point p's channel c at out[p out_stride + c]
     int out_stride;
     int* counts;           // or null
-    int* status;
     unsigned long long* tests;   // measurement hook: survivor tests (lanes x survivors), or null
 };
 
-// [lo, hi] widened by 2^-20 of each bound overlaps the packet box (NaN: no).
-__device__ __forceinline__ bool overlaps(const float lo, const float hi, const float plo, const float phi)
-{
-    return lo - fabsf(lo) * IP_SLACK <= phi && hi + fabsf(hi) * IP_SLACK >= plo;
-}
-
 // NW = channels of this walk (0: counts only).
 template <int KIND, int NW>
-__global__ __launch_bounds__(IP_BLOCK) void interpolate_kernel(const InterpArgs a)
+__global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs a)
 {
     constexpr int NS = NW > 0 ? NW : 1;
-    __shared__ float4 s_rec[IP_WAVES][64];               // survivors: {x, y, z, H^2}
-    __shared__ float2 s_inv[IP_WAVES][NW > 0 ? 64 : 1];  // {1/H, 1/H^3}
-    __shared__ float s_w[IP_WAVES][NW > 0 ? 64 : 1][NS]; // weights
-    __shared__ float s_cls[IP_WAVES][NW > 0 ? 8 : 1][NS][64];   // class sums, per lane
+    __shared__ float4 s_rec[PW_WAVES][64];               // survivors: {x, y, z, H^2}
+    __shared__ float2 s_inv[PW_WAVES][NW > 0 ? 64 : 1];  // {1/H, 1/H^3}
+    __shared__ float s_w[PW_WAVES][NW > 0 ? 64 : 1][NS]; // weights
+    __shared__ float s_cls[PW_WAVES][NW > 0 ? 8 : 1][NS][64];   // class sums, per lane
 
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int packet = blockIdx.x * IP_WAVES + wv;
+    const PacketWave w = packet_wave();
+    const int lane = w.lane, wv = w.wv, packet = w.packet;
     if (packet >= a.n_packets) return;                   // (wave-uniform)
 
     // ---- the packet's points ----
@@ -96,13 +71,10 @@ __global__ __launch_bounds__(IP_BLOCK) void interpolate_kernel(const InterpArgs 
     size_t slot;                                         // output index of this lane's point
     if (a.points) {
         if (packet >= int(*a.n_starts)) return;          // (wave-uniform)
-        const uint32_t first = a.starts[packet], end = a.starts[packet + 1];
-        const uint32_t sp = first + uint32_t(lane);
-        active = sp < end;
-        const uint32_t src = active ? a.perm[sp] : 0u;
-        slot = src;
-        const float* q = a.points + size_t(src) * a.stride;
-        px = q[0]; py = q[1]; pz = q[2];
+        const PacketPoint pt = load_point(a, packet, lane);
+        active = pt.in_range;
+        slot = pt.src;
+        px = pt.px; py = pt.py; pz = pt.pz;
     } else {
         const int bi = packet % a.nb[0], bj = (packet / a.nb[0]) % a.nb[1], bk = packet / (a.nb[0] * a.nb[1]);
         const int li = lane % a.brick[0], lj = (lane / a.brick[0]) % a.brick[1], lk = lane / (a.brick[0] * a.brick[1]);
@@ -134,85 +106,71 @@ __global__ __launch_bounds__(IP_BLOCK) void interpolate_kernel(const InterpArgs 
     int count = 0;
     unsigned long long tests = 0;
 
-    // ---- packet stack: entry e in lane (e & 63) of stk0 (e < 64) or stk1 ----
-    int stk0 = 0, stk1 = 0, sp = -1;
-    bool overflow = false;
-    auto push = [&](const int value) {
-        if (sp >= IP_STACK - 1) { overflow = true; return; }   // bounds check before every push
-        ++sp;
-        if (sp < 64) stk0 = lane == sp ? value : stk0;
-        else stk1 = lane == sp - 64 ? value : stk1;
-    };
+    PacketStack stack;
+    auto push = [&](const int idx) { stack.push(lane, idx); };
     push(*a.root);
 
-    while (sp >= 0) {
-        const int idx = sp < 64 ? __builtin_amdgcn_readlane(stk0, sp) : __builtin_amdgcn_readlane(stk1, sp - 64);
-        --sp;
+    while (!stack.empty()) {
+        const int idx = stack.pop();
         if (idx < a.n_nodes) {
             const float4* np = a.nodes + 4 * size_t(idx);
             const float4 n0 = np[0], L = np[1], R = np[2], Z = np[3];
-            const bool hit_l = overlaps(L.x, L.y, plo_x, phi_x) && overlaps(L.z, L.w, plo_y, phi_y)
-                && overlaps(Z.x, Z.y, plo_z, phi_z);
-            const bool hit_r = overlaps(R.x, R.y, plo_x, phi_x) && overlaps(R.z, R.w, plo_y, phi_y)
-                && overlaps(Z.z, Z.w, plo_z, phi_z);
+            const bool hit_l = overlaps_widened(L.x, L.y, plo_x, phi_x) && overlaps_widened(L.z, L.w, plo_y, phi_y)
+                && overlaps_widened(Z.x, Z.y, plo_z, phi_z);
+            const bool hit_r = overlaps_widened(R.x, R.y, plo_x, phi_x) && overlaps_widened(R.z, R.w, plo_y, phi_y)
+                && overlaps_widened(Z.z, Z.w, plo_z, phi_z);
             if (hit_r) push(__float_as_int(n0.y));
             if (hit_l) push(__float_as_int(n0.x));       // popped first: ascending primitive order
             continue;
         }
         const int4 lf = a.leaves[idx - a.n_nodes];
-        const int r_lo = lf.x, r_hi = lf.x + lf.y;
-        for (int cl = r_lo >> 6; cl <= (r_hi - 1) >> 6; ++cl) {
-            const int pj = (cl << 6) + lane;
-            const bool in = pj >= r_lo && pj < r_hi;
-            const int pc = min(max(pj, r_lo), r_hi - 1);
-            const float4 s = a.spheres[pc];
-            const bool keep = in && overlaps(s.x - s.w, s.x + s.w, plo_x, phi_x)
-                && overlaps(s.y - s.w, s.y + s.w, plo_y, phi_y) && overlaps(s.z - s.w, s.z + s.w, plo_z, phi_z);
-            const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
-            if (mask == 0ull) continue;
-            const int n_surv = __builtin_popcountll(mask);
-            if constexpr (NW > 0) {
-                const int cls = (cl >> (GRANULE_SHIFT - 6)) & (SUM_CLASSES - 1);
-                if (cls != cur) {
-#pragma unroll
-                    for (int c = 0; c < NW; ++c) {
-                        s_cls[wv][cur][c][lane] = acc[c];
-                        acc[c] = s_cls[wv][cls][c][lane];
-                    }
-                    cur = cls;
-                }
-            }
-            if (keep) {
-                const int pos = __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
+        sweep_clusters(a.spheres, lf.x, lf.x + lf.y, lane,
+            [&](const bool in, const float4& s) {
+                return in && overlaps_widened(s.x - s.w, s.x + s.w, plo_x, phi_x)
+                    && overlaps_widened(s.y - s.w, s.y + s.w, plo_y, phi_y)
+                    && overlaps_widened(s.z - s.w, s.z + s.w, plo_z, phi_z);
+            },
+            [&](const int pos, const float4& s, const int j) {
                 s_rec[wv][pos] = make_float4(s.x, s.y, s.z, s.w * s.w);
                 if constexpr (NW > 0) {
                     const float ih = 1.0f / s.w;
                     s_inv[wv][pos] = make_float2(ih, (ih * ih) * ih);
 #pragma unroll
-                    for (int c = 0; c < NW; ++c) s_w[wv][pos][c] = a.weights[size_t(pc) * a.w_stride + c];
+                    for (int c = 0; c < NW; ++c) s_w[wv][pos][c] = a.weights[size_t(j) * a.w_stride + c];
                 }
-            }
-            wave_sync();
-            tests += uint64_t(n_surv);
-            for (int j = 0; j < n_surv; ++j) {
-                const float4 r = s_rec[wv][j];
-                const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                if (d2 < r.w) {
-                    ++count;
-                    if constexpr (NW > 0) {
-                        const float2 inv = s_inv[wv][j];
-                        const float W = kernel_f<KIND>(sqrt_rn(d2) * inv.x) * inv.y;
+            },
+            [&](const int cl, const int n_surv) {
+                if constexpr (NW > 0) {
+                    // the lane's own slots: the swap needs no order against the staging
+                    const int cls = (cl >> (GRANULE_SHIFT - 6)) & (SUM_CLASSES - 1);
+                    if (cls != cur) {
 #pragma unroll
-                        for (int c = 0; c < NW; ++c) acc[c] = acc[c] + s_w[wv][j][c] * W;
+                        for (int c = 0; c < NW; ++c) {
+                            s_cls[wv][cur][c][lane] = acc[c];
+                            acc[c] = s_cls[wv][cls][c][lane];
+                        }
+                        cur = cls;
                     }
                 }
-            }
-            wave_sync();
-        }
+                tests += uint64_t(n_surv);
+                for (int j = 0; j < n_surv; ++j) {
+                    const float4 r = s_rec[wv][j];
+                    const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 < r.w) {
+                        ++count;
+                        if constexpr (NW > 0) {
+                            const float2 inv = s_inv[wv][j];
+                            const float W = kernel_f<KIND>(sqrt_rn(d2) * inv.x) * inv.y;
+#pragma unroll
+                            for (int c = 0; c < NW; ++c) acc[c] = acc[c] + s_w[wv][j][c] * W;
+                        }
+                    }
+                }
+            });
     }
 
-    if (overflow && lane == 0) *a.status = GRACE_STACK_OVERFLOW;
+    stack.report(lane, a.status);
     const unsigned long long n_active = __builtin_popcountll(__builtin_amdgcn_ballot_w64(active));
     if (a.tests && lane == 0) atomicAdd(a.tests, tests * n_active);
     if (!active) return;
@@ -235,35 +193,18 @@ __global__ __launch_bounds__(IP_BLOCK) void interpolate_kernel(const InterpArgs 
 unsigned long long* g_tests = nullptr;
 bool g_stats = false;
 
-template <int KIND>
-grace_status launch_kind(const InterpArgs& a, int nw, hipStream_t stream)
+grace_status launch_walk(const InterpArgs& a, int kind, int nw, hipStream_t stream)
 {
-    const int blocks = ceil_div(size_t(a.n_packets), IP_WAVES);
-    switch (nw) {
-    case 1: interpolate_kernel<KIND, 1><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
-    case 2: interpolate_kernel<KIND, 2><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
-    case 3: interpolate_kernel<KIND, 3><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
-    default: interpolate_kernel<KIND, 4><<<blocks, IP_BLOCK, 0, stream>>>(a); break;
+    const int blocks = ceil_div(size_t(a.n_packets), PW_WAVES);
+    if (nw == 0) {
+        interpolate_kernel<GRACE_SPH_KERNEL_CUBIC, 0><<<blocks, PW_BLOCK, 0, stream>>>(a);
+    } else {
+        with_kernel(kind, nw, [&](auto k, auto n) {
+            interpolate_kernel<decltype(k)::value, decltype(n)::value><<<blocks, PW_BLOCK, 0, stream>>>(a);
+        });
     }
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
-}
-
-grace_status launch_walk(const InterpArgs& a, int kind, int nw, hipStream_t stream)
-{
-    if (nw == 0) {
-        interpolate_kernel<GRACE_SPH_KERNEL_CUBIC, 0><<<ceil_div(size_t(a.n_packets), IP_WAVES), IP_BLOCK, 0, stream>>>(a);
-        GRACE_CHECK_LAUNCH();
-        return GRACE_OK;
-    }
-    switch (kind) {
-    case GRACE_SPH_KERNEL_CUBIC: return launch_kind<GRACE_SPH_KERNEL_CUBIC>(a, nw, stream);
-    case GRACE_SPH_KERNEL_QUARTIC: return launch_kind<GRACE_SPH_KERNEL_QUARTIC>(a, nw, stream);
-    case GRACE_SPH_KERNEL_QUINTIC: return launch_kind<GRACE_SPH_KERNEL_QUINTIC>(a, nw, stream);
-    case GRACE_SPH_KERNEL_WENDLAND_C2: return launch_kind<GRACE_SPH_KERNEL_WENDLAND_C2>(a, nw, stream);
-    case GRACE_SPH_KERNEL_WENDLAND_C4: return launch_kind<GRACE_SPH_KERNEL_WENDLAND_C4>(a, nw, stream);
-    default: return launch_kind<GRACE_SPH_KERNEL_WENDLAND_C6>(a, nw, stream);
-    }
 }
 
 // Checks shared by both entry points, and the scene / output fields of the arguments.
@@ -271,9 +212,7 @@ grace_status interp_common(InterpArgs& a, const float* d_spheres, size_t n_spher
                            size_t n_nodes, const int* d_leaves, const int* d_root, const float* d_weights,
                            int n_channels, float* d_out, int* d_counts, TraceState** ts_out)
 {
-    GRACE_REQUIRE(d_spheres && d_nodes && d_leaves && d_root, "interpolate: null scene pointer");
-    GRACE_REQUIRE(n_nodes >= 1 && n_nodes < (size_t(1) << 30), "interpolate: bad node count");
-    GRACE_REQUIRE(n_spheres > 0 && n_spheres < (size_t(1) << 31), "interpolate: bad sphere count");
+    PACKET_SCENE(a, "interpolate", false, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
     GRACE_REQUIRE(d_out || d_counts, "interpolate: no output");
     if (d_out) {
         GRACE_REQUIRE(n_channels >= 1 && n_channels <= 64, "interpolate: channels must be 1..64");
@@ -283,45 +222,35 @@ grace_status interp_common(InterpArgs& a, const float* d_spheres, size_t n_spher
     GRACE_TRY(trace_state(&ts));
     GRACE_REQUIRE(ts->sph_kernel >= GRACE_SPH_KERNEL_CUBIC && ts->sph_kernel <= GRACE_SPH_KERNEL_WENDLAND_C6,
                   "interpolate: a custom SPH kernel table has no kernel function f(q)");
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.n_nodes = int(n_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
     a.w_stride = n_channels;
     a.out_stride = n_channels;
     *ts_out = ts;
     return GRACE_OK;
 }
 
-// The walks of one call: channels four at a time, counts with the first walk.
-grace_status interp_walks(InterpArgs a, TraceState& ts, const float* d_weights, int n_channels, float* d_out,
-                          int* d_counts, hipStream_t stream)
+// The measurement hook's counter, zeroed for this call.
+grace_status interp_hook(InterpArgs& a, hipStream_t stream)
 {
-    GRACE_TRY(ensure_status(ts, stream));
-    a.status = ts.status;
-    a.tests = nullptr;
     if (g_stats && g_tests) {
         GRACE_TRY_HIP(hipMemsetAsync(g_tests, 0, sizeof(unsigned long long), stream));
         a.tests = g_tests;
     }
-    if (ts.timing) {
-        if (!ts.ev0) { GRACE_TRY_HIP(hipEventCreate(&ts.ev0)); GRACE_TRY_HIP(hipEventCreate(&ts.ev1)); }
-        GRACE_TRY_HIP(hipEventRecord(ts.ev0, stream));
-    }
+    return GRACE_OK;
+}
+
+// The walks of one call: channels four at a time, counts with the first walk.
+grace_status interp_walks(InterpArgs a, int kind, const float* d_weights, int n_channels, float* d_out,
+                          int* d_counts, hipStream_t stream)
+{
     if (!d_out) {
         a.counts = d_counts;
-        GRACE_TRY(launch_walk(a, ts.sph_kernel, 0, stream));
+        return launch_walk(a, kind, 0, stream);
     }
-    for (int g = 0; d_out && g < n_channels; g += IP_CHANNELS) {
+    for (int g = 0; g < n_channels; g += IP_CHANNELS) {
         a.weights = d_weights + g;
         a.out = d_out + g;
         a.counts = g == 0 ? d_counts : nullptr;
-        GRACE_TRY(launch_walk(a, ts.sph_kernel, min(IP_CHANNELS, n_channels - g), stream));
-    }
-    if (ts.timing) {
-        GRACE_TRY_HIP(hipEventRecord(ts.ev1, stream));
-        ts.ev_valid = true;
+        GRACE_TRY(launch_walk(a, kind, min(IP_CHANNELS, n_channels - g), stream));
     }
     return GRACE_OK;
 }
@@ -345,17 +274,12 @@ grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points,
     GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
                             d_out, d_counts, &ts));
     const hipStream_t stream_ = as_stream(stream);
-    FrameGuard frame;
-    PointPackets pk;
-    GRACE_TRY(point_packets(frame, d_points, n_points, elems_per_point, a.nodes, a.n_nodes, d_root, stream_, pk));
-    a.points = d_points;
-    a.stride = elems_per_point;
-    a.perm = pk.perm;
-    a.n_points = int(n_points);
-    a.starts = pk.starts;
-    a.n_starts = pk.n_starts;
-    a.n_packets = int(pk.max_packets);
-    return interp_walks(a, *ts, d_weights, n_channels, d_out, d_counts, stream_);
+    GRACE_TRY(interp_hook(a, stream_));
+    return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
+                      [&](InterpArgs w, size_t max_packets) -> grace_status {
+        w.n_packets = int(max_packets);
+        return interp_walks(w, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_);
+    });
 }
 
 grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
@@ -384,7 +308,11 @@ grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uv
     const size_t packets = size_t(a.nb[0]) * a.nb[1] * size_t(ceil_div(size_t(h_dims3[2]), a.brick[2]));
     GRACE_REQUIRE(packets < (size_t(1) << 31) / 64, "interpolate_grid: too many lattice points");
     a.n_packets = int(packets);
-    return interp_walks(a, *ts, d_weights, n_channels, d_out, d_counts, as_stream(stream));
+    const hipStream_t stream_ = as_stream(stream);
+    GRACE_TRY(interp_hook(a, stream_));
+    return timed_walks(a, *ts, stream_, [&] {  // (a lattice has no packets to make)
+        return interp_walks(a, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_);
+    });
 }
 
 grace_status grace_interpolate_enable_stats(int enabled)

@@ -2,11 +2,10 @@
 // smoothing lengths from the k-th neighbour of every particle (grace_smoothing_lengths_f4).  An
 // extension the reference lacks; the ranking is stated exactly in include/grace_hip.h.
 //
-// Packets are the interpolation's (point_packets.hpp): one wave owns up to 64 points of one Morton
-// cell, keys against the tree's root box, sorted.  The smoothing-length entry sorts the sphere
-// centres too: tree order is a Morton order of the build's bounds, whose grid is not the root box's
-// (the root box includes H), so cutting tree order at root-box cell changes left packets of ~4
-// points (lane fill 0.061 measured on bench.py's scene).
+// The walk is packet_walk.hpp's (packets, stack, cluster sweep, box helpers).  The smoothing-length
+// entry sorts the sphere centres too: tree order is a Morton order of the build's bounds, whose grid
+// is not the root box's (the root box includes H), so cutting tree order at root-box cell changes
+// left packets of ~4 points (lane fill 0.061 measured on bench.py's scene).
 //
 // Every lane keeps its k best candidates as 64-bit keys (bits(d2) << 32) | j, ascending in K
 // registers (K in {8, 16, 32, 64}, k <= K): for d2 >= 0 the float bits order as the floats, so one
@@ -16,20 +15,15 @@
 // slots hold (+inf, 0xffffffff), above every real candidate, also one at d2 = +inf.
 //
 // The wave walks the ALBVH against the union of its lanes' query boxes [p - r, p + r], r the
-// lane's current k-th distance widened (below), recomputed whenever a lane's list changes.  Nearer
-// child first (box distance to the packet centre), so lists fill early and the boxes shrink.  A
-// leaf's primitives are swept in 64-aligned clusters: each lane tests one centre against the union
-// box, a ballot compacts the survivors {x, y, z, j} into LDS, and every lane ranks them all.
+// lane's current k-th distance widened, recomputed whenever a lane's list changes.  Nearer child
+// first (box distance to the packet centre), so lists fill early and the boxes shrink.  Leaves are
+// pushed as node indices; a leaf's primitives go through the cluster sweep, the survivors
+// {x, y, z, j}, and every lane ranks them all.
 //
-// Widening.  A candidate with d2 <= D (the lane's k-th d2, fp32) has fl(dx*dx) <= D, since the
-// rounded sums of non-negative terms never fall below a term, so the exact |p - x| per component
-// is below sqrt(D) (1 + 2^-22).  r = fl(v_sqrt(D) (1 + 2^-20)) + 2^-60 exceeds that (v_sqrt is
-// within 1 ulp; the 2^-60 covers d2 that underflowed to 0 or a flushed denormal), and the rounded
-// bounds p - r, p + r are then moved out by 2^-20 of themselves, far more than their rounding.
-// Node boxes built with any H >= 0 contain their centres exactly.  So pruning only drops
-// candidates whose d2 is strictly above the lane's k-th d2: equal d2 with a lower index still
-// gets in, and the result does not depend on the visiting order.
-#include "point_packets.hpp"
+// Widening.  packet_walk.hpp's argument with D := the lane's k-th d2: pruning only drops
+// candidates whose d2 is strictly above it, so equal d2 with a lower index still gets in, and the
+// result does not depend on the visiting order.
+#include "packet_walk.hpp"
 
 #include <cmath>
 
@@ -37,45 +31,16 @@ using namespace grace_hip;
 
 namespace {
 
-constexpr int NB_BLOCK = 256;
-constexpr int NB_WAVES = NB_BLOCK / 64;
-constexpr int NB_STACK = 128;
-constexpr float NB_SLACK = 9.5367431640625e-07f;     // 2^-20
-constexpr float NB_FLOOR = 8.673617379884035e-19f;   // 2^-60
 constexpr uint64_t NB_EMPTY = (uint64_t(0x7f800000u) << 32) | 0xffffffffu;
 
-struct NbrArgs {
-    const float* points;         // n records of `stride` floats, visited in the order `perm`
-    int stride;
-    const uint32_t* perm;        // sorted position -> point index
-    const uint32_t* starts;      // packet p: sorted points [starts[p], starts[p + 1])
-    const uint32_t* n_starts;    // number of packets (device)
-    const float4* spheres;
-    const float4* nodes;
-    int n_nodes;
-    const int4* leaves;
-    const int* root;
+struct NbrArgs : PacketPoints, PacketScene {
     int k;
     int* indices;                // point p's slot s at [p k + s], or null
     float* d2;                   // or null
     float* h;                    // smoothing lengths: h[p] = fl(eta sqrt_rn(d2 of slot k - 1)), or null
     float eta;
-    int* status;
     unsigned long long* stats;   // measurement hook (grace_neighbours_last_stats), or null
 };
-
-// The lane's query box on one axis, widened as stated above (inactive lanes: empty, +inf / -inf).
-__device__ __forceinline__ void query_bounds(const float p, const float r, const bool active, float& lo, float& hi)
-{
-    const float l = p - r, u = p + r;
-    lo = active ? l - fabsf(l) * NB_SLACK : __int_as_float(0x7f800000);
-    hi = active ? u + fabsf(u) * NB_SLACK : __int_as_float(0xff800000);
-}
-
-__device__ __forceinline__ bool overlaps(const float lo, const float hi, const float ulo, const float uhi)
-{
-    return lo <= uhi && hi >= ulo;
-}
 
 // Squared distance from c to the box (gap per axis; for ordering only).
 __device__ __forceinline__ float box_dist2(const float xlo, const float xhi, const float ylo, const float yhi,
@@ -93,12 +58,10 @@ template <int K>
 __device__ __forceinline__ void walk_packet(const NbrArgs& a, const int packet, const int lane, float4* s_rec)
 {
     // ---- the packet's points ----
-    const uint32_t first = a.starts[packet], end = a.starts[packet + 1];
-    const uint32_t spos = first + uint32_t(lane);
-    const bool in_range = spos < end;
-    const uint32_t src = in_range ? (a.perm[spos]) : 0u;
-    const float* q = a.points + size_t(src) * a.stride;
-    float px = q[0], py = q[1], pz = q[2];
+    const PacketPoint pt = load_point(a, packet, lane);
+    const bool in_range = pt.in_range;
+    const uint32_t src = pt.src;
+    float px = pt.px, py = pt.py, pz = pt.pz;
     const bool active = in_range && isfinite(px) && isfinite(py) && isfinite(pz);
     if (!active) px = py = pz = __int_as_float(0x7fc00000);   // NaN: d2 is NaN, ranked after every slot
     const float cx = 0.5f * (wave_min(px) + wave_max(px));    // packet centre (NaN points skipped)
@@ -113,7 +76,7 @@ __device__ __forceinline__ void walk_packet(const NbrArgs& a, const int packet, 
     float ulo_x, uhi_x, ulo_y, uhi_y, ulo_z, uhi_z;      // union of the lanes' query boxes
     auto union_box = [&]() {
         const float D = __uint_as_float(uint32_t(key[K - 1] >> 32));
-        const float r = __builtin_amdgcn_sqrtf(D) * (1.0f + NB_SLACK) + NB_FLOOR;   // D = +inf: +inf
+        const float r = widened_radius(D);
         float lo, hi;
         query_bounds(px, r, active, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
         query_bounds(py, r, active, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
@@ -122,20 +85,12 @@ __device__ __forceinline__ void walk_packet(const NbrArgs& a, const int packet, 
     union_box();
     unsigned long long tests = 0, steps = 0;               // survivors; survivors some lane inserted
 
-    // ---- packet stack: entry e in lane (e & 63) of stk0 (e < 64) or stk1 ----
-    int stk0 = 0, stk1 = 0, sp = -1;
-    bool overflow = false;
-    auto push = [&](const int value) {
-        if (sp >= NB_STACK - 1) { overflow = true; return; }   // bounds check before every push
-        ++sp;
-        if (sp < 64) stk0 = lane == sp ? value : stk0;
-        else stk1 = lane == sp - 64 ? value : stk1;
-    };
+    PacketStack stack;
+    auto push = [&](const int idx) { stack.push(lane, idx); };
     push(*a.root);
 
-    while (sp >= 0) {
-        const int idx = sp < 64 ? __builtin_amdgcn_readlane(stk0, sp) : __builtin_amdgcn_readlane(stk1, sp - 64);
-        --sp;
+    while (!stack.empty()) {
+        const int idx = stack.pop();
         if (idx < a.n_nodes) {
             const float4* np = a.nodes + 4 * size_t(idx);
             const float4 n0 = np[0], L = np[1], R = np[2], Z = np[3];
@@ -160,50 +115,42 @@ __device__ __forceinline__ void walk_packet(const NbrArgs& a, const int packet, 
             continue;
         }
         const int4 lf = a.leaves[idx - a.n_nodes];
-        const int r_lo = lf.x, r_hi = lf.x + lf.y;
-        for (int cl = r_lo >> 6; cl <= (r_hi - 1) >> 6; ++cl) {
-            const int pj = (cl << 6) + lane;
-            const bool in = pj >= r_lo && pj < r_hi;
-            const int pc = min(max(pj, r_lo), r_hi - 1);
-            const float4 s = a.spheres[pc];
-            const bool keep = in && s.x >= ulo_x && s.x <= uhi_x && s.y >= ulo_y && s.y <= uhi_y
-                && s.z >= ulo_z && s.z <= uhi_z;
-            const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
-            if (mask == 0ull) continue;
-            const int n_surv = __builtin_popcountll(mask);
-            if (keep) {
-                const int pos = __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
-                s_rec[pos] = make_float4(s.x, s.y, s.z, __int_as_float(pj));
-            }
-            wave_sync();
-            tests += uint64_t(n_surv);
-            bool changed = false;
-            for (int j = 0; j < n_surv; ++j) {
-                const float4 r = s_rec[j];
-                const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                const uint64_t c = (uint64_t(__float_as_uint(d2)) << 32) | uint32_t(__float_as_int(r.w));
-                const bool ins = c < key[K - 1];
-                steps += __builtin_amdgcn_ballot_w64(ins) != 0ull;
-                if (ins) {
-                    // compare-and-shift: slot s takes slot s - 1 if c ranks below it, else c if c ranks below slot s
-                    bool lt_hi = true;                         // c < key[s2]
+        sweep_clusters(a.spheres, lf.x, lf.x + lf.y, lane,
+            [&](const bool in, const float4& c) {
+                return in && c.x >= ulo_x && c.x <= uhi_x && c.y >= ulo_y && c.y <= uhi_y
+                    && c.z >= ulo_z && c.z <= uhi_z;
+            },
+            [&](const int pos, const float4& c, const int j) {
+                s_rec[pos] = make_float4(c.x, c.y, c.z, __int_as_float(j));
+            },
+            [&](int, const int n_surv) {
+                tests += uint64_t(n_surv);
+                bool changed = false;
+                for (int j = 0; j < n_surv; ++j) {
+                    const float4 r = s_rec[j];
+                    const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    const uint64_t c = (uint64_t(__float_as_uint(d2)) << 32) | uint32_t(__float_as_int(r.w));
+                    const bool ins = c < key[K - 1];
+                    steps += __builtin_amdgcn_ballot_w64(ins) != 0ull;
+                    if (ins) {
+                        // compare-and-shift: slot s takes slot s - 1 if c ranks below it, else c if c ranks below slot s
+                        bool lt_hi = true;                         // c < key[s2]
 #pragma unroll
-                    for (int s2 = K - 1; s2 > 0; --s2) {
-                        const bool lt_lo = c < key[s2 - 1];
-                        key[s2] = lt_lo ? key[s2 - 1] : (lt_hi ? c : key[s2]);
-                        lt_hi = lt_lo;
+                        for (int s2 = K - 1; s2 > 0; --s2) {
+                            const bool lt_lo = c < key[s2 - 1];
+                            key[s2] = lt_lo ? key[s2 - 1] : (lt_hi ? c : key[s2]);
+                            lt_hi = lt_lo;
+                        }
+                        key[0] = lt_hi ? c : key[0];
+                        changed = true;
                     }
-                    key[0] = lt_hi ? c : key[0];
-                    changed = true;
                 }
-            }
-            wave_sync();
-            if (__builtin_amdgcn_ballot_w64(changed)) union_box();
-        }
+                if (__builtin_amdgcn_ballot_w64(changed)) union_box();
+            });
     }
 
-    if (overflow && lane == 0) *a.status = GRACE_STACK_OVERFLOW;
+    stack.report(lane, a.status);
     const unsigned long long n_active = __builtin_popcountll(__builtin_amdgcn_ballot_w64(active));   // (all lanes)
     if (a.stats && lane == 0) {
         atomicAdd(a.stats, tests * n_active);
@@ -227,13 +174,11 @@ __device__ __forceinline__ void walk_packet(const NbrArgs& a, const int packet, 
 }
 
 template <int K>
-__global__ __launch_bounds__(NB_BLOCK) void neighbours_kernel(const NbrArgs a)
+__global__ __launch_bounds__(PW_BLOCK) void neighbours_kernel(const NbrArgs a)
 {
-    __shared__ float4 s_rec[NB_WAVES][64];
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int packet = blockIdx.x * NB_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
-    if (packet < int(*a.n_starts)) walk_packet<K>(a, packet, lane, s_rec[wv]);
+    __shared__ float4 s_rec[PW_WAVES][64];
+    const PacketWave w = packet_wave();
+    if (w.packet < int(*a.n_starts)) walk_packet<K>(a, w.packet, w.lane, s_rec[w.wv]);
 }
 
 // Process-wide measurement hook (grace_neighbours_enable_stats): {candidate tests, packets,
@@ -244,22 +189,7 @@ bool g_stats = false;
 template <int K>
 void launch_k(const NbrArgs& a, size_t waves, hipStream_t stream)
 {
-    neighbours_kernel<K><<<ceil_div(waves, NB_WAVES), NB_BLOCK, 0, stream>>>(a);
-}
-
-grace_status nbr_scene(NbrArgs& a, const float* d_spheres, size_t n_spheres, const int* d_nodes, size_t n_nodes,
-                       const int* d_leaves, const int* d_root, int k)
-{
-    GRACE_REQUIRE(d_spheres && d_leaves && d_root && (d_nodes || n_nodes == 0), "neighbours: null scene pointer");
-    GRACE_REQUIRE(n_nodes < (size_t(1) << 30), "neighbours: bad node count");
-    GRACE_REQUIRE(n_spheres > 0 && n_spheres < (size_t(1) << 31), "neighbours: bad sphere count");
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.n_nodes = int(n_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
-    a.k = k;
-    return GRACE_OK;
+    neighbours_kernel<K><<<ceil_div(waves, PW_WAVES), PW_BLOCK, 0, stream>>>(a);
 }
 
 // Keys against the root box, sort, packet starts, then the walk.
@@ -267,36 +197,18 @@ grace_status nbr_run(NbrArgs a, const float* d_points, size_t n_points, int stri
 {
     TraceState* ts = nullptr;
     GRACE_TRY(trace_state(&ts));
-    FrameGuard frame;
-    PointPackets pk;
-    GRACE_TRY(point_packets(frame, d_points, n_points, stride, a.nodes, a.n_nodes, a.root, stream, pk));
-    a.points = d_points;
-    a.stride = stride;
-    a.perm = pk.perm;
-    a.starts = pk.starts;
-    a.n_starts = pk.n_starts;
-
-    GRACE_TRY(ensure_status(*ts, stream));
-    a.status = ts->status;
-    a.stats = nullptr;
     if (g_stats && g_stats_dev) {
         GRACE_TRY_HIP(hipMemsetAsync(g_stats_dev, 0, 3 * sizeof(unsigned long long), stream));
         a.stats = g_stats_dev;
     }
-    if (ts->timing) {
-        if (!ts->ev0) { GRACE_TRY_HIP(hipEventCreate(&ts->ev0)); GRACE_TRY_HIP(hipEventCreate(&ts->ev1)); }
-        GRACE_TRY_HIP(hipEventRecord(ts->ev0, stream));
-    }
-    if (a.k <= 8) launch_k<8>(a, pk.max_packets, stream);
-    else if (a.k <= 16) launch_k<16>(a, pk.max_packets, stream);
-    else if (a.k <= 32) launch_k<32>(a, pk.max_packets, stream);
-    else launch_k<64>(a, pk.max_packets, stream);
-    GRACE_CHECK_LAUNCH();
-    if (ts->timing) {
-        GRACE_TRY_HIP(hipEventRecord(ts->ev1, stream));
-        ts->ev_valid = true;
-    }
-    return GRACE_OK;
+    return packet_run(a, *ts, d_points, n_points, stride, stream, [&](const NbrArgs& w, size_t waves) -> grace_status {
+        if (w.k <= 8) launch_k<8>(w, waves, stream);
+        else if (w.k <= 16) launch_k<16>(w, waves, stream);
+        else if (w.k <= 32) launch_k<32>(w, waves, stream);
+        else launch_k<64>(w, waves, stream);
+        GRACE_CHECK_LAUNCH();
+        return GRACE_OK;
+    });
 }
 
 } // namespace
@@ -315,7 +227,8 @@ grace_status grace_nearest_neighbours_f4(const float* d_points, size_t n_points,
     GRACE_REQUIRE(d_points, "nearest_neighbours: null points");
     GRACE_REQUIRE(d_indices || d_d2, "nearest_neighbours: no output");
     NbrArgs a = {};
-    GRACE_TRY(nbr_scene(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, k));
+    PACKET_SCENE(a, "neighbours", true, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
+    a.k = k;
     a.indices = d_indices;
     a.d2 = d_d2;
     return nbr_run(a, d_points, n_points, elems_per_point, as_stream(stream));
@@ -330,7 +243,8 @@ grace_status grace_smoothing_lengths_f4(const float* d_spheres, size_t n_spheres
     GRACE_REQUIRE(d_h, "smoothing_lengths: null output");
     GRACE_REQUIRE(size_t(k) <= n_spheres, "smoothing_lengths: k exceeds the number of spheres");
     NbrArgs a = {};
-    GRACE_TRY(nbr_scene(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, k));
+    PACKET_SCENE(a, "neighbours", true, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
+    a.k = k;
     a.h = d_h;
     a.eta = eta;
     return nbr_run(a, d_spheres, n_spheres, 4, as_stream(stream));

@@ -124,22 +124,21 @@ struct PairVisitor {
 };
 
 template <int BT, int NW, typename Args>
-__global__ __launch_bounds__(RG_BLOCK) void pair_kernel(const Args a)
+__global__ __launch_bounds__(PW_BLOCK) void pair_kernel(const Args a)
 {
     constexpr int NS = NW > 0 ? NW : 1;
     constexpr int SR = sums_rows(BT, NW);
-    __shared__ float4 s_rec[RG_WAVES][64];
-    __shared__ float s_w[RG_WAVES][NW > 0 ? 64 : 1][NS];
-    __shared__ uint32_t s_cnt[RG_WAVES][BT][64];
-    __shared__ float s_sum[RG_WAVES][SR > 0 ? SR : 1][SR > 0 ? 64 : 1];
+    __shared__ float4 s_rec[PW_WAVES][64];
+    __shared__ float s_w[PW_WAVES][NW > 0 ? 64 : 1][NS];
+    __shared__ uint32_t s_cnt[PW_WAVES][BT][64];
+    __shared__ float s_sum[PW_WAVES][SR > 0 ? SR : 1][SR > 0 ? 64 : 1];
     __shared__ float s_e2[BT > PC_LINEAR_MAX ? BT : 1];
     if constexpr (BT > PC_LINEAR_MAX) {
         if (threadIdx.x < BT) s_e2[threadIdx.x] = a.e2[threadIdx.x];
         __syncthreads();
     }
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int packet = blockIdx.x * RG_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
+    const PacketWave w = packet_wave();
+    const int lane = w.lane, wv = w.wv, packet = w.packet;
     if (packet >= int(*a.n_starts)) return;
     PairVisitor<BT, NW> v(a, &s_cnt[wv][0][lane], &s_sum[wv][0][SR > 0 ? lane : 0], s_w[wv], s_e2);
     walk(a, packet, lane, s_rec[wv], v);
@@ -159,18 +158,18 @@ template <int BT, typename Args>
 void launch_tier(const Args& a, int nw, int blocks, hipStream_t stream)
 {
     switch (nw) {
-    case 0: pair_kernel<BT, 0><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    case 1: pair_kernel<BT, 1><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    case 2: pair_kernel<BT, 2><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    case 3: pair_kernel<BT, 3><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    default: pair_kernel<BT, 4><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
+    case 0: pair_kernel<BT, 0><<<blocks, PW_BLOCK, 0, stream>>>(a); break;
+    case 1: pair_kernel<BT, 1><<<blocks, PW_BLOCK, 0, stream>>>(a); break;
+    case 2: pair_kernel<BT, 2><<<blocks, PW_BLOCK, 0, stream>>>(a); break;
+    case 3: pair_kernel<BT, 3><<<blocks, PW_BLOCK, 0, stream>>>(a); break;
+    default: pair_kernel<BT, 4><<<blocks, PW_BLOCK, 0, stream>>>(a); break;
     }
 }
 
 template <typename Args>
 grace_status launch_pairs(const Args& a, int nw, size_t waves, hipStream_t stream)
 {
-    const int blocks = ceil_div(waves, RG_WAVES);
+    const int blocks = ceil_div(waves, PW_WAVES);
     if (a.n_edges <= 8) launch_tier<8>(a, nw, blocks, stream);
     else if (a.n_edges <= 16) launch_tier<16>(a, nw, blocks, stream);
     else launch_tier<64>(a, nw, blocks, stream);
@@ -219,8 +218,8 @@ grace_status pair_counts(Args a, const float* d_points, size_t n_points, int ele
     a.counts = d_counts;
     a.sums = d_sums;
     if (d_totals) GRACE_TRY_HIP(hipMemsetAsync(d_totals, 0, size_t(n_edges) * sizeof(unsigned long long), stream_));
-    return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                    [&](const Args& w, size_t waves) -> grace_status {
+    return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
+                      [&](const Args& w, size_t waves) -> grace_status {
         return launch_pairs(w, d_sums ? n_channels : 0, waves, stream_);
     });
 }

@@ -110,27 +110,14 @@ struct RangeVisitor {
 };
 
 template <int MODE, int KIND, int NW, typename Args>
-__global__ __launch_bounds__(RG_BLOCK) void range_kernel(const Args a)
+__global__ __launch_bounds__(PW_BLOCK) void range_kernel(const Args a)
 {
-    __shared__ float4 s_rec[RG_WAVES][64];
-    __shared__ float s_w[RG_WAVES][NW > 0 ? 64 : 1][NW > 0 ? NW : 1];
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int packet = blockIdx.x * RG_WAVES + wv;      // (surplus waves of the n / 64 + cells bound exit)
-    if (packet < int(*a.n_starts)) {
-        RangeVisitor<MODE, KIND, NW> v(a, s_w[wv]);
-        walk(a, packet, lane, s_rec[wv], v);
-    }
-}
-
-template <int KIND, typename Args>
-void launch_sums(const Args& a, int nw, int blocks, hipStream_t stream)
-{
-    switch (nw) {
-    case 1: range_kernel<RG_SUMS, KIND, 1><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    case 2: range_kernel<RG_SUMS, KIND, 2><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    case 3: range_kernel<RG_SUMS, KIND, 3><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
-    default: range_kernel<RG_SUMS, KIND, 4><<<blocks, RG_BLOCK, 0, stream>>>(a); break;
+    __shared__ float4 s_rec[PW_WAVES][64];
+    __shared__ float s_w[PW_WAVES][NW > 0 ? 64 : 1][NW > 0 ? NW : 1];
+    const PacketWave w = packet_wave();
+    if (w.packet < int(*a.n_starts)) {
+        RangeVisitor<MODE, KIND, NW> v(a, s_w[w.wv]);
+        walk(a, w.packet, w.lane, s_rec[w.wv], v);
     }
 }
 
@@ -138,20 +125,15 @@ void launch_sums(const Args& a, int nw, int blocks, hipStream_t stream)
 template <typename Args>
 grace_status launch_walk(const Args& a, int mode, int kind, int nw, size_t waves, hipStream_t stream)
 {
-    const int blocks = ceil_div(waves, RG_WAVES);
+    const int blocks = ceil_div(waves, PW_WAVES);
     if (mode == RG_COUNT) {
-        range_kernel<RG_COUNT, GRACE_SPH_KERNEL_CUBIC, 0><<<blocks, RG_BLOCK, 0, stream>>>(a);
+        range_kernel<RG_COUNT, GRACE_SPH_KERNEL_CUBIC, 0><<<blocks, PW_BLOCK, 0, stream>>>(a);
     } else if (mode == RG_FILL) {
-        range_kernel<RG_FILL, GRACE_SPH_KERNEL_CUBIC, 0><<<blocks, RG_BLOCK, 0, stream>>>(a);
+        range_kernel<RG_FILL, GRACE_SPH_KERNEL_CUBIC, 0><<<blocks, PW_BLOCK, 0, stream>>>(a);
     } else {
-        switch (kind) {
-        case GRACE_SPH_KERNEL_CUBIC: launch_sums<GRACE_SPH_KERNEL_CUBIC>(a, nw, blocks, stream); break;
-        case GRACE_SPH_KERNEL_QUARTIC: launch_sums<GRACE_SPH_KERNEL_QUARTIC>(a, nw, blocks, stream); break;
-        case GRACE_SPH_KERNEL_QUINTIC: launch_sums<GRACE_SPH_KERNEL_QUINTIC>(a, nw, blocks, stream); break;
-        case GRACE_SPH_KERNEL_WENDLAND_C2: launch_sums<GRACE_SPH_KERNEL_WENDLAND_C2>(a, nw, blocks, stream); break;
-        case GRACE_SPH_KERNEL_WENDLAND_C4: launch_sums<GRACE_SPH_KERNEL_WENDLAND_C4>(a, nw, blocks, stream); break;
-        default: launch_sums<GRACE_SPH_KERNEL_WENDLAND_C6>(a, nw, blocks, stream); break;
-        }
+        with_kernel(kind, nw, [&](auto k, auto n) {
+            range_kernel<RG_SUMS, decltype(k)::value, decltype(n)::value><<<blocks, PW_BLOCK, 0, stream>>>(a);
+        });
     }
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
@@ -193,8 +175,8 @@ grace_status range_counts(Args a, const float* d_points, size_t n_points, int el
                       "range_counts: a custom SPH kernel table has no kernel function f(q)");
     a.w_stride = n_channels;
     const hipStream_t stream_ = as_stream(stream);
-    return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                     [&](Args w, size_t waves) -> grace_status {
+    return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
+                      [&](Args w, size_t waves) -> grace_status {
         if (!d_sums) {
             w.counts = d_counts;
             return launch_walk(w, RG_COUNT, kind, 0, waves, stream_);
@@ -230,8 +212,8 @@ grace_status range_neighbours(Args a, const float* d_points, size_t n_points, in
     a.indices = d_indices;
     a.d2 = d_d2;
     const hipStream_t stream_ = as_stream(stream);
-    return walk_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                     [&](const Args& w, size_t waves) -> grace_status {
+    return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
+                      [&](const Args& w, size_t waves) -> grace_status {
         return launch_walk(w, RG_FILL, GRACE_SPH_KERNEL_CUBIC, 0, waves, stream_);
     });
 }

@@ -1,35 +1,30 @@
-// The fixed-radius packet walk shared by the range queries (range.hip) and the friends-of-friends
-// link kernel (fof.hip): one wave owns up to 64 query points of one Morton cell
-// (point_packets.hpp) and walks the ALBVH against the union of its lanes' query boxes; what a lane
-// does with a centre in range is the including file's Visitor.  Each including translation unit
-// gets its own copies (internal linkage).
+// The fixed-radius packet walk shared by the range queries (range.hip), the friends-of-friends link
+// kernel (fof.hip) and the pair counts (pairs.hip): packet_walk.hpp's walk against the union of its
+// lanes' query boxes, the radii known up front; what a lane does with a centre in range is the
+// including file's Visitor.  Each including translation unit gets its own copies (internal linkage).
 //
 // Order.  A node's left child covers the lower index range (albvh.hip: the left child spans leaves
 // first .. j, the right one j + 1 .. last), so left child first visits the leaves, and with them
 // the primitives, in ascending tree index: lists and running sums fall out of the walk in order.
 //
-// Stack.  128 entries, one per lane of two registers (the trace's convention), and a second word
-// per entry: an entry is an inner node, or a RANGE of primitives [lo, lo + n) -- a leaf whose box
-// met the union box.  A range pushed directly under a range that starts where it ends is merged
-// into it.  The ALBVH of coincident points is a spine of leaves deeper than the stack; whichever
-// side its leaves hang on, they are popped at once (left) or merged into the waiting range
-// (right), so the spine never grows the stack.  Overflow is reported through the status word.
+// Stack.  packet_walk.hpp's convention (128 entries, one per lane of two registers), kept here as
+// local words with a second word per entry: an entry is an inner node, or a RANGE of primitives
+// [lo, lo + n) -- a leaf whose box met the union box.  A range pushed directly under a range that
+// starts where it ends is merged into it.  The ALBVH of coincident points is a spine of leaves
+// deeper than the stack; whichever side its leaves hang on, they are popped at once (left) or
+// merged into the waiting range (right), so the spine never grows the stack.  (Two-word entries
+// as members of packet_walk.hpp's PacketStack cost this walk 3 to 8 % on the MI355X with the
+// same survivor loop, so the words and the sweep below stay local to it.)
 //
-// A range is swept in 64-aligned clusters: each lane tests one centre against the union box, a
-// ballot compacts the survivors {x, y, z, j} (and whatever the visitor stages beside them) into LDS
-// in ascending j, and every lane tests them all against its own point: one compare, then the
-// visitor's hit().
+// A range is swept as packet_walk.hpp's sweep_clusters does, the survivors {x, y, z, j} (and
+// whatever the visitor stages beside them) in ascending j, and every lane tests them all against
+// its own point: one compare, then the visitor's hit().
 //
-// Widening.  A centre in range has d2 <= D := R2 = fl(r * r), so fl(dx*dx) <= D, since the rounded
-// sums of non-negative terms never fall below a term, so the exact |p - x| per component is below
-// sqrt(D) (1 + 2^-22).  r' = fl(v_sqrt(D) (1 + 2^-20)) + 2^-60 exceeds that (v_sqrt is within 1 ulp;
-// the 2^-60 covers D that underflowed to 0 or a flushed denormal), and the rounded bounds p - r',
-// p + r' are then moved out by 2^-20 of themselves, far more than their rounding.  Node boxes built
-// with any H >= 0 contain their centres exactly.  So pruning only drops centres whose d2 is
-// strictly above the lane's R2: d2 == R2 still gets in, and the result does not depend on the tree's
-// H, max_per_leaf or the packets.  Off points (a non-finite coordinate; r negative, NaN or +inf)
-// have an empty box and NaN in place of their coordinates and R2: no lane widens for them, and
-// no compare is ever true.
+// Widening.  packet_walk.hpp's argument with D := R2 = fl(r * r): pruning only drops centres whose
+// d2 is strictly above the lane's R2, so d2 == R2 still gets in, and the result does not depend on
+// the tree's H, max_per_leaf or the packets.  Off points (a non-finite coordinate; r negative, NaN
+// or +inf) have an empty box and NaN in place of their coordinates and R2: no lane widens for
+// them, and no compare is ever true.
 //
 // Periodic boxes (walk_packet<Visitor, true>, a WalkPeriod: per axis the period L and h = fl(0.5 L),
 // exact; an open axis has L = 0 and h = +inf, which no |d| exceeds and no radius, so it needs no
@@ -38,7 +33,7 @@
 // still tested once per lane: the union box stays one box, and per axis a node or a centre passes
 // if it meets the box, the box shifted by -L or the box shifted by +L (both rounded outward, once
 // per packet, in SGPRs like the box itself).
-//   Widening, wrapped.  Let rho = sqrt(D) (1 + 2^-22) < r' as above; a centre in range has a
+//   Widening, wrapped.  Let rho = sqrt(D) (1 + 2^-22) < r' = widened_radius(D); a centre in range has a
 // wrapped component |dw| <= rho.  No wrap: dw = fl(p - x) and x is in [p - r', p + r'] as before.
 // d0 = fl(p - x) > h: if d0 > 2 L then fl(d0 - L) >= L >= 2 r and the square is above D (an on lane
 // has r <= h); else d0 is in [L / 2, 2 L] and d0 - L is exact (Sterbenz), so |d0 - L| <= rho and
@@ -71,7 +66,7 @@
 //   void finish(uint32_t src)        after the walk, lanes of the packet only
 #pragma once
 
-#include "point_packets.hpp"
+#include "packet_walk.hpp"
 
 #include <cmath>
 #include <limits>
@@ -79,27 +74,10 @@
 
 namespace {
 
-constexpr int RG_BLOCK = 256;
-constexpr int RG_WAVES = RG_BLOCK / 64;
-constexpr int RG_STACK = 128;
-constexpr float RG_SLACK = 9.5367431640625e-07f;     // 2^-20
-constexpr float RG_FLOOR = 8.673617379884035e-19f;   // 2^-60
-
 // What the walk itself reads: the packets, the query points with their radii, and the scene.
-struct WalkArgs {
-    const float* points;         // n records of `stride` floats, visited in the order `perm`
-    int stride;
-    const uint32_t* perm;        // sorted position -> point index
-    const uint32_t* starts;      // packet p: sorted points [starts[p], starts[p + 1])
-    const uint32_t* n_starts;    // number of packets (device)
+struct WalkArgs : PacketPoints, PacketScene {
     const float* radii;          // per point, caller's order, or null: `radius` for all
     float radius;
-    const float4* spheres;
-    const float4* nodes;
-    int n_nodes;
-    const int4* leaves;
-    const int* root;
-    int* status;
 };
 
 // A periodic box: per axis the period L (0: open) and h = fl(0.5 L) (open: +inf).
@@ -115,19 +93,6 @@ struct Periodic : Base {
 };
 template <typename T> struct is_periodic : std::false_type {};
 template <typename Base> struct is_periodic<Periodic<Base>> : std::true_type {};
-
-// The lane's query box on one axis, widened as stated above (off lanes: empty, +inf / -inf).
-__device__ __forceinline__ void query_bounds(const float p, const float r, const bool on, float& lo, float& hi)
-{
-    const float l = p - r, u = p + r;
-    lo = on ? l - fabsf(l) * RG_SLACK : __int_as_float(0x7f800000);
-    hi = on ? u + fabsf(u) * RG_SLACK : __int_as_float(0xff800000);
-}
-
-__device__ __forceinline__ bool overlaps(const float lo, const float hi, const float ulo, const float uhi)
-{
-    return lo <= uhi && hi >= ulo;
-}
 
 // The union box on one axis and its images shifted by -L and +L, rounded outward (wave-uniform).
 struct AxisImages {
@@ -151,8 +116,8 @@ __device__ __forceinline__ float uniform(const float v)
 __device__ __forceinline__ AxisImages axis_images(const float ulo, const float uhi, const float L)
 {
     const float ml = ulo - L, mh = uhi - L, pl = ulo + L, ph = uhi + L;
-    return { ulo, uhi, uniform(ml - fabsf(ml) * RG_SLACK), uniform(mh + fabsf(mh) * RG_SLACK),
-             uniform(pl - fabsf(pl) * RG_SLACK), uniform(ph + fabsf(ph) * RG_SLACK) };
+    return { ulo, uhi, uniform(ml - fabsf(ml) * PW_SLACK), uniform(mh + fabsf(mh) * PW_SLACK),
+             uniform(pl - fabsf(pl) * PW_SLACK), uniform(ph + fabsf(ph) * PW_SLACK) };
 }
 
 // One component of the periodic separation: at most one wrap (open axis: h = +inf, none).
@@ -167,12 +132,10 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
                                             Visitor& v, const WalkPeriod& per = WalkPeriod())
 {
     // ---- the packet's points ----
-    const uint32_t first = a.starts[packet], end = a.starts[packet + 1];
-    const uint32_t spos = first + uint32_t(lane);
-    const bool in_range = spos < end;
-    const uint32_t src = in_range ? a.perm[spos] : 0u;
-    const float* q = a.points + size_t(src) * a.stride;
-    float px = q[0], py = q[1], pz = q[2];
+    const PacketPoint pt = load_point(a, packet, lane);
+    const bool in_range = pt.in_range;
+    const uint32_t src = pt.src;
+    float px = pt.px, py = pt.py, pz = pt.pz;
     const float r = a.radii ? a.radii[src] : a.radius;
     bool on = in_range && isfinite(px) && isfinite(py) && isfinite(pz) && r >= 0.0f
         && r < __int_as_float(0x7f800000);
@@ -183,12 +146,12 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
     // ---- the union of the lanes' query boxes, once ----
     float ulo_x, uhi_x, ulo_y, uhi_y, ulo_z, uhi_z;
     {
-        const float rw = __builtin_amdgcn_sqrtf(R2) * (1.0f + RG_SLACK) + RG_FLOOR;   // R2 = +inf: +inf
+        const float rw = widened_radius(R2);
         float lo, hi;
         if constexpr (PERIODIC) {
-            query_bounds(px, rw + per.L[0] * 0.25f * RG_SLACK, on, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
-            query_bounds(py, rw + per.L[1] * 0.25f * RG_SLACK, on, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
-            query_bounds(pz, rw + per.L[2] * 0.25f * RG_SLACK, on, lo, hi); ulo_z = wave_min(lo); uhi_z = wave_max(hi);
+            query_bounds(px, rw + per.L[0] * 0.25f * PW_SLACK, on, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
+            query_bounds(py, rw + per.L[1] * 0.25f * PW_SLACK, on, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
+            query_bounds(pz, rw + per.L[2] * 0.25f * PW_SLACK, on, lo, hi); ulo_z = wave_min(lo); uhi_z = wave_max(hi);
         } else {
             query_bounds(px, rw, on, lo, hi); ulo_x = wave_min(lo); uhi_x = wave_max(hi);
             query_bounds(py, rw, on, lo, hi); ulo_y = wave_min(lo); uhi_y = wave_max(hi);
@@ -202,8 +165,8 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
         bx = axis_images(ulo_x, uhi_x, per.L[0]);
         by = axis_images(ulo_y, uhi_y, per.L[1]);
         bz = axis_images(ulo_z, uhi_z, per.L[2]);
-        narrow = (uhi_x - ulo_x) * (1.0f + RG_SLACK) <= per.h[0] && (uhi_y - ulo_y) * (1.0f + RG_SLACK) <= per.h[1]
-            && (uhi_z - ulo_z) * (1.0f + RG_SLACK) <= per.h[2];
+        narrow = (uhi_x - ulo_x) * (1.0f + PW_SLACK) <= per.h[0] && (uhi_y - ulo_y) * (1.0f + PW_SLACK) <= per.h[1]
+            && (uhi_z - ulo_z) * (1.0f + PW_SLACK) <= per.h[2];
         // the root's box (the union of its children's) holds every node box and centre: a packet none
         // of whose images meets it needs the box itself only (a root that is a leaf has no box: images)
         const int rt = *a.root;
@@ -245,7 +208,7 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
                 if (tc > 0 && tv == value + count) { set_top(value, count + tc); return; }   // merge
             }
         }
-        if (sp >= RG_STACK - 1) { overflow = true; return; }   // bounds check before every push
+        if (sp >= PW_STACK - 1) { overflow = true; return; }   // bounds check before every push
         ++sp;
         set_top(value, count);
     };
@@ -319,7 +282,7 @@ __device__ __forceinline__ void walk_packet(const WalkArgs& a, const int packet,
         }
     }
 
-    if (overflow && lane == 0) atomicMax(a.status, int(GRACE_STACK_OVERFLOW));
+    report_overflow(overflow, lane, a.status);
     if (!in_range) return;
     v.finish(src);
 }
@@ -348,49 +311,14 @@ grace_status walk_period(WalkPeriod& per, const float* h_period3, const float* r
     return GRACE_OK;
 }
 
-// The checks every entry point over this walk shares (before anything is enqueued), and the
-// scene's fields.
+// The checks every entry point over this walk shares (before anything is enqueued), the radii and
+// the scene's fields.
 grace_status walk_scene(WalkArgs& a, const float* d_radii, float radius, const float* d_spheres, size_t n_spheres,
                         const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root)
 {
-    GRACE_REQUIRE(d_spheres && d_leaves && d_root && (d_nodes || n_nodes == 0), "range query: null scene pointer");
-    GRACE_REQUIRE(n_nodes < (size_t(1) << 30), "range query: bad node count");
-    GRACE_REQUIRE(n_spheres > 0 && n_spheres < (size_t(1) << 31), "range query: bad sphere count");
+    PACKET_SCENE(a, "range query", true, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
     a.radii = d_radii;
     a.radius = radius;
-    a.spheres = reinterpret_cast<const float4*>(d_spheres);
-    a.nodes = reinterpret_cast<const float4*>(d_nodes);
-    a.n_nodes = int(n_nodes);
-    a.leaves = reinterpret_cast<const int4*>(d_leaves);
-    a.root = d_root;
-    return GRACE_OK;
-}
-
-// Keys against the root box, sort, packet starts, then the walks of one call (timed together).
-// Args: WalkArgs or a struct derived from it; walks(args, max_packets) launches.
-template <typename Args, typename Walks>
-grace_status walk_run(Args a, grace_hip::TraceState& ts, const float* d_points, size_t n_points, int stride,
-                      hipStream_t stream, Walks walks)
-{
-    grace_hip::FrameGuard frame;
-    PointPackets pk;
-    GRACE_TRY(point_packets(frame, d_points, n_points, stride, a.nodes, a.n_nodes, a.root, stream, pk));
-    a.points = d_points;
-    a.stride = stride;
-    a.perm = pk.perm;
-    a.starts = pk.starts;
-    a.n_starts = pk.n_starts;
-    GRACE_TRY(ensure_status(ts, stream));
-    a.status = ts.status;
-    if (ts.timing) {
-        if (!ts.ev0) { GRACE_TRY_HIP(hipEventCreate(&ts.ev0)); GRACE_TRY_HIP(hipEventCreate(&ts.ev1)); }
-        GRACE_TRY_HIP(hipEventRecord(ts.ev0, stream));
-    }
-    GRACE_TRY(walks(a, pk.max_packets));
-    if (ts.timing) {
-        GRACE_TRY_HIP(hipEventRecord(ts.ev1, stream));
-        ts.ev_valid = true;
-    }
     return GRACE_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "common.hpp"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -42,6 +43,23 @@ __device__ __forceinline__ float kernel_f(const float q)
         const float u4 = pow4(u);
         return ((u4 * u4) * (q * (q * (32.0f * q + 25.0f) + 8.0f) + 1.0f)) * float(1365.0 / (64.0 * M_PI));
     }
+}
+
+// The run-time choice of a built-in kernel and 1..4 channels as compile-time constants:
+// f(kind, nw) gets two std::integral_constant<int, ...> (a generic lambda reads their ::value).
+// Steps through the kinds CUBIC .. WENDLAND_C6 (consecutive values), then through the channel
+// counts, to the first that matches; a value that matches none gets the last, as a switch's default.
+template <int KIND = GRACE_SPH_KERNEL_CUBIC, int NW = 1, typename F>
+void with_kernel(const int kind, const int nw, F f)
+{
+    static_assert(GRACE_SPH_KERNEL_CUBIC == 0 && GRACE_SPH_KERNEL_WENDLAND_C6 == 5, "six consecutive kinds");
+    if constexpr (KIND < GRACE_SPH_KERNEL_WENDLAND_C6) {
+        if (kind != KIND) return with_kernel<KIND + 1, NW>(kind, nw, f);
+    }
+    if constexpr (NW < 4) {
+        if (nw != NW) return with_kernel<KIND, NW + 1>(kind, nw, f);
+    }
+    f(std::integral_constant<int, KIND>(), std::integral_constant<int, NW>());
 }
 
 } // namespace

@@ -136,15 +136,6 @@ grace_status trace_state(TraceState** out)
 
 namespace {
 
-grace_status ensure_status(TraceState& ts, hipStream_t stream)
-{
-    if (!ts.status) {
-        GRACE_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&ts.status), sizeof(int)));
-        GRACE_TRY_HIP(hipMemsetAsync(ts.status, 0, sizeof(int), stream));
-    }
-    return GRACE_OK;
-}
-
 struct LaunchPlan {   // how a call is launched: everything that follows from the sizes and the knobs alone
     int width = 64, n_packets = 0;   // rays per packet, packets
     int split = 1;                   // waves launched per packet ...
@@ -550,17 +541,10 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         ts.hits.valid = true; ts.hits.rays = a.rays; ts.hits.n_rays = n_rays;
         ts.hits.prims = a.spheres; ts.hits.n_prims = n_spheres; ts.hits.n_chunks = p.hit_chunks;
     }
-    if (ts.timing) {
-        if (!ts.ev0) { GRACE_TRY_HIP(hipEventCreate(&ts.ev0)); GRACE_TRY_HIP(hipEventCreate(&ts.ev1)); }
-        GRACE_TRY_HIP(hipEventRecord(ts.ev0, stream));
-    }
     ts.last_lat_dev = a.lat_dev; ts.last_lat_stream = stream;
-    GRACE_TRY(dispatch<MODE>(ts, a, b, p, reuse_chunks ? ts.hits.chunk_counts : nullptr, n_rays, stream));
-    if (ts.timing) {
-        GRACE_TRY_HIP(hipEventRecord(ts.ev1, stream));
-        ts.ev_valid = true;
-    }
-    return GRACE_OK;
+    return timed(ts, stream, [&] {
+        return dispatch<MODE>(ts, a, b, p, reuse_chunks ? ts.hits.chunk_counts : nullptr, n_rays, stream);
+    });
 }
 
 // What every trace entry point passes the same way (a double4 trace also sets spheres_d; its

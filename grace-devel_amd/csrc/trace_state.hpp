@@ -306,6 +306,33 @@ struct TraceState {
 // The TraceState of the calling thread's context (created on first use).
 grace_status trace_state(TraceState** out);
 
+// The context's status word, allocated and zeroed on first use.
+inline grace_status ensure_status(TraceState& ts, hipStream_t stream)
+{
+    if (!ts.status) {
+        GRACE_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&ts.status), sizeof(int)));
+        GRACE_TRY_HIP(hipMemsetAsync(ts.status, 0, sizeof(int), stream));
+    }
+    return GRACE_OK;
+}
+
+// The ts.timing bracket around the launches of one call (what grace_trace_last_kernel_ms reports):
+// the events are created on first use.
+template <typename Launches>
+grace_status timed(TraceState& ts, hipStream_t stream, Launches launches)
+{
+    if (ts.timing) {
+        if (!ts.ev0) { GRACE_TRY_HIP(hipEventCreate(&ts.ev0)); GRACE_TRY_HIP(hipEventCreate(&ts.ev1)); }
+        GRACE_TRY_HIP(hipEventRecord(ts.ev0, stream));
+    }
+    GRACE_TRY(launches());
+    if (ts.timing) {
+        GRACE_TRY_HIP(hipEventRecord(ts.ev1, stream));
+        ts.ev_valid = true;
+    }
+    return GRACE_OK;
+}
+
 // trace_cache.hip: signatures of the inputs behind cached records.
 // One launch reads up to four arrays -- the scene's primitives, nodes and leaves (group 0) and the
 // rays (group 1); a null array is skipped -- and leaves per-workgroup partial sums in `partial`

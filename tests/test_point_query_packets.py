@@ -1,4 +1,4 @@
-"""The point-query front end (csrc/point_packets.hpp: Morton keys of the caller's points, the nested sort,
+"""The point-query front end (csrc/point_packets.hip: Morton keys of the caller's points, the nested sort,
 packets cut at every 64th sorted point and at every change of Morton cell) across the point counts at
 which it changes behaviour, and on streams and contexts of its own.
 
@@ -71,7 +71,7 @@ def root_box(s):
     return lo, hi
 
 
-# ---- interp_keys_kernel, restated --------------------------------------------------------------------
+# ---- packet_keys_kernel, restated --------------------------------------------------------------------
 def cell_level(m):
     level = 0
     while level < 10 and (1 << (3 * (level + 1))) * 256 <= m:
@@ -550,7 +550,7 @@ def total_of(ps, sh):
 
 @pytest.mark.gpu
 def test_the_restated_root_box_is_the_trees(gh, scenes, cuda):
-    """The CPU test's cells are the kernel's: the box interp_keys_kernel reads from the root node is the
+    """The CPU test's cells are the kernel's: the box packet_keys_kernel reads from the root node is the
     restated one to within a few ulp -- far inside the margins of the point sets."""
     built, sh = scenes
     s, lo, hi = scene_and_box()
