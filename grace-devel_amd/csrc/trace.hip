@@ -74,6 +74,11 @@
 //     (choose_split).  A wave keeps its class accumulators in LDS (2 KiB) and switches at
 //     granule boundaries, once per culling round at most.  Hit counts split the same way
 //     (integers);
+//   * packet plan: once the scene records and the ray order both come out of their validated
+//     caches, the cull of every axis-aligned packet -- per class the list of its non-empty rounds,
+//     {cluster, survivor mask, lean / fat bits} -- is recorded beside them (trace_planned.hip) and
+//     the column-density calls that follow run the PLANNED instantiation: survivor loops only,
+//     entries by scalar loads; re-recorded on the device when a signature has moved;
 //   * per-hit outputs (ordered per ray): large batches stage hits per lane in LDS and drain
 //     them eight entries per ray; small batches split a packet over K waves by contiguous
 //     chunk ranges with per-(ray, chunk) output offsets from a counting walk (hits_plan_kernel);
@@ -104,6 +109,7 @@ static grace_status trace_state_destroy(Context& c)
 {
     if (!c.trace) return GRACE_OK;
     TraceState& ts = *c.trace;
+    GRACE_TRY(plan_release(ts));
     GRACE_TRY(scene_release(ts));
     GRACE_TRY(rays_release(ts));
     if (ts.hits.chunk_counts) GRACE_TRY_HIP(hipFree(ts.hits.chunk_counts));
@@ -252,6 +258,9 @@ struct TraceBuffers {   // a call's buffers in its workspace frame (null: not ne
     uint32_t *pk_prefix = nullptr, *pk_total = nullptr;
     // ray order; ext: 12 extents + [12] the device-side split + [13] the lattice flag (per call)
     uint32_t* ext = nullptr; uint32_t* keys = nullptr; uint32_t* perm = nullptr;
+    // Packet plan (set by use_records): this call may use one -- both caches serve it --, under this key
+    bool plan_eligible = false;
+    PlanKey plan_key;
 };
 
 // Opens the call's frame and points `a` at its scene records and ray order, cached or derived here.
@@ -293,6 +302,19 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
         if (rays_use == USE_FILL && rays_cache_alloc(ts, rkey) != GRACE_OK) rays_use = USE_NONE;
     }
     const bool scene_cached = scene_use != USE_NONE, rays_cached = rays_use != USE_NONE;
+    // A packet plan is recorded from, and used with, records and an order that both come out of
+    // their caches (each seen repeated, or prepared).  Batches that run the lattice kernel split
+    // (lat_split) keep it: their heaviest packets need its four waves.
+    auto held = [](const CacheUse u) { return u == USE_CHECK || u == USE_TRUST; };
+    b.plan_eligible = ts.plan_on && f4_sums(MODE) && held(scene_use) && held(rays_use) && p.lat_split == 0;
+    if (b.plan_eligible)
+        b.plan_key = PlanKey{ p.fast_b, group_shift(n_prims), p.width, p.reorder, n_rays, n_prims, ts.scene.gen, ts.rays.gen };
+    // (a recorded plan of this key: the device-side gate decides whether this call re-records it)
+    PlanGate gate;
+    const bool plan_steady = b.plan_eligible && ts.plan.valid && ts.plan.key == b.plan_key;
+    if (plan_steady) {
+        gate.ctl = ts.plan.ctl; gate.scene = ts.scene.ctl; gate.rays = ts.rays.ctl;
+    }
     const bool scene_sig = scene_use == USE_FILL || scene_use == USE_CHECK;
     const bool rays_sig = rays_use == USE_FILL || rays_use == USE_CHECK, sig = scene_sig || rays_sig;
     // The frame's layout: carve(base) takes the buffers from `base` and returns the bytes taken; over
@@ -376,9 +398,9 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
                 ro.valid = true;
             }
             // cached order: only this call's device-side choices remain
-            if (lat_flag || split_dev)
+            if (lat_flag || split_dev || plan_steady)
                 GRACE_TRY(launch_choose_variants(ro.ext, int(n_rays), scene_min, lat_flag, p.n_packets,
-                                                 p.split | split_flags, split_dev, stream));
+                                                 p.split | split_flags, split_dev, stream, plan_steady ? &gate : nullptr));
             a.perm = ro.perm;
         } else {
             GRACE_TRY(ray_order(a.rays, n_rays, b.ext, b.keys, b.perm, scene_min, lat_flag, p.n_packets,
@@ -435,6 +457,14 @@ grace_status dispatch(const TraceState& ts, const TraceArgs& a, const TraceBuffe
                                                       TRACE_BLOCK, 0, stream>>>(a_lat);
                 GRACE_CHECK_LAUNCH();
                 return combine(p.lat_split, nullptr, a.lat_dev);
+            }
+            if constexpr (f4_sums(MODE)) if (a.plan_usable) {
+                // A call with a packet plan: the gated re-record, the planned kernel (always the
+                // class-split one: with one wave per packet it leaves one partial sum per ray), then
+                // the ordinary kernels; the plan's device flag lets one side run.
+                GRACE_TRY(plan_record(ts, a, stream));
+                GRACE_TRY(launch_planned(MODE, ALT, grid, a, stream));
+                if (p.split == 1) GRACE_TRY(combine(1, nullptr, reinterpret_cast<const int*>(a.plan_usable)));
             }
             if (p.split > 1) launch_walk<MODE, true, ALT>(grid, a, stream);
             else launch_walk<MODE, false, ALT>(grid, a, stream);
@@ -542,6 +572,19 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         ts.hits.prims = a.spheres; ts.hits.n_prims = n_spheres; ts.hits.n_chunks = p.hit_chunks;
     }
     ts.last_lat_dev = a.lat_dev; ts.last_lat_stream = stream;
+    if constexpr (f4_sums(MODE)) {
+        // The packet plan: sized and recorded by the first call that both caches serve (one stream
+        // synchronisation, where the caches' own fills have theirs), used from then on.
+        PacketPlan& pp = ts.plan;
+        if (b.plan_eligible && !(pp.key == b.plan_key && (pp.valid || pp.dead)))
+            GRACE_TRY(plan_fill(ts, b.plan_key, a, stream));
+        ts.last_plan_ctl = nullptr;
+        if (b.plan_eligible && pp.valid && pp.key == b.plan_key) {
+            a.plan_entries = pp.entries; a.plan_spans = pp.spans; a.plan_counts = pp.counts;
+            a.plan_usable = &pp.ctl->usable;
+            ts.last_plan_ctl = pp.ctl; ts.last_plan_stream = stream;
+        }
+    }
     return timed(ts, stream, [&] {
         return dispatch<MODE>(ts, a, b, p, reuse_chunks ? ts.hits.chunk_counts : nullptr, n_rays, stream);
     });
@@ -877,6 +920,7 @@ grace_status grace_trace_prepare_rays(const void* d_rays, size_t n_rays, grace_s
 grace_status grace_trace_release_rays(void)
 {
     GRACE_TRACE_STATE();
+    GRACE_TRY(plan_release(ts));
     return rays_release(ts);
 }
 
@@ -888,6 +932,7 @@ grace_status grace_trace_release(void)
         GRACE_TRY_HIP(hipFree(ts.hits.chunk_counts));
     }
     ts.hits = HitsCache();
+    GRACE_TRY(plan_release(ts));
     return scene_release(ts);
 }
 
@@ -918,6 +963,45 @@ grace_status grace_trace_last_lattice(int* h_lattice)
         GRACE_TRY_HIP(hipStreamSynchronize(ts.last_lat_stream));
         GRACE_TRY_HIP(hipMemcpy(h_lattice, ts.last_lat_dev, sizeof(int), hipMemcpyDeviceToHost));
     }
+    return GRACE_OK;
+}
+
+grace_status grace_trace_last_plan_used(int* h_used)
+{
+    GRACE_REQUIRE(h_used, "null output");
+    *h_used = 0;
+    GRACE_TRACE_STATE();
+    if (ts.last_plan_ctl) {
+        PlanCtl h = {};
+        GRACE_TRY_HIP(hipStreamSynchronize(ts.last_plan_stream));
+        GRACE_TRY_HIP(hipMemcpy(&h, ts.last_plan_ctl, sizeof(h), hipMemcpyDeviceToHost));
+        *h_used = h.usable != 0u ? 1 : 0;
+    }
+    return GRACE_OK;
+}
+
+grace_status grace_trace_set_plan(int on)
+{
+    GRACE_TRACE_STATE();
+    ts.plan_on = on != 0;
+    if (!ts.plan_on) GRACE_TRY(plan_release(ts));
+    return GRACE_OK;
+}
+
+grace_status grace_trace_set_plan_budget(size_t bytes)
+{
+    GRACE_TRACE_STATE();
+    ts.plan_budget = bytes;
+    GRACE_TRY(plan_release(ts));    // (sized again, under the new budget, by the next call it can serve)
+    return GRACE_OK;
+}
+
+grace_status grace_trace_plan_bytes(size_t* h_bytes)
+{
+    GRACE_REQUIRE(h_bytes, "null output");
+    GRACE_TRACE_STATE();
+    const PacketPlan& pp = ts.plan;
+    *h_bytes = pp.valid ? (pp.n_entries + 4) * sizeof(uint4) + pp.n_lists * (sizeof(int) + sizeof(int2)) + sizeof(PlanCtl) : 0;
     return GRACE_OK;
 }
 
@@ -1017,6 +1101,7 @@ grace_status grace_trace_set_cache_auto(int enabled)
     GRACE_TRACE_STATE();
     ts.cache_auto = enabled != 0;
     if (!ts.cache_auto) {     // what was cached automatically goes; pinned (prepared) records stay
+        if ((ts.scene.valid && !ts.scene.pinned) || (ts.rays.valid && !ts.rays.pinned)) GRACE_TRY(plan_release(ts));
         if (ts.scene.valid && !ts.scene.pinned) GRACE_TRY(scene_release(ts));
         if (ts.rays.valid && !ts.rays.pinned) GRACE_TRY(rays_release(ts));
         ts.scene.seen = SceneKey();

@@ -223,9 +223,24 @@ __device__ void choose_variants(const uint32_t* __restrict__ ext12, int n, const
 // The same choices for a call whose ray order is cached (grace_trace_prepare_rays).
 __global__ void choose_variants_kernel(const uint32_t* __restrict__ ext12, int n, const float4* __restrict__ scene_min,
                                        uint32_t* __restrict__ lat_flag, int split_packets, int split_launched,
-                                       int* __restrict__ split_dev)
+                                       int* __restrict__ split_dev, const PlanGate gate)
 {
-    choose_variants(ext12, n, scene_min, lat_flag, split_packets, split_launched, split_dev);
+    if (lat_flag || split_dev)
+        choose_variants(ext12, n, scene_min, lat_flag, split_packets, split_launched, split_dev);
+    // The packet plan of this call: recorded from the scene records and the ray order, so it is
+    // re-recorded when either cache's signature is no longer the one it was recorded under (the
+    // gated pre-pass / ray order have re-derived them, in this call or an earlier one).
+    if (gate.ctl) {
+        PlanCtl& pc = *gate.ctl;
+        const bool stale = pc.sig[0] != gate.scene->sig[0] || pc.sig[1] != gate.scene->sig[1]
+            || pc.sig[2] != gate.rays->sig[0] || pc.sig[3] != gate.rays->sig[1];
+        pc.record = stale ? 1u : 0u;
+        if (stale) {
+            pc.unusable = 0u; pc.usable = 1u;
+            pc.sig[0] = gate.scene->sig[0]; pc.sig[1] = gate.scene->sig[1];
+            pc.sig[2] = gate.rays->sig[0]; pc.sig[3] = gate.rays->sig[1];
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void ray_keys_kernel(const float* __restrict__ rays, int n,
@@ -326,10 +341,11 @@ __global__ __launch_bounds__(256) void ray_keys_kernel(const float* __restrict__
 namespace grace_hip {
 
 grace_status launch_choose_variants(const uint32_t* ext12, int n, const float4* scene_min, uint32_t* lat_flag,
-                                    int split_packets, int split_launched, int* split_dev, hipStream_t stream)
+                                    int split_packets, int split_launched, int* split_dev, hipStream_t stream,
+                                    const PlanGate* gate)
 {
     choose_variants_kernel<<<1, 1, 0, stream>>>(ext12, n, scene_min, lat_flag, split_packets, split_launched,
-                                                split_dev);
+                                                split_dev, gate ? *gate : PlanGate());
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
 }
@@ -365,6 +381,7 @@ grace_status rays_cache_alloc(TraceState& ts, const RayKey& key)
         return set_error(GRACE_OUT_OF_MEMORY, __FILE__, __LINE__, "ray order cache: out of device memory");
     }
     ro.key = key;
+    ro.gen = ++ts.cache_gen;
     return GRACE_OK;
 }
 

@@ -1,5 +1,6 @@
 // The traversal kernel of libgrace_hip.so (see trace.hip for the design notes): device helpers,
-// beam / pencil / cluster culls, and trace_kernel<MODE, SPLIT, ALT, LAT>.  Included by trace.hip only.
+// beam / pencil / cluster culls, and trace_kernel<MODE, SPLIT, ALT, LAT, PLANNED>.  Included by trace.hip
+// and, for the PLANNED instantiations and the plan's record kernel, by trace_planned.hip.
 #pragma once
 
 #include "trace_diag.hpp"
@@ -322,6 +323,17 @@ __device__ __forceinline__ bool cluster_may_hit(const float4 blo, const float4 b
     }
 }
 
+// The packet plan is read through the constant address space: written by an earlier launch, never
+// during this one, and every address is wave-uniform -- so the entries arrive by scalar loads into
+// SGPRs (a global pointer gave vector loads of one address, twelve VGPRs and a readfirstlane each).
+typedef uint32_t plan_u32x4 __attribute__((ext_vector_type(4)));
+typedef int plan_i32x2 __attribute__((ext_vector_type(2)));
+template <typename T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* plan_const(const void* p)
+{
+    return (const __attribute__((address_space(4))) T*)(uintptr_t)p;
+}
+
 // A survivor's 1/h terms {x, y} with its staged weights (weighted sums; padded to even channels).
 template <int N>
 struct WeightedB {
@@ -340,7 +352,13 @@ struct WeightedB {
 // sphere (choose_lattice, in ray_keys_kernel) lets exactly one of them run -- the test costs the
 // class-split kernels registers they do not have, and the frame kernel 2 %, so scenes without
 // sub-spacing spheres must not carry it.
-template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false>
+// PLANNED: the packet-plan consumer (PacketPlan, trace_state.hpp) of the class-split column-density
+// kernels: each wave walks the recorded lists of its classes -- entry by entry the cluster to
+// fetch, the round's survivor mask and its lean / fat bits, read through scalar loads three
+// entries ahead -- and runs the survivor loops of the axis path as they are.  It makes no group
+// pass, no cluster test, no cull, keeps no stack and has no LAT variant (the recorded masks hold
+// the lattice cull's result).
+template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false, bool PLANNED = false>
 // The one-wave-per-packet hit-count / column-density kernels are held to 6 waves per SIMD (<= 80
 // VGPRs): left to itself the register allocator drifts between 77 and 102 VGPRs from one edit of
 // this file to the next, and at 5 waves per SIMD the frame kernel loses 20 % (2.9 -> 3.55 ms,
@@ -355,8 +373,12 @@ void trace_kernel(const TraceArgs a)
 {
     static_assert(!ALT || f4_integrals(MODE), "no alternative path for this mode");
     static_assert(!LAT || has_lattice(MODE), "no lattice cull for this mode");
-    if (has_lattice(MODE)) {
-        if (a.lat_dev ? (*a.lat_dev != 0) != LAT : LAT) return;   // (workgroup-uniform)
+    static_assert(!PLANNED || (SPLIT && !LAT && f4_sums(MODE)), "planned: class-split column densities only");
+    if constexpr (PLANNED) {
+        if (*plan_const<uint32_t>(a.plan_usable) == 0u) return;    // (workgroup-uniform)
+    } else if (has_lattice(MODE)) {
+        if (a.plan_usable && *a.plan_usable != 0u) return;         // the planned kernel runs
+        if (a.lat_dev ? (*a.lat_dev != 0) != LAT : LAT) return;
         if (a.stage_dev && *a.stage_dev != a.stage_want) return;
     }
     constexpr bool FAST = ALT && f4_sums(MODE);
@@ -494,7 +516,7 @@ void trace_kernel(const TraceArgs a)
     __shared__ Pencil s_pencil[TRACE_BLOCK / 64];
     Pencil pencil;
     bool is_pencil = false;
-    if (axis < 0 && MODE != MODE_STATS && beam.olo[0] == beam.ohi[0] && beam.olo[1] == beam.ohi[1]
+    if (!PLANNED && axis < 0 && MODE != MODE_STATS && beam.olo[0] == beam.ohi[0] && beam.olo[1] == beam.ohi[1]
         && beam.olo[2] == beam.ohi[2]) {
         float sx = dx, sy = dy, sz = dz;
 #pragma unroll
@@ -764,7 +786,7 @@ void trace_kernel(const TraceArgs a)
     // and directions -- keeps nearly every group, where the walk's per-ray slab tests prune
     // exactly: 262144 random rays through 10^7 spheres took 990 ms with the group passes against
     // 145 ms with the walk.  Those packets keep the walk.
-    bool flat = FLAT_OK && (axis >= 0 || is_pencil);
+    bool flat = FLAT_OK && !PLANNED && (axis >= 0 || is_pencil);
     int groups_kept = 0;                    // surviving groups of this packet (wave-uniform)
     const float4* const group_boxes = a.C + 2 * ((size_t(a.n_prims) + 63) >> 6) + 1;
     // The passes sweep [0, covered): the primitives the tree's leaves cover (node_prims_kernel),
@@ -779,7 +801,7 @@ void trace_kernel(const TraceArgs a)
     // All passes are made up front, their loads in flight together (made one by one between the
     // sweeps, each pass exposed its load latency: 39 of them per wave at 10^7 primitives); the
     // survivor masks wait in LDS.
-    __shared__ unsigned long long s_group_mask[FLAT_OK ? TRACE_BLOCK / 64 : 1][FLAT_OK ? 64 : 1];
+    __shared__ unsigned long long s_group_mask[FLAT_OK && !PLANNED ? TRACE_BLOCK / 64 : 1][FLAT_OK && !PLANNED ? 64 : 1];
     if (flat && axis < 0) {
         // pencil packets: their cluster test on the group boxes
         const int wvg = threadIdx.x >> 6;
@@ -850,7 +872,11 @@ void trace_kernel(const TraceArgs a)
     // spheres: 16.5 ms walking, 31 ms with every packet on the group passes, 16.6 ms with this rule.
     constexpr int FLAT_MAX_GROUPS = 256;
     if (flat && groups_kept > FLAT_MAX_GROUPS) flat = false;
-    if (!flat) push(*a.root, ~0ull);
+    if (!flat && !PLANNED) push(*a.root, ~0ull);
+    // PLANNED: the list being walked (wave-uniform) and the next class of this wave
+    const __attribute__((address_space(4))) plan_u32x4* plan_at = nullptr;
+    int plan_n = 0, plan_cls = own_lo;
+    (void)plan_at; (void)plan_n; (void)plan_cls;
     unsigned long long st_walk = 0, st_cluster = 0, st_cull = 0, st_surv = 0, st_rounds = 0, st_nsurv = 0;
     const unsigned long long st_begin = STAMP_NOW();
     (void)st_walk; (void)st_cluster; (void)st_cull; (void)st_surv; (void)st_rounds; (void)st_nsurv; (void)st_begin;
@@ -859,7 +885,15 @@ void trace_kernel(const TraceArgs a)
         const unsigned long long st_t0 = STAMP_NOW(); (void)st_t0;
         int sweep_first = 0, sweep_count = 0;
         bool sweep = false;
-        if (flat) {
+        if constexpr (PLANNED) {
+            if (plan_cls >= own_hi) break;
+            const int list = packet * SUM_CLASSES + plan_cls++;
+            plan_n = plan_const<int>(a.plan_counts)[list];
+            if (plan_n <= 0) continue;
+            plan_at = plan_const<plan_u32x4>(a.plan_entries) + plan_const<plan_i32x2>(a.plan_spans)[list].x;
+            cur_granule_end = 0;     // the first round of a list switches to its class accumulator
+            sweep = true; sweep_count = a.n_prims;
+        } else if (flat) {
             while (group_mask == 0ull && group_next < n_groups) {
                 group_mask = s_group_mask[threadIdx.x >> 6][group_next >> 6];
                 group_mask = (unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(group_mask))))
@@ -1004,7 +1038,9 @@ void trace_kernel(const TraceArgs a)
             // hardware's range check returning zeros for the masked lanes -- same images, frame
             // kernel +-0, hit counts -1.7 %, 1/8 shard +2.3 %: not kept.)
             auto load_cluster = [&](const int c, float4& m4, float2& m2) {
-                const int pj = min(max((c << 6) + lane, r_lo), r_hi - 1);
+                // (PLANNED: the cluster comes from the plan; clamped as unsigned, so in range whatever it holds)
+                const int pj = PLANNED ? int(min(uint32_t(c << 6) + uint32_t(lane), uint32_t(r_hi - 1)))
+                                       : min(max((c << 6) + lane, r_lo), r_hi - 1);
                 m4 = a.A[pj];
                 if (LDS_TILE && NEED_B) m2 = a.B[pj];
                 if (D4) mined_next = reinterpret_cast<const double4*>(a.spheres_d)[pj];
@@ -1020,11 +1056,11 @@ void trace_kernel(const TraceArgs a)
             // The range's clusters, 64 at a time: lane j decides for cluster cg + j whether ANY ray
             // of the packet can hit ANY of its members (cluster_may_hit); culling rounds then run
             // over the surviving clusters only, in ascending order.
-            for (int cg = c_first; cg <= c_last; cg += 64) {
+            for (int cg = c_first; cg <= (PLANNED ? c_first : c_last); cg += 64) {
                 const unsigned long long st_t1 = STAMP_NOW(); (void)st_t1;
                 unsigned long long cmask = 1ull;
                 unsigned long long small_mask = ~0ull;   // clusters with members smaller than the ray spacing
-                if (c_last != c_first) {   // (one cluster -- a small leaf -- goes straight to its round)
+                if (!PLANNED && c_last != c_first) {   // (one cluster -- a small leaf -- goes straight to its round)
                     const int cj = min(cg + lane, c_last);
                     const float4 blo = a.C[2 * size_t(cj)], bhi = a.C[2 * size_t(cj) + 1];
                     const bool c_may = cluster_may_hit<AX>(blo, bhi, beam, &s_pencil[wv]);
@@ -1043,6 +1079,15 @@ void trace_kernel(const TraceArgs a)
                 if (cmask == 0ull) continue;
                 int cnext = cg + __builtin_ctzll(cmask);
                 cmask &= cmask - 1ull;
+                // PLANNED: entries i, i + 1, i + 2 of the list (wave-uniform: scalar loads; the plan is
+                // padded so that reading past a list's end stays inside it)
+                plan_u32x4 e0 = { 0u, 0u, 0u, 0u }, e1 = e0, e2 = e0;
+                int plan_i = 0;
+                (void)plan_i;
+                if constexpr (PLANNED) {
+                    e0 = plan_at[0]; e1 = plan_at[1]; e2 = plan_at[2];
+                    cnext = int(e0.x);
+                }
                 // A round's 64 candidates are fetched one round ahead (vector loads, 16 B/lane,
                 // coalesced) so that their latency hides behind the previous round's survivors.
                 // (Round 3, measured and rejected: two register sets taking turns with the round
@@ -1066,8 +1111,16 @@ void trace_kernel(const TraceArgs a)
 #pragma unroll
                         for (int c = 0; c < NW; ++c) mw[c] = mw_next[c];
                     }
-                    const bool more = cmask != 0ull;
-                    if (more) {
+                    bool more = cmask != 0ull;
+                    const plan_u32x4 ent = e0;
+                    if constexpr (PLANNED) {
+                        more = ++plan_i < plan_n;
+                        e0 = e1; e1 = e2; e2 = plan_at[plan_i + 2];
+                        if (more) {
+                            cnext = int(e0.x);
+                            load_cluster(cnext, mine_next, mineb_next);
+                        }
+                    } else if (more) {
                         cnext = cg + __builtin_ctzll(cmask);
                         cmask &= cmask - 1ull;
                         load_cluster(cnext, mine_next, mineb_next);
@@ -1080,25 +1133,29 @@ void trace_kernel(const TraceArgs a)
                 // there is no control flow; lane masks are formed from ballots of the bare
                 // comparisons and combined on the scalar unit: a ballot of a combined boolean
                 // costs two extra vector instructions each.)
-                bool may_hit;
-                if constexpr (AX >= 0) may_hit = axis_beam_may_hit<AX, FAST>(mine, beam);
+                bool may_hit = false;
+                if constexpr (PLANNED) { }
+                else if constexpr (AX >= 0) may_hit = axis_beam_may_hit<AX, FAST>(mine, beam);
                 else if constexpr (AX == -2) may_hit = pencil_may_hit(mine, s_pencil[wv]);
                 else may_hit = beam_may_hit(mine, beam);
-                unsigned long long rest = __builtin_amdgcn_ballot_w64(may_hit) & m_mask;
+                unsigned long long rest = PLANNED
+                    ? ((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(int(ent.y)))
+                       | ((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(int(ent.z))) << 32))
+                    : (__builtin_amdgcn_ballot_w64(may_hit) & m_mask);
                 bool keep = __builtin_amdgcn_inverse_ballot_w64(rest);   // (the scalar mask itself: no lane compares)
                 // Axis packets: if every kept candidate lies inside every ray's [0, length)
                 // along the axis -- decided per candidate with the same FMA the rays use, which
                 // is monotone in its addend -- the round's survivors skip the two range tests.
-                bool lean_round = false;
-                if constexpr (AX >= 0 && f4_class_split(MODE)) {
+                bool lean_round = PLANNED && (__builtin_amdgcn_readfirstlane(int(ent.w)) & 1) != 0;
+                if constexpr (!PLANNED && AX >= 0 && f4_class_split(MODE)) {
                     const float sa = AX == 0 ? mine.x : AX == 1 ? mine.y : mine.z;
                     const unsigned long long inside =
                         __builtin_amdgcn_ballot_w64(__builtin_fmaf(sa, da0, noda_lo) >= 0.0f)
                         & __builtin_amdgcn_ballot_w64(__builtin_fmaf(sa, da0, noda_hi) < len_lo);
                     lean_round = same_sense & ((rest & ~inside) == 0ull);
                 }
-                bool fat_round = false;
-                if constexpr (LEAN4)
+                bool fat_round = PLANNED && (__builtin_amdgcn_readfirstlane(int(ent.w)) & 2) != 0;
+                if constexpr (LEAN4 && !PLANNED)
                     fat_round = (rest & ~__builtin_amdgcn_ballot_w64(mine.w >= fat_r2)) == 0ull;
                 if constexpr (LATTICE && AX >= 0) {
                     // Origin-lattice cull (see the packet set-up): only in rounds over clusters that
@@ -1549,8 +1606,10 @@ void trace_kernel(const TraceArgs a)
             case 1: sweep_range(std::integral_constant<int, 1>()); break;
             case 2: sweep_range(std::integral_constant<int, 2>()); break;
             default:
-                if (is_pencil) sweep_range(std::integral_constant<int, -2>());
-                else sweep_range(std::integral_constant<int, -1>());
+                if constexpr (!PLANNED) {   // (a plan is usable only if every packet is axis-aligned)
+                    if (is_pencil) sweep_range(std::integral_constant<int, -2>());
+                    else sweep_range(std::integral_constant<int, -1>());
+                }
                 break;
             }
             // Keep the warming load alive (child / primitive indices are never negative).

@@ -1,0 +1,312 @@
+// The packet plan of the column-density traces, for gfx950 (see PacketPlan in trace_state.hpp):
+// the kernel that records it, its buffers, and the PLANNED instantiations of trace_kernel that
+// consume it (a translation unit of their own: they compile beside trace.hip's).
+//
+// The record kernel is the cull of trace_kernel's axis path on its own -- group boxes, cluster
+// boxes, then per culling round the exact beam bound, the lean / fat decisions and the
+// origin-lattice cull -- one wave per packet, all eight classes, no survivor loop.  It is not a
+// hot path (it runs when a plan is first sized and recorded, and again when a signature goes
+// stale), so the axis is a run-time value and nothing is prefetched.  A recorded mask need not
+// equal the mask the ordinary kernel would form: any conservative superset of the true hits gives
+// the same sums bit for bit (the exact integral tests every survivor; the fast one adds exactly +0
+// for a miss), as long as the lean and fat bits are decided on the recorded survivors, which they
+// are.  The lattice cull is applied wherever the packet's origins form a lattice, whatever the
+// batch-level flag says.
+#include "trace_kernel.hpp"
+
+#include <vector>
+
+using namespace grace_hip;
+
+namespace {
+
+struct PlanRef {
+    uint4* entries;
+    const int2* spans;   // null: sizing pass (counts only)
+    int* counts;
+    PlanCtl* ctl;
+    int force;           // record whatever ctl->record says (the first fill)
+};
+
+template <bool FUSED>
+__global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArgs a, const PlanRef pl)
+{
+    __shared__ float s_lat[TRACE_BLOCK / 64][2][8];   // the packets' origin lattices
+    if (pl.spans && !pl.force && pl.ctl->record == 0u) return;   // (workgroup-uniform)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int n_packets = (a.n_rays + a.width - 1) / a.width;
+    const int packet = blockIdx.x * (TRACE_BLOCK / 64) + wv;
+    if (packet >= n_packets) return;
+    // the packet's rays, as trace_kernel loads them
+    const int first_ray = packet * a.width;
+    const int slot_index = first_ray + lane;
+    const bool valid = lane < a.width && slot_index < a.n_rays;
+    const int slot_clamped = valid ? slot_index : min(first_ray + a.width, a.n_rays) - 1;
+    const int ray_index = a.perm ? int(a.perm[slot_clamped]) : slot_clamped;
+    const float* rp = a.rays + 7 * size_t(ray_index);
+    const float dx = rp[0], dy = rp[1], dz = rp[2];
+    const float ox = rp[3], oy = rp[4], oz = rp[5];
+    const float len = rp[6];
+    int axis = -1;
+    {
+        const unsigned long long all = ~0ull;
+        const bool zx = dx == 0.f, zy = dy == 0.f, zz = dz == 0.f;
+        if (__builtin_amdgcn_ballot_w64(zy && zz && fabsf(dx) == 1.f) == all) axis = 0;
+        else if (__builtin_amdgcn_ballot_w64(zx && zz && fabsf(dy) == 1.f) == all) axis = 1;
+        else if (__builtin_amdgcn_ballot_w64(zx && zy && fabsf(dz) == 1.f) == all) axis = 2;
+    }
+    const float4* const group_boxes = a.C + 2 * ((size_t(a.n_prims) + 63) >> 6) + 1;
+    const int covered = min(__float_as_int(group_boxes[-1].y), a.n_prims);
+    int cnt = 0;     // lane c < SUM_CLASSES: entries of class c so far
+    bool failed = axis < 0 || covered < 0;   // not an axis-aligned flat packet: no plan for this batch
+    if (!failed) {
+        const float oa = axis == 0 ? ox : axis == 1 ? oy : oz;
+        const float da = axis == 0 ? dx : axis == 1 ? dy : dz;
+        const float o1 = axis == 0 ? oy : ox;
+        const float o2 = axis == 2 ? oy : oz;
+        const float noda = -(oa * da);
+        const float lo1 = wave_min(o1), hi1 = wave_max(o1), lo2 = wave_min(o2), hi2 = wave_max(o2);
+        const float noda_lo = wave_min(noda), noda_hi = wave_max(noda), len_lo = wave_min(len);
+        const unsigned long long fwd = __builtin_amdgcn_ballot_w64(da > 0.f);
+        const bool same_sense = fwd == 0ull || fwd == ~0ull;
+        const float da0 = fwd ? 1.f : -1.f;
+        const float ea = oa + da * len;
+        const float alo = wave_min(fminf(oa, ea)), ahi = wave_max(fmaxf(oa, ea));
+        // (trace_kernel's fat_r2: survivors at least this wide need no clamp of the table position)
+        const float e1 = hi1 - lo1, e2 = hi2 - lo2;
+        const float fat_r2 = (e1 * e1 + e2 * e2) * (1.0f / 9.0f) * 1.0001f;
+        // origin lattice (trace_kernel's LAT set-up): the distinct values of each perpendicular origin
+        bool lat_ok = true;
+        float cell2 = 0.f;
+#pragma unroll
+        for (int dim = 0; dim < 2; ++dim) {
+            const float o = dim ? o2 : o1;
+            unsigned long long todo = ~0ull;
+            int n_val = 0;
+            float v = 0.f, v_lo = INFINITY, v_hi = -INFINITY;
+#pragma unroll 1
+            for (int k = 0; k < 8 && todo != 0ull; ++k) {
+                v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, o),
+                                                                        __builtin_ctzll(todo)));
+                v_lo = fminf(v_lo, v); v_hi = fmaxf(v_hi, v);
+                todo &= ~__builtin_amdgcn_ballot_w64(o == v);
+                if (lane == 0) s_lat[wv][dim][k] = v;
+                ++n_val;
+            }
+            lat_ok = lat_ok && todo == 0ull;
+            if (lane == 0)
+                for (int k = n_val; k < 8; ++k) s_lat[wv][dim][k] = v;
+            const float gap = n_val > 1 ? (v_hi - v_lo) / float(n_val - 1) : 0.f;
+            cell2 += gap * gap;
+        }
+        const float lat_r2 = lat_ok ? cell2 : 0.f;
+
+        // a box against the packet's origin rectangle (and, for groups, its extent along the axis)
+        auto box_may_hit = [&](const float4 blo, const float4 bhi, const bool along) {
+            const float l1 = axis == 0 ? blo.y : blo.x, h1 = axis == 0 ? bhi.y : bhi.x;
+            const float l2 = axis == 2 ? blo.y : blo.z, h2 = axis == 2 ? bhi.y : bhi.z;
+            const float la = axis == 0 ? blo.x : axis == 1 ? blo.y : blo.z;
+            const float ha = axis == 0 ? bhi.x : axis == 1 ? bhi.y : bhi.z;
+            // (negated forms: a NaN bound keeps the box)
+            return !(l1 > hi1) && !(h1 < lo1) && !(l2 > hi2) && !(h2 < lo2)
+                && (!along || (!(la > ahi) && !(ha < alo)));
+        };
+        const int n_groups = int((size_t(covered) + (size_t(1) << a.group_shift) - 1) >> a.group_shift);
+        for (int g0 = 0; g0 < n_groups; g0 += 64) {
+            const int gj = min(g0 + lane, n_groups - 1);
+            const bool g_may = box_may_hit(group_boxes[2 * size_t(gj)], group_boxes[2 * size_t(gj) + 1], true);
+            const int n_g = min(64, n_groups - g0);
+            unsigned long long gmask = __builtin_amdgcn_ballot_w64(g_may) & (n_g >= 64 ? ~0ull : ((1ull << n_g) - 1ull));
+            while (gmask != 0ull) {
+                const int g = g0 + __builtin_ctzll(gmask);
+                gmask &= gmask - 1ull;
+                const int r_lo = g << a.group_shift;
+                const int r_hi = r_lo + min(1 << a.group_shift, covered - r_lo);
+                const int c_first = r_lo >> 6, c_last = (r_hi - 1) >> 6;
+                for (int cg = c_first; cg <= c_last; cg += 64) {
+                    const int cj = min(cg + lane, c_last);
+                    const bool c_may = box_may_hit(a.C[2 * size_t(cj)], a.C[2 * size_t(cj) + 1], false);
+                    const int n_c = min(64, c_last - cg + 1);
+                    unsigned long long cmask = __builtin_amdgcn_ballot_w64(c_may)
+                        & (n_c >= 64 ? ~0ull : ((1ull << n_c) - 1ull));
+                    while (cmask != 0ull) {
+                        const int c = cg + __builtin_ctzll(cmask);
+                        cmask &= cmask - 1ull;
+                        const int pbase = c << 6;
+                        const int pj = min(max(pbase + lane, r_lo), r_hi - 1);
+                        const float4 mine = a.A[pj];
+                        const int lo_bit = max(r_lo - pbase, 0), hi_bit = min(r_hi - pbase, 64);
+                        const unsigned long long m_mask =
+                            (hi_bit >= 64 ? ~0ull : ((1ull << hi_bit) - 1ull)) & (~0ull << lo_bit);
+                        const float s1 = axis == 0 ? mine.y : mine.x;
+                        const float s2 = axis == 2 ? mine.y : mine.z;
+                        const float sa = axis == 0 ? mine.x : axis == 1 ? mine.y : mine.z;
+                        // axis_beam_may_hit: the exact lower bound of the rays' own b^2 expression
+                        const float q1 = s1 - __builtin_amdgcn_fmed3f(s1, lo1, hi1);
+                        const float q2 = s2 - __builtin_amdgcn_fmed3f(s2, lo2, hi2);
+                        const float b2_lo = FUSED ? __builtin_fmaf(q1, q1, q2 * q2) : q1 * q1 + q2 * q2;
+                        bool keep = !(b2_lo >= mine.w);
+                        unsigned long long rest = __builtin_amdgcn_ballot_w64(keep) & m_mask;
+                        keep = __builtin_amdgcn_inverse_ballot_w64(rest);
+                        if (rest != 0ull && __builtin_amdgcn_ballot_w64(keep && mine.w < lat_r2) != 0ull) {
+                            float p1 = INFINITY, p2 = INFINITY;
+                            for (int k = 0; k < 8; ++k) {
+                                p1 = fminf(p1, fabsf(s1 - s_lat[wv][0][k]));
+                                p2 = fminf(p2, fabsf(s2 - s_lat[wv][1][k]));
+                            }
+                            const float nan_if_nan = (s1 + s2) * 0.0f;   // (a NaN centre stays)
+                            const float l2 = (FUSED ? __builtin_fmaf(p1, p1, p2 * p2) : p1 * p1 + p2 * p2) + nan_if_nan;
+                            keep = keep && !(l2 >= mine.w);
+                            rest = __builtin_amdgcn_ballot_w64(keep);
+                        }
+                        if (rest == 0ull) continue;
+                        // lean: every survivor lies inside every ray's [0, length) along the axis
+                        const unsigned long long inside =
+                            __builtin_amdgcn_ballot_w64(__builtin_fmaf(sa, da0, noda_lo) >= 0.0f)
+                            & __builtin_amdgcn_ballot_w64(__builtin_fmaf(sa, da0, noda_hi) < len_lo);
+                        const bool lean = same_sense && (rest & ~inside) == 0ull;
+                        const bool fat = FUSED && (rest & ~__builtin_amdgcn_ballot_w64(mine.w >= fat_r2)) == 0ull;
+                        const int cls = (c >> (GRANULE_SHIFT - 6)) & (SUM_CLASSES - 1);
+                        const int n = __builtin_amdgcn_readlane(cnt, cls);
+                        if (pl.spans) {
+                            const int2 span = pl.spans[packet * SUM_CLASSES + cls];
+                            if (n < span.y) {
+                                if (lane == 0)
+                                    pl.entries[size_t(span.x) + n] =
+                                        make_uint4(uint32_t(c), uint32_t(rest), uint32_t(rest >> 32),
+                                                   (lean ? 1u : 0u) | (fat ? 2u : 0u));
+                            } else {
+                                failed = true;   // the list has outgrown its room
+                            }
+                        }
+                        cnt += lane == cls ? 1 : 0;
+                    }
+                }
+            }
+        }
+    }
+    if (failed) {
+        cnt = 0;
+        if (lane == 0) { pl.ctl->unusable = 1u; pl.ctl->usable = 0u; }
+    }
+    if (lane < SUM_CLASSES) pl.counts[packet * SUM_CLASSES + lane] = cnt;
+}
+
+grace_status launch_record(const bool fast, const TraceArgs& a, const PlanRef& pl, hipStream_t stream)
+{
+    const int n_packets = (a.n_rays + a.width - 1) / a.width;
+    const int grid = ceil_div(size_t(n_packets), size_t(TRACE_BLOCK / 64));
+    if (fast) plan_record_kernel<true><<<grid, TRACE_BLOCK, 0, stream>>>(a, pl);
+    else plan_record_kernel<false><<<grid, TRACE_BLOCK, 0, stream>>>(a, pl);
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+grace_status plan_free_buffers(PacketPlan& pp)
+{
+    void* bufs[] = { pp.entries, pp.spans, pp.counts, pp.ctl };
+    bool any = false;
+    for (void* b : bufs) any = any || b;
+    if (any) GRACE_TRY_HIP(hipDeviceSynchronize());
+    for (void* b : bufs)
+        if (b) GRACE_TRY_HIP(hipFree(b));
+    pp.entries = nullptr; pp.spans = nullptr; pp.counts = nullptr; pp.ctl = nullptr;
+    pp.valid = false;
+    pp.n_lists = pp.n_entries = pp.recorded = 0;
+    return GRACE_OK;
+}
+
+} // namespace
+
+namespace grace_hip {
+
+grace_status plan_release(TraceState& ts)
+{
+    GRACE_TRY(plan_free_buffers(ts.plan));
+    ts.plan = PacketPlan();
+    ts.last_plan_ctl = nullptr;
+    return GRACE_OK;
+}
+
+grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, hipStream_t stream)
+{
+    PacketPlan& pp = ts.plan;
+    GRACE_TRY(plan_free_buffers(pp));
+    ts.last_plan_ctl = nullptr;
+    pp.key = key;
+    pp.dead = true;      // until the plan stands
+    const int n_packets = (a.n_rays + a.width - 1) / a.width;
+    const size_t n_lists = size_t(n_packets) * SUM_CLASSES;
+    // (out of memory at any step: no plan, the call goes on without one)
+    auto alloc = [&](auto*& ptr, const size_t bytes) {
+        if (hipMalloc(reinterpret_cast<void**>(&ptr), bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        ptr = nullptr;
+        return false;
+    };
+    if (n_lists * (sizeof(int) + sizeof(int2)) > ts.plan_budget) return GRACE_OK;
+    if (!alloc(pp.counts, n_lists * sizeof(int)) || !alloc(pp.spans, n_lists * sizeof(int2))
+        || !alloc(pp.ctl, sizeof(PlanCtl)))
+        return plan_free_buffers(pp);
+    // 1. sizing pass: entries per list, and whether every packet can be planned at all
+    GRACE_TRY_HIP(hipMemsetAsync(pp.ctl, 0, sizeof(PlanCtl), stream));
+    GRACE_TRY(launch_record(key.fast, a, PlanRef{ nullptr, nullptr, pp.counts, pp.ctl, 1 }, stream));
+    std::vector<int> counts(n_lists);
+    PlanCtl seen = {};
+    GRACE_TRY_HIP(hipMemcpyAsync(counts.data(), pp.counts, n_lists * sizeof(int), hipMemcpyDeviceToHost, stream));
+    GRACE_TRY_HIP(hipMemcpyAsync(&seen, pp.ctl, sizeof(seen), hipMemcpyDeviceToHost, stream));
+    GRACE_TRY_HIP(hipStreamSynchronize(stream));
+    if (seen.unusable) return plan_free_buffers(pp);
+    // 2. room per list: what it holds now and an eighth more, so that a re-record after a small
+    //    change of the scene or the rays still fits
+    std::vector<int2> spans(n_lists);
+    size_t total = 0, used = 0;
+    for (size_t l = 0; l < n_lists; ++l) {
+        const size_t room = size_t(counts[l]) + size_t(counts[l]) / 8 + 2;
+        spans[l] = make_int2(int(total), int(room));
+        total += room;
+        used += size_t(counts[l]);
+        if (total >= (size_t(1) << 31)) return plan_free_buffers(pp);
+    }
+    const size_t bytes = (total + 4) * sizeof(uint4) + n_lists * (sizeof(int) + sizeof(int2));
+    if (bytes > ts.plan_budget || !alloc(pp.entries, (total + 4) * sizeof(uint4))) return plan_free_buffers(pp);
+    GRACE_TRY_HIP(hipMemcpy(pp.spans, spans.data(), n_lists * sizeof(int2), hipMemcpyHostToDevice));
+    // (the padding the planned kernel may read past the last list)
+    GRACE_TRY_HIP(hipMemsetAsync(pp.entries + total, 0, 4 * sizeof(uint4), stream));
+    pp.n_lists = n_lists; pp.n_entries = total; pp.recorded = used;
+    // 3. record
+    GRACE_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&pp.ctl->usable), 1, 1, stream));
+    GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[0], ts.scene.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
+    GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[2], ts.rays.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
+    GRACE_TRY(launch_record(key.fast, a, PlanRef{ pp.entries, pp.spans, pp.counts, pp.ctl, 1 }, stream));
+    pp.valid = true;
+    pp.dead = false;
+    return GRACE_OK;
+}
+
+grace_status plan_record(const TraceState& ts, const TraceArgs& a, hipStream_t stream)
+{
+    const PacketPlan& pp = ts.plan;
+    return launch_record(pp.key.fast, a, PlanRef{ pp.entries, pp.spans, pp.counts, pp.ctl, 0 }, stream);
+}
+
+grace_status launch_planned(const int mode, const bool fast, const int grid, const TraceArgs& a, hipStream_t stream)
+{
+    auto go = [&](auto mode_tag) {
+        constexpr int MODE = decltype(mode_tag)::value;
+        if (fast) trace_kernel<MODE, true, true, false, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);
+        else trace_kernel<MODE, true, false, false, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);
+    };
+    switch (mode) {
+    case MODE_CUMULATIVE: go(std::integral_constant<int, MODE_CUMULATIVE>()); break;
+    case MODE_WCUM1: go(std::integral_constant<int, MODE_WCUM1>()); break;
+    case MODE_WCUM2: go(std::integral_constant<int, MODE_WCUM2>()); break;
+    case MODE_WCUM3: go(std::integral_constant<int, MODE_WCUM3>()); break;
+    case MODE_WCUM4: go(std::integral_constant<int, MODE_WCUM4>()); break;
+    default: return set_error(GRACE_INVALID_ARGUMENT, __FILE__, __LINE__, "no planned kernel for this mode");
+    }
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+} // namespace grace_hip

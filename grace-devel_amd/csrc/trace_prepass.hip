@@ -332,6 +332,7 @@ grace_status scene_cache_alloc(TraceState& ts, const SceneKey& key)
     if (st == GRACE_OK) st = alloc(reinterpret_cast<void**>(&sc.ctl), sizeof(CacheCtl));
     if (st != GRACE_OK) { (void)scene_free_buffers(sc); return st; }
     sc.key = key;
+    sc.gen = ++ts.cache_gen;
     return GRACE_OK;
 }
 

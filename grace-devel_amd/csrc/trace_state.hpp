@@ -196,6 +196,13 @@ struct TraceArgs {
     // memory (a row of the built-in tables, or the context's custom table).  Captured when the call
     // is enqueued; the prologue copies it into LDS (s_lut / s_lutf) and nothing else reads it.
     const double* kernel_table;
+    // Packet plan (appended; see PacketPlan below; all null: no plan for this call).  List
+    // packet * SUM_CLASSES + class holds plan_counts[list] entries from plan_entries[plan_spans[list].x]
+    // on.  *plan_usable != 0: the planned kernel runs and the others return at once; 0: the reverse.
+    const uint4* plan_entries;
+    const int2* plan_spans;
+    const int* plan_counts;
+    const uint32_t* plan_usable;
 };
 
 
@@ -238,6 +245,7 @@ struct Scene {
     int2* node_prims = nullptr; float4* C = nullptr;
     CacheCtl* ctl = nullptr;
     bool pinned = false;          // filled by grace_trace_prepare_*: kept until released / replaced
+    unsigned long long gen = 0;   // which fill of the cache this is (TraceState::cache_gen; see PacketPlan)
 };
 
 struct RayKey {
@@ -255,6 +263,62 @@ struct RayOrder {
                                   // of d, o), [14] not-a-grid flag, [15] longest ray
     CacheCtl* ctl = nullptr;
     bool pinned = false;
+    unsigned long long gen = 0;
+};
+
+// Packet plan (trace_planned.hip): the cull of an axis-aligned batch -- which groups, clusters and
+// candidates survive for each packet -- is a function of the ray order and the scene records alone,
+// the two things the caches above hold and validate.  Once both caches serve a call, the cull is
+// recorded: for every packet and summation class, the ordered list of its non-empty culling
+// rounds, 16 bytes each: {cluster, survivor mask lo, hi, flags (bit 0: lean round, bit 1: fat
+// round)}.  The planned kernel (trace_kernel<.., PLANNED>) walks the lists of its classes and runs
+// the survivor loops; it makes no group pass, cluster test or cull.  The lists are per class
+// because a class is summed in ascending primitive order and nothing depends on the order between
+// classes: one plan serves every packet split K.
+// The plan is tied to the fills of the two caches it was recorded from (gen) and remembers their
+// signatures: when either cache's signature has moved on -- its records were re-derived, by this
+// call or by a call of another kind in between -- the plan is re-recorded in place on that call
+// (PlanCtl::record, set on the device).  A batch with a
+// packet that is not axis-aligned, a list that outgrows its room on a re-record, or a plan beyond
+// the byte budget is unusable: the call runs the ordinary kernels.
+struct PlanCtl {                  // device memory
+    uint32_t record;              // this call re-records (set by the gate in choose_variants_kernel)
+    uint32_t unusable;            // set by the record kernel
+    uint32_t usable;              // its complement (a run_if for the kernels that follow)
+    uint32_t pad;
+    unsigned long long sig[4];    // the scene cache's and the ray cache's signatures it was recorded under
+};
+
+struct PlanKey {
+    bool fast = false;            // axis_beam_may_hit<AX, FUSED> bounds the b^2 the survivors compute
+    int group_shift = 0, width = 0;
+    bool reorder = false;
+    size_t n_rays = 0, n_prims = 0;
+    unsigned long long scene_gen = 0, rays_gen = 0;
+    bool operator==(const PlanKey& o) const
+    {
+        return fast == o.fast && group_shift == o.group_shift && width == o.width && reorder == o.reorder
+            && n_rays == o.n_rays && n_prims == o.n_prims && scene_gen == o.scene_gen && rays_gen == o.rays_gen;
+    }
+};
+
+struct PacketPlan {
+    bool valid = false;           // the buffers hold a plan recorded under `key`
+    bool dead = false;            // `key`'s batch cannot be planned (known on the host): nothing is launched for it
+    PlanKey key;
+    uint4* entries = nullptr;     // n_entries + 4 (the planned kernel reads up to three entries ahead)
+    int2* spans = nullptr;        // per list {first entry, room}
+    int* counts = nullptr;        // per list
+    PlanCtl* ctl = nullptr;
+    size_t n_lists = 0, n_entries = 0;
+    size_t recorded = 0;          // entries in use when the plan was sized
+};
+
+// What the device-side gate of a call with a recorded plan needs (launch_choose_variants).
+struct PlanGate {
+    const CacheCtl* scene = nullptr;   // the caches the plan was recorded from
+    const CacheCtl* rays = nullptr;
+    PlanCtl* ctl = nullptr;
 };
 
 // trace_sph walks twice -- hit counts (for the offsets), then the per-hit pass -- and the split
@@ -298,9 +362,16 @@ struct TraceState {
     const double* kernel_table = nullptr;
     double* custom_table = nullptr;          // N_TABLE doubles, allocated by the first custom table
     double custom_host[N_TABLE] = {};        // its host copy (grace_trace_get_sph_kernel)
+    bool plan_on = true;                   // record and use packet plans (grace_trace_set_plan)
+    size_t plan_budget = size_t(512) << 20;  // bytes a plan may take (grace_trace_set_plan_budget)
     Scene scene;
     RayOrder rays;
     HitsCache hits;
+    unsigned long long cache_gen = 0;      // fills of the scene / ray caches so far
+    PacketPlan plan;
+    // Measurement hook (grace_trace_last_plan_used): the last class-sum launch's plan flags
+    const PlanCtl* last_plan_ctl = nullptr;
+    hipStream_t last_plan_stream = nullptr;
 };
 
 // The TraceState of the calling thread's context (created on first use).
@@ -377,7 +448,19 @@ grace_status ray_order(const float* d_rays, size_t n_rays, uint32_t* ext, uint32
                        hipStream_t stream, const uint32_t* run_if = nullptr);
 grace_status rays_prepare(TraceState& ts, const float* d_rays, size_t n_rays, hipStream_t stream);
 // The device-side choices of a trace launch for a batch whose order is cached.
+// gate (optional): also decides whether this call re-records its packet plan.
 grace_status launch_choose_variants(const uint32_t* ext12, int n, const float4* scene_min, uint32_t* lat_flag,
-                                    int split_packets, int split_launched, int* split_dev, hipStream_t stream);
+                                    int split_packets, int split_launched, int* split_dev, hipStream_t stream,
+                                    const PlanGate* gate = nullptr);
+
+// trace_planned.hip: the packet plan, its record kernel and the planned class-sum kernels.
+grace_status plan_release(TraceState& ts);
+// Sizes, allocates and records the plan of `key` for the batch `a` describes (its records and ray
+// order already queued on `stream`); synchronises the stream once.  On return ts.plan is valid, or dead.
+grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, hipStream_t stream);
+// The gated re-record of a call with a valid plan.
+grace_status plan_record(const TraceState& ts, const TraceArgs& a, hipStream_t stream);
+// trace_kernel<mode, SPLIT, fast, false, PLANNED> over `grid` workgroups (mode: f4_sums).
+grace_status launch_planned(int mode, bool fast, int grid, const TraceArgs& a, hipStream_t stream);
 
 } // namespace grace_hip

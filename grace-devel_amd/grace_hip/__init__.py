@@ -398,6 +398,30 @@ def set_cache_auto(enabled):
     _check(_lib.grace_trace_set_cache_auto(C.c_int(1 if enabled else 0)))
 
 
+def set_plan(enabled):
+    """Record and use packet plans for column-density traces served by both caches."""
+    _check(_lib.grace_trace_set_plan(C.c_int(1 if enabled else 0)))
+
+
+def set_plan_budget(n_bytes):
+    """Device memory a packet plan may take (a plan beyond it is not kept)."""
+    _check(_lib.grace_trace_set_plan_budget(C.c_size_t(int(n_bytes))))
+
+
+def plan_bytes():
+    """Device memory of the context's current packet plan (0: none)."""
+    v = C.c_size_t(0)
+    _check(_lib.grace_trace_plan_bytes(C.byref(v)))
+    return v.value
+
+
+def last_plan_used():
+    """1 if the last column-density trace ran the planned kernel (measurement hook)."""
+    v = C.c_int(0)
+    _check(_lib.grace_trace_last_plan_used(C.byref(v)))
+    return v.value
+
+
 def set_lattice_split(k):
     _check(_lib.grace_trace_set_lattice_split(C.c_int(k)))
 

@@ -609,6 +609,30 @@ grace_status grace_trace_release_rays(void);
 grace_status grace_trace_set_cache_validation(int enabled);
 grace_status grace_trace_set_cache_auto(int enabled);
 
+/* Packet plan of the column-density traces (grace_trace_cumulative_f4, _weighted_f4).  Which groups,
+ * clusters and candidates a packet of axis-aligned rays has to look at depends on the rays, their
+ * coherence order and the scene records only: once BOTH caches above serve a call (each has seen
+ * its arrays repeated, or was prepared), that call records the cull -- per packet and summation
+ * class the list of its non-empty culling rounds, 16 bytes each -- and later calls on the same
+ * arrays (the next frame field, the next group of weight channels, another SPH kernel, any packet
+ * split) run the survivor loops from the plan without repeating it.  The plan lives and dies with
+ * the two caches; when a signature shows that the scene or the rays have changed, the same call
+ * re-records it in place on the device.  The call that first records a plan synchronises its
+ * stream once (it sizes the plan on the host).  A batch with a packet that is not axis-aligned, or
+ * whose plan would exceed the byte budget, has no plan and runs as before.  Results are bit for bit
+ * those without a plan.
+ * grace_trace_set_plan(0 / 1): off / on (default: see DESIGN.md section 6).
+ * grace_trace_set_plan_budget(bytes): the device memory a plan may take (default 512 MiB; the
+ * 1024^2 frame over 10^7 particles takes about a fifth of that).
+ * grace_trace_plan_bytes: the device memory of the current plan (0: none).
+ * grace_trace_last_plan_used (measurement hook, in the manner of grace_trace_last_lattice): 1 if
+ * the last column-density trace ran the planned kernel, else 0.  Synchronises.
+ * Not part of the reference API. */
+grace_status grace_trace_set_plan(int on);
+grace_status grace_trace_set_plan_budget(size_t bytes);
+grace_status grace_trace_plan_bytes(size_t* h_bytes);
+grace_status grace_trace_last_plan_used(int* h_used);
+
 /* Reads (and clears) the traversal status word: GRACE_STACK_OVERFLOW if any packet ran out
  * of its 128-entry stack since the last check (the reference only asserts this in
  * GRACE_DEBUG builds, bintree_trace.cuh:164); GRACE_INVALID_ARGUMENT if grace_range_neighbours_f4
