@@ -308,7 +308,7 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
     auto held = [](const CacheUse u) { return u == USE_CHECK || u == USE_TRUST; };
     b.plan_eligible = ts.plan_on && f4_sums(MODE) && held(scene_use) && held(rays_use) && p.lat_split == 0;
     if (b.plan_eligible)
-        b.plan_key = PlanKey{ p.fast_b, group_shift(n_prims), p.width, p.reorder, n_rays, n_prims, ts.scene.gen, ts.rays.gen };
+        b.plan_key = PlanKey{ PLAN_FORMAT, p.fast_b, group_shift(n_prims), p.width, p.reorder, n_rays, n_prims, ts.scene.gen, ts.rays.gen };
     // (a recorded plan of this key: the device-side gate decides whether this call re-records it)
     PlanGate gate;
     const bool plan_steady = b.plan_eligible && ts.plan.valid && ts.plan.key == b.plan_key;
@@ -976,6 +976,23 @@ grace_status grace_trace_last_plan_used(int* h_used)
         GRACE_TRY_HIP(hipStreamSynchronize(ts.last_plan_stream));
         GRACE_TRY_HIP(hipMemcpy(&h, ts.last_plan_ctl, sizeof(h), hipMemcpyDeviceToHost));
         *h_used = h.usable != 0u ? 1 : 0;
+    }
+    return GRACE_OK;
+}
+
+grace_status grace_trace_plan_stats(unsigned long long* h_stats)
+{
+    GRACE_REQUIRE(h_stats, "null output");
+    for (int k = 0; k < 7; ++k) h_stats[k] = 0;
+    GRACE_TRACE_STATE();
+    if (ts.last_plan_ctl) {
+        PlanCtl h = {};
+        GRACE_TRY_HIP(hipStreamSynchronize(ts.last_plan_stream));
+        GRACE_TRY_HIP(hipMemcpy(&h, ts.last_plan_ctl, sizeof(h), hipMemcpyDeviceToHost));
+        if (h.usable != 0u) {
+            for (int k = 0; k < 6; ++k) h_stats[k] = h.stats[k];
+            h_stats[6] = h.largest_round;
+        }
     }
     return GRACE_OK;
 }

@@ -239,6 +239,8 @@ __global__ void choose_variants_kernel(const uint32_t* __restrict__ ext12, int n
             pc.unusable = 0u; pc.usable = 1u;
             pc.sig[0] = gate.scene->sig[0]; pc.sig[1] = gate.scene->sig[1];
             pc.sig[2] = gate.rays->sig[0]; pc.sig[3] = gate.rays->sig[1];
+            for (int k = 0; k < 6; ++k) pc.stats[k] = 0ull;   // (the re-record tallies afresh)
+            pc.largest_round = 0u;
         }
     }
 }

@@ -353,11 +353,12 @@ struct WeightedB {
 // class-split kernels registers they do not have, and the frame kernel 2 %, so scenes without
 // sub-spacing spheres must not carry it.
 // PLANNED: the packet-plan consumer (PacketPlan, trace_state.hpp) of the class-split column-density
-// kernels: each wave walks the recorded lists of its classes -- entry by entry the cluster to
-// fetch, the round's survivor mask and its lean / fat bits, read through scalar loads three
-// entries ahead -- and runs the survivor loops of the axis path as they are.  It makes no group
-// pass, no cluster test, no cull, keeps no stack and has no LAT variant (the recorded masks hold
-// the lattice cull's result).
+// kernels: each wave walks the recorded lists of its classes one DENSE ROUND at a time -- the
+// consecutive entries the recorder grouped (at most 64 survivors, one lean / fat class), read
+// through scalar loads four entries ahead; their survivors are gathered from all the round's
+// clusters, one per lane (gather_round, in the sweep) -- and runs the survivor loops of the axis
+// path as they are, once per dense round.  It makes no group pass, no cluster test, no cull, keeps
+// no stack and has no LAT variant (the recorded masks hold the lattice cull's result).
 template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false, bool PLANNED = false>
 // The one-wave-per-packet hit-count / column-density kernels are held to 6 waves per SIMD (<= 80
 // VGPRs): left to itself the register allocator drifts between 77 and 102 VGPRs from one edit of
@@ -891,7 +892,7 @@ void trace_kernel(const TraceArgs a)
             plan_n = plan_const<int>(a.plan_counts)[list];
             if (plan_n <= 0) continue;
             plan_at = plan_const<plan_u32x4>(a.plan_entries) + plan_const<plan_i32x2>(a.plan_spans)[list].x;
-            cur_granule_end = 0;     // the first round of a list switches to its class accumulator
+            enter_granule((plan_cls - 1) << GRANULE_SHIFT);   // the list's class accumulator (granule g is of class g & 7)
             sweep = true; sweep_count = a.n_prims;
         } else if (flat) {
             while (group_mask == 0ull && group_next < n_groups) {
@@ -1079,15 +1080,12 @@ void trace_kernel(const TraceArgs a)
                 if (cmask == 0ull) continue;
                 int cnext = cg + __builtin_ctzll(cmask);
                 cmask &= cmask - 1ull;
-                // PLANNED: entries i, i + 1, i + 2 of the list (wave-uniform: scalar loads; the plan is
-                // padded so that reading past a list's end stays inside it)
-                plan_u32x4 e0 = { 0u, 0u, 0u, 0u }, e1 = e0, e2 = e0;
+                // PLANNED: entries plan_i .. plan_i + 3 of the list (wave-uniform: scalar loads; the plan
+                // is padded so that reading past a list's end stays inside it)
+                plan_u32x4 e0 = { 0u, 0u, 0u, 0u }, e1 = e0, e2 = e0, e3 = e0;
                 int plan_i = 0;
                 (void)plan_i;
-                if constexpr (PLANNED) {
-                    e0 = plan_at[0]; e1 = plan_at[1]; e2 = plan_at[2];
-                    cnext = int(e0.x);
-                }
+                if constexpr (PLANNED) { e0 = plan_at[0]; e1 = plan_at[1]; e2 = plan_at[2]; e3 = plan_at[3]; }
                 // A round's 64 candidates are fetched one round ahead (vector loads, 16 B/lane,
                 // coalesced) so that their latency hides behind the previous round's survivors.
                 // (Round 3, measured and rejected: two register sets taking turns with the round
@@ -1099,9 +1097,62 @@ void trace_kernel(const TraceArgs a)
                 // the rounds without a loop leave the prefetch no time.)
                 float4 mine_next;
                 float2 mineb_next = make_float2(0.f, 0.f);
-                load_cluster(cnext, mine_next, mineb_next);
+                // PLANNED: a DENSE round -- the survivors of the list's next entries up to the one
+                // the recorder marked (at most 64, one lean / fat class).  Invert: entry by entry on
+                // the scalar unit, the lanes its mask names store their candidate's index at the
+                // round's running survivor count + their rank in the mask.  Gather: lane l reads
+                // index l and fetches that survivor's records -- one record per lane in flight
+                // however many clusters the round draws on.  Leaves the round's survivor count and
+                // bits in round_n_next / round_bits_next.  The 64 indices pass through the first
+                // 256 bytes of the wave's tile: the previous round's loop has read its survivors,
+                // this round's are staged after the gather, and a wave's LDS accesses keep their order.
+                int round_n_next = 0;
+                uint32_t round_bits_next = 0u;
+                (void)round_n_next; (void)round_bits_next;
+                auto gather_round = [&]() {
+                    if constexpr (PLANNED) {
+                        float* const idx = &s_tile[wv][0][0].x;
+                        int p = 0;
+                        round_bits_next = e0.w;
+                        // One entry: false once the round is complete (the entry may then be left for
+                        // the next round).
+                        auto take = [&](const plan_u32x4 ent) {
+                            const uint32_t m_lo = uint32_t(__builtin_amdgcn_readfirstlane(int(ent.y)));
+                            const uint32_t m_hi = uint32_t(__builtin_amdgcn_readfirstlane(int(ent.z)));
+                            const unsigned long long m = (unsigned long long)m_lo | ((unsigned long long)m_hi << 32);
+                            const int n_e = __builtin_popcountll(m);
+                            if (p + n_e > 64) return false;   // (never a round's first entry; a sound plan never gets here)
+                            if (__builtin_amdgcn_inverse_ballot_w64(m))
+                                idx[p + int(__builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u)))] =
+                                    __uint_as_float((uint32_t(__builtin_amdgcn_readfirstlane(int(ent.x))) << 6) + uint32_t(lane));
+                            p += n_e;
+                            ++plan_i;
+                            return (uint32_t(__builtin_amdgcn_readfirstlane(int(ent.w))) & 4u) == 0u && plan_i < plan_n;
+                        };
+                        // Four entries are at hand (fetched when the previous round was gathered: a
+                        // whole survivor loop ago); a longer round fetches four more at a time.
+                        while (take(e0) && take(e1) && take(e2) && take(e3)) {
+                            e0 = plan_at[plan_i]; e1 = plan_at[plan_i + 1]; e2 = plan_at[plan_i + 2]; e3 = plan_at[plan_i + 3];
+                        }
+                        e0 = plan_at[plan_i]; e1 = plan_at[plan_i + 1]; e2 = plan_at[plan_i + 2]; e3 = plan_at[plan_i + 3];
+                        round_n_next = p;
+                        // (lanes past the round's survivors read what an earlier round left: clamped
+                        // as unsigned like the rest, so in range whatever the slot or the plan holds)
+                        const int pj = int(min(__float_as_uint(idx[lane]), uint32_t(r_hi - 1)));
+                        mine_next = a.A[pj];
+                        if (NEED_B) mineb_next = a.B[pj];
+                        if constexpr (WEIGHTED) {
+#pragma unroll
+                            for (int c = 0; c < NW; ++c) mw_next[c] = a.weights[size_t(pj) * a.w_stride + c];
+                        }
+                    }
+                };
+                if constexpr (PLANNED) gather_round();
+                else load_cluster(cnext, mine_next, mineb_next);
                 for (;;) {
                     const unsigned long long st_t2 = STAMP_NOW(); (void)st_t2;
+                    // (PLANNED: cnext, pbase, cmask and the m_mask below are dead -- a dense round has no
+                    // one cluster; its candidates come from gather_round, its mask from round_n)
                     const int pbase = cnext << 6;          // first primitive of this round's cluster
                     const float4 mine = mine_next;
                     const float2 mineb = mineb_next;
@@ -1112,14 +1163,12 @@ void trace_kernel(const TraceArgs a)
                         for (int c = 0; c < NW; ++c) mw[c] = mw_next[c];
                     }
                     bool more = cmask != 0ull;
-                    const plan_u32x4 ent = e0;
+                    const int round_n = round_n_next;
+                    const uint32_t round_bits = round_bits_next;
+                    (void)round_n; (void)round_bits;
                     if constexpr (PLANNED) {
-                        more = ++plan_i < plan_n;
-                        e0 = e1; e1 = e2; e2 = plan_at[plan_i + 2];
-                        if (more) {
-                            cnext = int(e0.x);
-                            load_cluster(cnext, mine_next, mineb_next);
-                        }
+                        more = plan_i < plan_n;
+                        if (more) gather_round();   // the next round's inversion and loads, ahead of this round's loop
                     } else if (more) {
                         cnext = cg + __builtin_ctzll(cmask);
                         cmask &= cmask - 1ull;
@@ -1138,15 +1187,15 @@ void trace_kernel(const TraceArgs a)
                 else if constexpr (AX >= 0) may_hit = axis_beam_may_hit<AX, FAST>(mine, beam);
                 else if constexpr (AX == -2) may_hit = pencil_may_hit(mine, s_pencil[wv]);
                 else may_hit = beam_may_hit(mine, beam);
+                // (PLANNED: the round's survivors are lanes 0 .. n - 1, each with its own gathered record)
                 unsigned long long rest = PLANNED
-                    ? ((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(int(ent.y)))
-                       | ((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(int(ent.z))) << 32))
+                    ? (round_n >= 64 ? ~0ull : ((1ull << round_n) - 1ull))
                     : (__builtin_amdgcn_ballot_w64(may_hit) & m_mask);
                 bool keep = __builtin_amdgcn_inverse_ballot_w64(rest);   // (the scalar mask itself: no lane compares)
                 // Axis packets: if every kept candidate lies inside every ray's [0, length)
                 // along the axis -- decided per candidate with the same FMA the rays use, which
                 // is monotone in its addend -- the round's survivors skip the two range tests.
-                bool lean_round = PLANNED && (__builtin_amdgcn_readfirstlane(int(ent.w)) & 1) != 0;
+                bool lean_round = PLANNED && (__builtin_amdgcn_readfirstlane(int(round_bits)) & 1) != 0;
                 if constexpr (!PLANNED && AX >= 0 && f4_class_split(MODE)) {
                     const float sa = AX == 0 ? mine.x : AX == 1 ? mine.y : mine.z;
                     const unsigned long long inside =
@@ -1154,7 +1203,7 @@ void trace_kernel(const TraceArgs a)
                         & __builtin_amdgcn_ballot_w64(__builtin_fmaf(sa, da0, noda_hi) < len_lo);
                     lean_round = same_sense & ((rest & ~inside) == 0ull);
                 }
-                bool fat_round = PLANNED && (__builtin_amdgcn_readfirstlane(int(ent.w)) & 2) != 0;
+                bool fat_round = PLANNED && (__builtin_amdgcn_readfirstlane(int(round_bits)) & 2) != 0;
                 if constexpr (LEAN4 && !PLANNED)
                     fat_round = (rest & ~__builtin_amdgcn_ballot_w64(mine.w >= fat_r2)) == 0ull;
                 if constexpr (LATTICE && AX >= 0) {
@@ -1194,7 +1243,8 @@ void trace_kernel(const TraceArgs a)
                 // the class accumulator switch and the ownership test of a split packet stay out
                 // of the per-survivor loop.
                 bool skip_round = rest == 0ull;
-                if (!skip_round && (CLASSES || SPLIT)) {
+                // (PLANNED: a list is of one class, entered at its head)
+                if (!PLANNED && !skip_round && (CLASSES || SPLIT)) {
                     const int pf = pbase + __builtin_ctzll(rest);
                     if (CLASSES && pf >= cur_granule_end) enter_granule(pf); // ascending index
                     if (SPLIT && !(CLASSES ? cur_owned : owns_granule(pf >> GRANULE_SHIFT)))
@@ -1206,7 +1256,7 @@ void trace_kernel(const TraceArgs a)
                 if (LDS_TILE) {
                     // Stage the round's candidates; survivors are then broadcast-read from LDS
                     // into VGPRs (in-order LDS returns, no scalar-load round trips, VGPR operands).
-                    const int slot = COMPACT
+                    const int slot = PLANNED ? lane : COMPACT
                         ? int(__builtin_amdgcn_mbcnt_hi(uint32_t(rest >> 32),
                                                         __builtin_amdgcn_mbcnt_lo(uint32_t(rest), 0u)))
                         : lane;

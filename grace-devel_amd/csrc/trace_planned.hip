@@ -12,6 +12,8 @@
 // for a miss), as long as the lean and fat bits are decided on the recorded survivors, which they
 // are.  The lattice cull is applied wherever the packet's origins form a lattice, whatever the
 // batch-level flag says.
+// The recorder also groups each list's consecutive entries into dense rounds (PLAN_ROUND_END on a
+// round's last entry) and tallies what it formed in PlanCtl::stats.
 #include "trace_kernel.hpp"
 
 #include <vector>
@@ -58,6 +60,11 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
     const float4* const group_boxes = a.C + 2 * ((size_t(a.n_prims) + 63) >> 6) + 1;
     const int covered = min(__float_as_int(group_boxes[-1].y), a.n_prims);
     int cnt = 0;     // lane c < SUM_CLASSES: entries of class c so far
+    // Rounds (the planned kernel runs one survivor loop per round): consecutive entries of a list,
+    // at most 64 survivors together, all with the same lean / fat bits.  Lane c holds the open
+    // round of class c -- its survivors and its bits -- and the class's tallies for PlanCtl.
+    int round_n = 0, round_bits = 0;
+    int t_surv = 0, t_rounds = 0, t_full = 0, t_cap = 0, t_flag = 0, t_max = 0;
     bool failed = axis < 0 || covered < 0;   // not an axis-aligned flat packet: no plan for this batch
     if (!failed) {
         const float oa = axis == 0 ? ox : axis == 1 ? oy : oz;
@@ -168,18 +175,39 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
                         const bool fat = FUSED && (rest & ~__builtin_amdgcn_ballot_w64(mine.w >= fat_r2)) == 0ull;
                         const int cls = (c >> (GRANULE_SHIFT - 6)) & (SUM_CLASSES - 1);
                         const int n = __builtin_amdgcn_readlane(cnt, cls);
+                        const int bits = (lean ? 1 : 0) | (fat ? 2 : 0);
+                        // the class's open round takes this entry, or closes before it: (a) past 64
+                        // survivors with it, (b) other lean / fat bits
+                        const int n_surv = __builtin_popcountll(rest);
+                        const int open_n = __builtin_amdgcn_readlane(round_n, cls);
+                        const int open_bits = __builtin_amdgcn_readlane(round_bits, cls);
+                        const bool close_cap = n > 0 && open_n + n_surv > 64;
+                        const bool close_flag = n > 0 && !close_cap && open_bits != bits;
+                        const bool close = close_cap || close_flag;
                         if (pl.spans) {
                             const int2 span = pl.spans[packet * SUM_CLASSES + cls];
                             if (n < span.y) {
-                                if (lane == 0)
+                                if (lane == 0) {
+                                    // (the round's last entry: n - 1 < span.y held when it was written)
+                                    if (close) pl.entries[size_t(span.x) + n - 1].w = uint32_t(open_bits) | PLAN_ROUND_END;
                                     pl.entries[size_t(span.x) + n] =
-                                        make_uint4(uint32_t(c), uint32_t(rest), uint32_t(rest >> 32),
-                                                   (lean ? 1u : 0u) | (fat ? 2u : 0u));
+                                        make_uint4(uint32_t(c), uint32_t(rest), uint32_t(rest >> 32), uint32_t(bits));
+                                }
                             } else {
                                 failed = true;   // the list has outgrown its room
                             }
                         }
-                        cnt += lane == cls ? 1 : 0;
+                        if (lane == cls) {
+                            if (close) {
+                                t_rounds += 1; t_full += open_n == 64 ? 1 : 0;
+                                t_cap += close_cap ? 1 : 0; t_flag += close_flag ? 1 : 0;
+                                t_max = max(t_max, open_n);
+                                round_n = 0;
+                            }
+                            round_n += n_surv; round_bits = bits;
+                            t_surv += n_surv;
+                            cnt += 1;
+                        }
                     }
                 }
             }
@@ -190,6 +218,34 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
         if (lane == 0) { pl.ctl->unusable = 1u; pl.ctl->usable = 0u; }
     }
     if (lane < SUM_CLASSES) pl.counts[packet * SUM_CLASSES + lane] = cnt;
+    if (pl.spans && !failed) {
+        // (c) the end of a list closes its round; then the packet's tallies (the recording pass only:
+        // not a hot path, and the planned kernel never reads them)
+        for (int cls = 0; cls < SUM_CLASSES; ++cls) {
+            const int n = __builtin_amdgcn_readlane(cnt, cls);
+            const int open_bits = __builtin_amdgcn_readlane(round_bits, cls);
+            if (n > 0 && lane == 0)
+                pl.entries[size_t(pl.spans[packet * SUM_CLASSES + cls].x) + n - 1].w = uint32_t(open_bits) | PLAN_ROUND_END;
+        }
+        if (lane < SUM_CLASSES && cnt > 0) {
+            t_rounds += 1; t_full += round_n == 64 ? 1 : 0;
+            t_max = max(t_max, round_n);
+        }
+        if (lane >= SUM_CLASSES) cnt = 0;
+        int tally[6] = { cnt, t_surv, t_rounds, t_full, t_cap, t_flag };
+#pragma unroll
+        for (int off = 1; off < SUM_CLASSES; off <<= 1) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) tally[k] += __shfl_xor(tally[k], off);
+            t_max = max(t_max, __shfl_xor(t_max, off));
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (tally[k]) atomicAdd(&pl.ctl->stats[k], (unsigned long long)tally[k]);
+            atomicMax(&pl.ctl->largest_round, uint32_t(t_max));
+        }
+    }
 }
 
 grace_status launch_record(const bool fast, const TraceArgs& a, const PlanRef& pl, hipStream_t stream)

@@ -271,7 +271,10 @@ struct RayOrder {
 // the two things the caches above hold and validate.  Once both caches serve a call, the cull is
 // recorded: for every packet and summation class, the ordered list of its non-empty culling
 // rounds, 16 bytes each: {cluster, survivor mask lo, hi, flags (bit 0: lean round, bit 1: fat
-// round)}.  The planned kernel (trace_kernel<.., PLANNED>) walks the lists of its classes and runs
+// round, bit 2: last entry of a dense round)}.  Consecutive entries of a list form a dense round:
+// at most 64 survivors together, all with the same lean / fat bits; the recorder marks each
+// round's last entry, and the planned kernel runs one survivor loop per dense round.  The planned
+// kernel (trace_kernel<.., PLANNED>) walks the lists of its classes and runs
 // the survivor loops; it makes no group pass, cluster test or cull.  The lists are per class
 // because a class is summed in ascending primitive order and nothing depends on the order between
 // classes: one plan serves every packet split K.
@@ -285,11 +288,18 @@ struct PlanCtl {                  // device memory
     uint32_t record;              // this call re-records (set by the gate in choose_variants_kernel)
     uint32_t unusable;            // set by the record kernel
     uint32_t usable;              // its complement (a run_if for the kernels that follow)
-    uint32_t pad;
+    uint32_t largest_round;       // survivors of the largest dense round (tallied with stats)
     unsigned long long sig[4];    // the scene cache's and the ray cache's signatures it was recorded under
+    // Tallies of the last recording (grace_trace_plan_stats; never read by a trace): entries,
+    // survivors, dense rounds, rounds of exactly 64 survivors, rounds closed because the next entry
+    // would have passed 64, rounds closed because the next entry's lean / fat bits differed.
+    unsigned long long stats[6];
 };
+constexpr uint32_t PLAN_ROUND_END = 4u;   // entry flag: the last entry of its dense round
+constexpr int PLAN_FORMAT = 2;            // 1: one round per entry; 2: dense rounds
 
 struct PlanKey {
+    int format = PLAN_FORMAT;     // what the entries mean: a plan of another format is never consumed
     bool fast = false;            // axis_beam_may_hit<AX, FUSED> bounds the b^2 the survivors compute
     int group_shift = 0, width = 0;
     bool reorder = false;
@@ -297,7 +307,7 @@ struct PlanKey {
     unsigned long long scene_gen = 0, rays_gen = 0;
     bool operator==(const PlanKey& o) const
     {
-        return fast == o.fast && group_shift == o.group_shift && width == o.width && reorder == o.reorder
+        return format == o.format && fast == o.fast && group_shift == o.group_shift && width == o.width && reorder == o.reorder
             && n_rays == o.n_rays && n_prims == o.n_prims && scene_gen == o.scene_gen && rays_gen == o.rays_gen;
     }
 };

@@ -6,6 +6,7 @@ tests/helper/rays.cuh); torch tensors play the role of thrust::device_vector (de
 memory + streams only -- every computation is a hand-written HIP kernel behind the C ABI).
 There is NO CPU fallback: importing this module without the built library raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -420,6 +421,19 @@ def last_plan_used():
     v = C.c_int(0)
     _check(_lib.grace_trace_last_plan_used(C.byref(v)))
     return v.value
+
+
+PlanStats = collections.namedtuple(
+    "PlanStats", "entries survivors rounds full_rounds closed_by_capacity closed_by_flags largest_round")
+
+
+def plan_stats():
+    """Tallies of the plan the last column-density trace ran from (zeros: it ran from none): its
+    entries, survivors and dense rounds, the rounds of exactly 64 survivors, the rounds closed by
+    the 64-survivor capacity and by a change of the lean / fat bits, and the largest round."""
+    v = (C.c_ulonglong * 7)()
+    _check(_lib.grace_trace_plan_stats(v))
+    return PlanStats(*[int(x) for x in v])
 
 
 def set_lattice_split(k):

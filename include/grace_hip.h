@@ -627,11 +627,19 @@ grace_status grace_trace_set_cache_auto(int enabled);
  * grace_trace_plan_bytes: the device memory of the current plan (0: none).
  * grace_trace_last_plan_used (measurement hook, in the manner of grace_trace_last_lattice): 1 if
  * the last column-density trace ran the planned kernel, else 0.  Synchronises.
+ * grace_trace_plan_stats (diagnostic): seven figures of the plan the last column-density trace ran
+ * from, as its last recording tallied them (zeros if it ran from none): h_stats[0] entries,
+ * [1] survivors, [2] dense rounds (runs of consecutive entries of a list that the planned kernel
+ * works off in one survivor loop: at most 64 survivors, one lean / fat class), [3] rounds of exactly
+ * 64 survivors, [4] rounds closed because the next entry would have taken them past 64, [5] rounds
+ * closed because the next entry's lean / fat bits differed, [6] the largest round's survivors.
+ * Synchronises; a steady-state call pays nothing for it.
  * Not part of the reference API. */
 grace_status grace_trace_set_plan(int on);
 grace_status grace_trace_set_plan_budget(size_t bytes);
 grace_status grace_trace_plan_bytes(size_t* h_bytes);
 grace_status grace_trace_last_plan_used(int* h_used);
+grace_status grace_trace_plan_stats(unsigned long long* h_stats /* [7] */);
 
 /* Reads (and clears) the traversal status word: GRACE_STACK_OVERFLOW if any packet ran out
  * of its 128-entry stack since the last check (the reference only asserts this in
