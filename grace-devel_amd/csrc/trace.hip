@@ -257,6 +257,7 @@ struct TraceBuffers {   // a call's buffers in its workspace frame (null: not ne
     int4* wave_map = nullptr; int *n_wave_map = nullptr, *pk_first = nullptr, *pk_parts = nullptr;
     uint32_t *pk_prefix = nullptr, *pk_total = nullptr;
     // ray order; ext: 12 extents + [12] the device-side split + [13] the lattice flag (per call)
+    // + [14], [15] the grid flag and the longest ray + [16] the planned kernel's split (per call)
     uint32_t* ext = nullptr; uint32_t* keys = nullptr; uint32_t* perm = nullptr;
     // Packet plan (set by use_records): this call may use one -- both caches serve it --, under this key
     bool plan_eligible = false;
@@ -341,7 +342,7 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
             take(b.pk_prefix, p.hit_packets * size_t(p.hit_chunks));
             take(b.pk_total, p.hit_packets + 16); take(b.pk_first, p.hit_packets + 16); take(b.pk_parts, p.hit_packets + 16);
         }
-        if (p.reorder) { take(b.ext, 16); take(b.keys, n_rays); take(b.perm, n_rays); }
+        if (p.reorder) { take(b.ext, 20); take(b.keys, n_rays); take(b.perm, n_rays); }
         return used;
     };
     const size_t own = carve(nullptr);
@@ -398,10 +399,17 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
                 ro.valid = true;
             }
             // cached order: only this call's device-side choices remain
+            // (an unweighted call that may run from a plan, where the device chooses the split at all,
+            // also gets the planned kernel's own: see planned_split.  Weighted calls keep one K: their
+            // planned kernels run 3 to 8 waves per SIMD on LDS accumulators, and with four channels
+            // the extra waves cost 6-13 % instead of saving time -- measured, see planned_split)
+            int* plan_split_dev = b.plan_eligible && split_dev && !weighted(MODE)
+                ? reinterpret_cast<int*>(b.ext + 16) : nullptr;
             if (lat_flag || split_dev || plan_steady)
                 GRACE_TRY(launch_choose_variants(ro.ext, int(n_rays), scene_min, lat_flag, p.n_packets,
-                                                 p.split | split_flags, split_dev, stream, plan_steady ? &gate : nullptr));
-            a.perm = ro.perm;
+                                                 p.split | split_flags, split_dev, stream, plan_steady ? &gate : nullptr,
+                                                 plan_split_dev));
+            a.perm = ro.perm; a.plan_split_dev = plan_split_dev;
         } else {
             GRACE_TRY(ray_order(a.rays, n_rays, b.ext, b.keys, b.perm, scene_min, lat_flag, p.n_packets,
                                 p.split | split_flags, split_dev, stream));
@@ -430,15 +438,19 @@ grace_status dispatch(const TraceState& ts, const TraceArgs& a, const TraceBuffe
     const int grid = ceil_div(size_t(p.n_packets) * p.split, TRACE_BLOCK / 64);
     // Upper levels of the class sum tree: k partial sums per ray (k_dev: the device's k, if set;
     // run_if: the kernel returns at once if *run_if == 0).  Counts are summed by atomics.
+    // (a planned kernel with a split of its own: the pass takes that K if the plan's flag says it ran)
+    const int* const plan_k_dev = a.plan_usable ? a.plan_split_dev : nullptr;
     auto combine = [&](const int k, const int* k_dev, const int* run_if) -> grace_status {
         const int g = ceil_div(n_rays * channels(MODE), 256);   // (one thread per ray and channel)
         if constexpr (double_sums(MODE))
             combine_classes_kernel<double><<<g, 256, 0, stream>>>(a.partial_d, int(n_rays), k, k_dev, a.out_sums_d, run_if);
         else if constexpr (weighted(MODE))
             combine_channel_classes_kernel<<<g, 256, 0, stream>>>(a.partial, int(n_rays), channels(MODE), k, k_dev,
-                                                                  a.out_sums, a.out_stride, run_if);
+                                                                  a.out_sums, a.out_stride, run_if,
+                                                                  a.plan_usable, plan_k_dev);
         else if constexpr (f4_sums(MODE))
-            combine_classes_kernel<float><<<g, 256, 0, stream>>>(a.partial, int(n_rays), k, k_dev, a.out_sums, run_if);
+            combine_classes_kernel<float><<<g, 256, 0, stream>>>(a.partial, int(n_rays), k, k_dev, a.out_sums, run_if,
+                                                                 a.plan_usable, plan_k_dev);
         else return GRACE_OK;
         GRACE_CHECK_LAUNCH();
         return GRACE_OK;
@@ -463,7 +475,13 @@ grace_status dispatch(const TraceState& ts, const TraceArgs& a, const TraceBuffe
                 // class-split one: with one wave per packet it leaves one partial sum per ray), then
                 // the ordinary kernels; the plan's device flag lets one side run.
                 GRACE_TRY(plan_record(ts, a, stream));
-                GRACE_TRY(launch_planned(MODE, ALT, grid, a, stream));
+                // (its own grid where it has its own waves per packet.  The kernel takes its K from the
+                // word choose_variants_kernel wrote, planned_split(p.n_packets) as well: the grid covers
+                // every working wave only because host and device call the same function with the same
+                // packet count -- a rule that looks at anything else must size this grid for its largest K)
+                const int grid_planned = a.plan_split_dev
+                    ? ceil_div(size_t(p.n_packets) * planned_split(p.n_packets), TRACE_BLOCK / 64) : grid;
+                GRACE_TRY(launch_planned(MODE, ALT, grid_planned, a, stream));
                 if (p.split == 1) GRACE_TRY(combine(1, nullptr, reinterpret_cast<const int*>(a.plan_usable)));
             }
             if (p.split > 1) launch_walk<MODE, true, ALT>(grid, a, stream);

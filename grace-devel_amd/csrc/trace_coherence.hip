@@ -223,10 +223,13 @@ __device__ void choose_variants(const uint32_t* __restrict__ ext12, int n, const
 // The same choices for a call whose ray order is cached (grace_trace_prepare_rays).
 __global__ void choose_variants_kernel(const uint32_t* __restrict__ ext12, int n, const float4* __restrict__ scene_min,
                                        uint32_t* __restrict__ lat_flag, int split_packets, int split_launched,
-                                       int* __restrict__ split_dev, const PlanGate gate)
+                                       int* __restrict__ split_dev, const PlanGate gate,
+                                       int* __restrict__ plan_split_dev)
 {
     if (lat_flag || split_dev)
         choose_variants(ext12, n, scene_min, lat_flag, split_packets, split_launched, split_dev);
+    // (the planned kernel's own waves per packet: read by it and by the combine pass if it runs)
+    if (plan_split_dev) *plan_split_dev = planned_split(split_packets);
     // The packet plan of this call: recorded from the scene records and the ray order, so it is
     // re-recorded when either cache's signature is no longer the one it was recorded under (the
     // gated pre-pass / ray order have re-derived them, in this call or an earlier one).
@@ -344,10 +347,10 @@ namespace grace_hip {
 
 grace_status launch_choose_variants(const uint32_t* ext12, int n, const float4* scene_min, uint32_t* lat_flag,
                                     int split_packets, int split_launched, int* split_dev, hipStream_t stream,
-                                    const PlanGate* gate)
+                                    const PlanGate* gate, int* plan_split_dev)
 {
     choose_variants_kernel<<<1, 1, 0, stream>>>(ext12, n, scene_min, lat_flag, split_packets, split_launched,
-                                                split_dev, gate ? *gate : PlanGate());
+                                                split_dev, gate ? *gate : PlanGate(), plan_split_dev);
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
 }

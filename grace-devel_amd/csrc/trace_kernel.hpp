@@ -419,7 +419,13 @@ void trace_kernel(const TraceArgs a)
     // Waves per packet: as launched, or fewer when the device-side choice (choose_split)
     // says so.  The working waves are packed into the first workgroups -- surplus workgroups exit
     // whole, before touching LDS, so that they do not hold resources of the working ones.
-    const int split = !SPLIT ? 1 : (!RANGE_SPLIT && a.split_dev) ? *a.split_dev : a.split;
+    // (PLANNED: its own choice, planned_split, where the call has one -- written by an earlier launch,
+    // read like the plan itself)
+    const int split_ordinary = !SPLIT ? 1 : (!RANGE_SPLIT && a.split_dev) ? *a.split_dev : a.split;
+    int split_planned = 0;
+    if constexpr (PLANNED)
+        if (a.plan_split_dev) split_planned = *plan_const<int>(a.plan_split_dev);
+    const int split = PLANNED && split_planned > 0 ? split_planned : split_ordinary;
     const int n_packets = (a.n_rays + a.width - 1) / a.width;
     const int nb = (n_packets * split + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64);   // working workgroups
     // Workgroups b and b + 8 share an XCD (round-robin dispatch; speed only, never

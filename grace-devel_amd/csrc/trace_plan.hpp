@@ -9,17 +9,23 @@ namespace {
 using namespace grace_hip;
 
 // Upper levels of the pairwise summation tree for split packets: K subtree sums per ray.
+// K: `split`, or the device's choice for the kernel that ran -- *plan_split_dev if the planned
+// kernel did (*plan_usable != 0; both null: no plan, or one without a split of its own), else
+// *split_dev.
 template <typename Real>
 __global__ __launch_bounds__(256) void combine_classes_kernel(const Real* __restrict__ partial,
                                                               int n_rays, int split,
                                                               const int* __restrict__ split_dev,
                                                               Real* __restrict__ out,
-                                                              const int* __restrict__ run_if = nullptr)
+                                                              const int* __restrict__ run_if = nullptr,
+                                                              const uint32_t* __restrict__ plan_usable = nullptr,
+                                                              const int* __restrict__ plan_split_dev = nullptr)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
     if (run_if && *run_if == 0) return;   // the one-wave-per-packet kernel ran: `out` is final
     if (split_dev) split = *split_dev;
+    if (plan_split_dev && *plan_usable != 0u) split = *plan_split_dev;
     Real t[SUM_CLASSES];
     for (int k = 0; k < split; ++k) t[k] = partial[size_t(r) * split + k];
     for (int w = 1; w < split; w *= 2)
@@ -33,12 +39,15 @@ __global__ __launch_bounds__(256) void combine_channel_classes_kernel(const floa
                                                                       int n_rays, int n_ch, int split,
                                                                       const int* __restrict__ split_dev,
                                                                       float* __restrict__ out, int out_stride,
-                                                                      const int* __restrict__ run_if = nullptr)
+                                                                      const int* __restrict__ run_if = nullptr,
+                                                                      const uint32_t* __restrict__ plan_usable = nullptr,
+                                                                      const int* __restrict__ plan_split_dev = nullptr)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rays * n_ch) return;
     if (run_if && *run_if == 0) return;
     if (split_dev) split = *split_dev;
+    if (plan_split_dev && *plan_usable != 0u) split = *plan_split_dev;
     const int r = i / n_ch, c = i - r * n_ch;
     float t[SUM_CLASSES];
     for (int k = 0; k < split; ++k) t[k] = partial[size_t(i) * split + k];

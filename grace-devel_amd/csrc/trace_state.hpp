@@ -203,6 +203,10 @@ struct TraceArgs {
     const int2* plan_spans;
     const int* plan_counts;
     const uint32_t* plan_usable;
+    // The planned kernel's own waves per packet (planned_split; the word next to *split_dev in the
+    // call's frame; null: it takes split_dev / split like the ordinary kernels).  The combine pass
+    // reads the one whose kernel ran.
+    const int* plan_split_dev;
 };
 
 
@@ -330,6 +334,21 @@ struct PlanGate {
     const CacheCtl* rays = nullptr;
     PlanCtl* ctl = nullptr;
 };
+
+// Waves per packet of the planned kernel, a function of the packet count alone.  Its extra waves
+// repeat nothing -- no walk, no cluster test, no cull: each takes its classes' lists -- so the
+// ordinary kernels' rule (choose_split: as few waves as fill the chip) does not apply; what an
+// extra wave costs is its prologue (the rays, the table) and a partial sum per ray.  Thresholds
+// from the sweep over the 1024^2 frame's shards (profiles/trace_quad_reads_mi355x.txt, section 3):
+// of the unweighted kernel with the fast integral; the exact integral's sweep agrees (K = 8 is
+// best or tied at every size).  The weighted planned kernels do NOT take it (use_records, trace.hip):
+// with four channels K = 2 or 4 is best and this rule would cost them 6-13 %; one to three
+// channels were not swept.  They keep the ordinary kernels' K.
+// The host sizes the planned launch with it, the device writes it to TraceArgs::plan_split_dev.
+__host__ __device__ inline int planned_split(const int n_packets)
+{
+    return n_packets <= 8192 ? SUM_CLASSES : SUM_CLASSES / 2;
+}
 
 // trace_sph walks twice -- hit counts (for the offsets), then the per-hit pass -- and the split
 // per-hit pass of small batches needs hits per (ray, chunk), a third walk.  The hit-count call
@@ -459,9 +478,10 @@ grace_status ray_order(const float* d_rays, size_t n_rays, uint32_t* ext, uint32
 grace_status rays_prepare(TraceState& ts, const float* d_rays, size_t n_rays, hipStream_t stream);
 // The device-side choices of a trace launch for a batch whose order is cached.
 // gate (optional): also decides whether this call re-records its packet plan.
+// plan_split_dev (optional): receives the planned kernel's waves per packet (planned_split).
 grace_status launch_choose_variants(const uint32_t* ext12, int n, const float4* scene_min, uint32_t* lat_flag,
                                     int split_packets, int split_launched, int* split_dev, hipStream_t stream,
-                                    const PlanGate* gate = nullptr);
+                                    const PlanGate* gate = nullptr, int* plan_split_dev = nullptr);
 
 // trace_planned.hip: the packet plan, its record kernel and the planned class-sum kernels.
 grace_status plan_release(TraceState& ts);

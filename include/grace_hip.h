@@ -510,8 +510,10 @@ grace_status grace_trace_last_lattice(int* h_lattice);
 /* Waves per 64-ray packet for the hit-count and cumulative traces: 1, 2, 4 or 8 (each wave
  * owns 8/K of the 8 interleaved primitive classes over which the column density is summed), or
  * -1 (default) = as many as it takes to put >= 16384 waves on the chip (>= 4096 if all rays of
- * the batch share one direction: decided on the device from the ray extents).  The results do not
- * depend on it (see csrc/trace.hip, "class-ordered sums and packet splitting"). */
+ * the batch share one direction: decided on the device from the ray extents; an unweighted
+ * column-density call that runs from a packet plan takes 8 up to 8192 packets and 4 up to 16384,
+ * whatever the directions: its waves repeat nothing).  An explicit value holds for every kernel of the call.
+ * The results do not depend on it (see csrc/trace.hip, "class-ordered sums and packet splitting"). */
 grace_status grace_trace_set_packet_split(int waves_per_packet);
 
 /* Rays per packet of the per-hit and triangle traces (which cannot split a packet among waves):
