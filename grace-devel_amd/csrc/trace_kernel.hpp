@@ -1,9 +1,11 @@
 // The traversal kernel of libgrace_hip.so (see trace.hip for the design notes): device helpers,
 // beam / pencil / cluster culls, and trace_kernel<MODE, SPLIT, ALT, LAT, PLANNED>.  Included by trace.hip
-// and, for the PLANNED instantiations and the plan's record kernel, by trace_planned.hip.
+// and, for the PLANNED instantiations and the plan's record kernel, by trace_planned.hip.  The
+// packet set-up that the record kernel shares is in trace_packet.hpp.
 #pragma once
 
 #include "trace_diag.hpp"
+#include "trace_packet.hpp"
 #include "trace_state.hpp"
 
 #include <type_traits>
@@ -165,25 +167,6 @@ __global__ __launch_bounds__(256) void hit_integrals_kernel(const float* __restr
         const float ir = 1.f / h[i];
         out[i] = hit_integral(b2[i], ir, ir * ir, s_lut);
     }
-}
-
-// Bounding boxes of the packet's origins and directions (wave-uniform, SGPRs).
-struct Beam {
-    float olo[3], ohi[3], dlo[3], dhi[3];
-};
-
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
 // Conservative: returns false only if sphere_hit (generic/intersect.h:10-55) is false for
@@ -480,41 +463,17 @@ void trace_kernel(const TraceArgs a)
         const int g0 = first >> GRANULE_SHIFT, g1 = (first + count - 1) >> GRANULE_SHIFT;
         return g1 - g0 <= 1 && !owns_granule(g0) && !owns_granule(g1);
     };
-    const int slot_index = first_ray + lane;
-    const bool valid = lane < a.width && slot_index < a.n_rays;
-    // Idle and tail lanes re-trace the packet's last ray so that they do not widen the packet.
-    const int slot_clamped = valid ? slot_index : min(first_ray + a.width, a.n_rays) - 1;
-    const int ray_index = a.perm ? int(a.perm[slot_clamped]) : slot_clamped;
-    const float* rp = a.rays + 7 * size_t(ray_index);
-    const float dx = rp[0], dy = rp[1], dz = rp[2];
-    const float ox = rp[3], oy = rp[4], oz = rp[5];
-    const float len = rp[6];
+    // The packet's set-up (trace_packet.hpp): its rays, their beam, its axis.
+    const PacketRay ray = load_packet_ray(a, first_ray, lane);
+    const bool valid = ray.valid;
+    const int ray_index = ray.index;
+    const float dx = ray.dx, dy = ray.dy, dz = ray.dz;
+    const float ox = ray.ox, oy = ray.oy, oz = ray.oz;
+    const float len = ray.len;
     const float ix = 1.f / dx, iy = 1.f / dy, iz = 1.f / dz; // bintree_trace.cuh:111-114
-
-    Beam beam;
-    beam.olo[0] = wave_min(ox); beam.ohi[0] = wave_max(ox);
-    beam.olo[1] = wave_min(oy); beam.ohi[1] = wave_max(oy);
-    beam.olo[2] = wave_min(oz); beam.ohi[2] = wave_max(oz);
-    beam.dlo[0] = wave_min(dx); beam.dhi[0] = wave_max(dx);
-    beam.dlo[1] = wave_min(dy); beam.dhi[1] = wave_max(dy);
-    beam.dlo[2] = wave_min(dz); beam.dhi[2] = wave_max(dz);
-
-    // Axis-aligned packet?  (wave-uniform; tail lanes replicate a valid ray)
+    const Beam beam = packet_beam(ray);
     int axis = -1;
-    if (!ordered(MODE)) {
-        const unsigned long long all = ~0ull;
-        const bool zx = dx == 0.f, zy = dy == 0.f, zz = dz == 0.f;
-        if (__builtin_amdgcn_ballot_w64(zy && zz && fabsf(dx) == 1.f) == all) axis = 0;
-        else if (__builtin_amdgcn_ballot_w64(zx && zz && fabsf(dy) == 1.f) == all) axis = 1;
-        else if (__builtin_amdgcn_ballot_w64(zx && zy && fabsf(dz) == 1.f) == all) axis = 2;
-    }
-    // Permuted per-lane constants for the axis path: along-axis origin/direction, then the
-    // two perpendicular origins in component order.
-    const float oa = axis == 0 ? ox : axis == 1 ? oy : oz;
-    const float da = axis == 0 ? dx : axis == 1 ? dy : dz;
-    // (s_a - o_a) * d_a with d_a = +-1 is the correctly rounded +-(s_a - o_a): one FMA
-    // s_a * d_a + (-o_a * d_a) gives the same bits (both products are exact).
-    const float noda = -(oa * da);
+    if (!ordered(MODE)) axis = packet_axis(dx, dy, dz);
     // Pencil packets: one origin, directions inside a cone narrower than 60 degrees.
     // The 20 constants live in LDS (one record per wave) and are re-read by every culling round
     // of a pencil sweep: held in registers they would be live across the whole walk and cost
@@ -571,39 +530,17 @@ void trace_kernel(const TraceArgs a)
             if (lane == 0) s_pencil[threadIdx.x >> 6] = pencil;
         }
     }
-    // For the range-check-free sweep (below): the packet's extremes of -o_a d_a and of the ray
-    // length, and whether all rays point the same way along the axis.
+    // The axis path's per-lane constants (o1, o2: the two perpendicular origins) and, for the
+    // range-check-free sweep below, the packet's wave-uniform extremes.
+    const AxisRay ar = axis_ray(axis, ray);
+    const float oa = ar.oa, da = ar.da, noda = ar.noda, o1 = ar.o1, o2 = ar.o2;
     float noda_lo = 0.f, noda_hi = 0.f, len_lo = 0.f, da0 = 0.f;
     bool same_sense = false;
-    if (axis >= 0) {
-        noda_lo = wave_min(noda); noda_hi = wave_max(noda); len_lo = wave_min(len);
-        const unsigned long long fwd = __builtin_amdgcn_ballot_w64(da > 0.f);
-        same_sense = fwd == 0ull || fwd == ~0ull;
-        da0 = fwd ? 1.f : -1.f;
-    }
-    const float o1 = axis == 0 ? oy : ox;
-    const float o2 = axis == 2 ? oy : oz;
-    // Axis-aligned packets, fast integral: a sphere hit by SOME ray of the packet lies within
-    // h + D of every other ray (D = diagonal of the origins' box), i.e. at a table position below
-    // 50 (1 + D / h).  For h >= D / 3 that stays below 200 < LUTF_N: such survivors need no clamp.
-    float fat_r2 = INFINITY;
-    if (FAST && axis >= 0) {
-        const float ex = beam.ohi[0] - beam.olo[0], ey = beam.ohi[1] - beam.olo[1], ez = beam.ohi[2] - beam.olo[2];
-        const float e1 = axis == 0 ? ey : ex, e2 = axis == 2 ? ey : ez;
-        fat_r2 = (e1 * e1 + e2 * e2) * (1.0f / 9.0f) * 1.0001f;
-    }
+    if (axis >= 0) axis_extremes(ar, len, noda_lo, noda_hi, len_lo, da0, same_sense);
+    // (fat_radius2: survivors at least that wide need no clamp of the table position)
+    const float fat_r2 = FAST && axis >= 0 ? fat_radius2(axis, beam) : INFINITY;
     const int treelet = axis >= 0 ? a.treelet_axis : a.treelet;
-    // Origin lattice of an axis-aligned packet.  The beam cull bounds b^2 at the point of the
-    // origin RECTANGLE nearest to the sphere; a sphere smaller than the ray spacing can lie
-    // inside the rectangle and still between the rays -- in the dense cores of clustered SPH
-    // data most do (h << pixel), and every one of them used to cost all 64 lanes a test (10^7
-    // particles, 90 % of them in 50 clumps: 180 863 surviving candidates in the heaviest packet
-    // against 2273 in the median one, whose wave outlived the launch 30x).  If the packet's
-    // origins take at most 8 distinct values in each perpendicular co-ordinate (pixel grids do:
-    // 8 x 8 tiles), the tables of those values give the exact minimum of the rays' own b^2
-    // expression over the lattice {x_i} x {y_j} -- a superset of the rays --: |s - x| rounds
-    // monotonically in the true difference, so the nearest table value minimises the rounded |q|
-    // in each co-ordinate, and b^2 is monotone in both.  No margin, same bits as the ray's test.
+    // Origin lattice of an axis-aligned packet (build_origin_lattice, trace_packet.hpp).
     constexpr bool LATTICE = LAT;
     __shared__ float s_lat[LATTICE ? TRACE_BLOCK / 64 : 1][2][8];
     // Spheres with r^2 below this can fall between the rays; 0 = no lattice.  Kept in LDS and
@@ -612,33 +549,9 @@ void trace_kernel(const TraceArgs a)
     __shared__ float s_lat_r2[LATTICE ? TRACE_BLOCK / 64 : 1];
     if (LATTICE && lane == 0) s_lat_r2[threadIdx.x >> 6] = 0.f;
     if (LATTICE && axis >= 0) {
-        // The distinct values of each co-ordinate, in any order (the nearest one is found by a
-        // plain minimum): take the first lane not yet accounted for, strike every lane that
-        // holds its value, eight times at most.  NaN origins strike nobody: no lattice.
-        bool ok = true;
-        float cell2 = 0.f;
-#pragma unroll
-        for (int dim = 0; dim < 2; ++dim) {
-            const float o = dim ? o2 : o1;
-            unsigned long long todo = ~0ull;
-            int n_val = 0;
-            float v = 0.f, v_lo = INFINITY, v_hi = -INFINITY;
-#pragma unroll 1
-            for (int k = 0; k < 8 && todo != 0ull; ++k) {
-                v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, o),
-                                                                        __builtin_ctzll(todo)));
-                v_lo = fminf(v_lo, v); v_hi = fmaxf(v_hi, v);
-                todo &= ~__builtin_amdgcn_ballot_w64(o == v);
-                if (lane == 0) s_lat[threadIdx.x >> 6][dim][k] = v;
-                ++n_val;
-            }
-            ok = ok && todo == 0ull;
-            if (lane == 0)
-                for (int k = n_val; k < 8; ++k) s_lat[threadIdx.x >> 6][dim][k] = v;   // padding repeats
-            // mean spacing (a gate only: it decides which spheres are worth the lattice test)
-            const float gap = n_val > 1 ? (v_hi - v_lo) / float(n_val - 1) : 0.f;
-            cell2 += gap * gap;
-        }
+        bool ok;
+        float cell2;
+        build_origin_lattice(o1, o2, lane, s_lat, ok, cell2);
         // spheres wider than the cell diagonal meet a ray wherever they lie inside the lattice
         if (lane == 0) s_lat_r2[threadIdx.x >> 6] = ok ? cell2 : 0.f;
     }

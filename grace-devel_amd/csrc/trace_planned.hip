@@ -39,24 +39,9 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
     const int n_packets = (a.n_rays + a.width - 1) / a.width;
     const int packet = blockIdx.x * (TRACE_BLOCK / 64) + wv;
     if (packet >= n_packets) return;
-    // the packet's rays, as trace_kernel loads them
-    const int first_ray = packet * a.width;
-    const int slot_index = first_ray + lane;
-    const bool valid = lane < a.width && slot_index < a.n_rays;
-    const int slot_clamped = valid ? slot_index : min(first_ray + a.width, a.n_rays) - 1;
-    const int ray_index = a.perm ? int(a.perm[slot_clamped]) : slot_clamped;
-    const float* rp = a.rays + 7 * size_t(ray_index);
-    const float dx = rp[0], dy = rp[1], dz = rp[2];
-    const float ox = rp[3], oy = rp[4], oz = rp[5];
-    const float len = rp[6];
-    int axis = -1;
-    {
-        const unsigned long long all = ~0ull;
-        const bool zx = dx == 0.f, zy = dy == 0.f, zz = dz == 0.f;
-        if (__builtin_amdgcn_ballot_w64(zy && zz && fabsf(dx) == 1.f) == all) axis = 0;
-        else if (__builtin_amdgcn_ballot_w64(zx && zz && fabsf(dy) == 1.f) == all) axis = 1;
-        else if (__builtin_amdgcn_ballot_w64(zx && zy && fabsf(dz) == 1.f) == all) axis = 2;
-    }
+    // the packet's set-up, with trace_kernel's own pieces (trace_packet.hpp)
+    const PacketRay ray = load_packet_ray(a, packet * a.width, lane);
+    const int axis = packet_axis(ray.dx, ray.dy, ray.dz);
     const float4* const group_boxes = a.C + 2 * ((size_t(a.n_prims) + 63) >> 6) + 1;
     const int covered = min(__float_as_int(group_boxes[-1].y), a.n_prims);
     int cnt = 0;     // lane c < SUM_CLASSES: entries of class c so far
@@ -67,45 +52,18 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
     int t_surv = 0, t_rounds = 0, t_full = 0, t_cap = 0, t_flag = 0, t_max = 0;
     bool failed = axis < 0 || covered < 0;   // not an axis-aligned flat packet: no plan for this batch
     if (!failed) {
-        const float oa = axis == 0 ? ox : axis == 1 ? oy : oz;
-        const float da = axis == 0 ? dx : axis == 1 ? dy : dz;
-        const float o1 = axis == 0 ? oy : ox;
-        const float o2 = axis == 2 ? oy : oz;
-        const float noda = -(oa * da);
-        const float lo1 = wave_min(o1), hi1 = wave_max(o1), lo2 = wave_min(o2), hi2 = wave_max(o2);
-        const float noda_lo = wave_min(noda), noda_hi = wave_max(noda), len_lo = wave_min(len);
-        const unsigned long long fwd = __builtin_amdgcn_ballot_w64(da > 0.f);
-        const bool same_sense = fwd == 0ull || fwd == ~0ull;
-        const float da0 = fwd ? 1.f : -1.f;
-        const float ea = oa + da * len;
-        const float alo = wave_min(fminf(oa, ea)), ahi = wave_max(fmaxf(oa, ea));
-        // (trace_kernel's fat_r2: survivors at least this wide need no clamp of the table position)
-        const float e1 = hi1 - lo1, e2 = hi2 - lo2;
-        const float fat_r2 = (e1 * e1 + e2 * e2) * (1.0f / 9.0f) * 1.0001f;
-        // origin lattice (trace_kernel's LAT set-up): the distinct values of each perpendicular origin
-        bool lat_ok = true;
-        float cell2 = 0.f;
-#pragma unroll
-        for (int dim = 0; dim < 2; ++dim) {
-            const float o = dim ? o2 : o1;
-            unsigned long long todo = ~0ull;
-            int n_val = 0;
-            float v = 0.f, v_lo = INFINITY, v_hi = -INFINITY;
-#pragma unroll 1
-            for (int k = 0; k < 8 && todo != 0ull; ++k) {
-                v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, o),
-                                                                        __builtin_ctzll(todo)));
-                v_lo = fminf(v_lo, v); v_hi = fmaxf(v_hi, v);
-                todo &= ~__builtin_amdgcn_ballot_w64(o == v);
-                if (lane == 0) s_lat[wv][dim][k] = v;
-                ++n_val;
-            }
-            lat_ok = lat_ok && todo == 0ull;
-            if (lane == 0)
-                for (int k = n_val; k < 8; ++k) s_lat[wv][dim][k] = v;
-            const float gap = n_val > 1 ? (v_hi - v_lo) / float(n_val - 1) : 0.f;
-            cell2 += gap * gap;
-        }
+        const AxisRay ar = axis_ray(axis, ray);
+        float noda_lo, noda_hi, len_lo, da0;
+        bool same_sense;
+        axis_extremes(ar, ray.len, noda_lo, noda_hi, len_lo, da0, same_sense);
+        // the origin rectangle, and the packet's extent along the axis
+        const float lo1 = wave_min(ar.o1), hi1 = wave_max(ar.o1), lo2 = wave_min(ar.o2), hi2 = wave_max(ar.o2);
+        const float ea = ar.oa + ar.da * ray.len;
+        const float alo = wave_min(fminf(ar.oa, ea)), ahi = wave_max(fmaxf(ar.oa, ea));
+        const float fat_r2 = fat_radius2(hi1 - lo1, hi2 - lo2);
+        bool lat_ok;
+        float cell2;
+        build_origin_lattice(ar.o1, ar.o2, lane, s_lat, lat_ok, cell2);
         const float lat_r2 = lat_ok ? cell2 : 0.f;
 
         // a box against the packet's origin rectangle (and, for groups, its extent along the axis)
