@@ -27,6 +27,32 @@
 // Containment d2 < fl(H^2) with d2 formed in fp32 is never true for a point outside the exact box
 // [x - H, x + H] of a sphere (|dx| >= H there, and every fp32 step is monotonic), so the widened
 // box tests drop no contained sphere: results are a function of the point and the scene only.
+//
+// Periodic boxes (interpolate_kernel over Periodic<InterpArgs>, grace_interpolate_points_periodic_f4 /
+// grace_interpolate_grid_periodic_f4; packet_walk.hpp's WalkPeriod: per axis the period L and
+// h = fl(0.5 L), an open axis L = 0 and h = +inf).  The separation is range_walk.hpp's: per component
+// d0 = fl(p - x); d0 > h: dw = fl(d0 - L); else d0 < -h: dw = fl(d0 + L); else dw = d0.  A sphere with
+// H > h on a periodic axis is off (more than one of its images could contain a point); every other
+// sphere is tested once per point, with the wrapped d2.
+//   The cull, wrapped.  Let d2 < fl(H H) for an on sphere.  fp32 squaring and the sums are monotonic,
+// so |dw| < H on every axis.  Not wrapped: dw = fl(p - x), so the exact |p - x| < H (H is a float)
+// and p is inside [x - H, x + H], as in the open walk.  d0 > h: beyond 2 L, fl(d0 - L) >= L >= 2 H,
+// impossible; up to 2 L the subtraction is exact (Sterbenz), so d0 is in (L - H, L + H), below 1.5 L,
+// and the exact p - x is within 1.5 L 2^-24 (1 + 2^-23) < 2^-23 L of d0: the exact box [x - H, x + H]
+// meets [p - L - 2^-23 L, p - L + 2^-23 L].  d0 < -h mirrors this about p + L.  That slack is absolute
+// in L and may exceed a small H, so the packet's box is that of its points moved out by
+// e = L 2^-22 (exact) and then, like a query box, by 2^-20 of each bound, which covers the rounding
+// of plo - e, phi + e; its images at -L and +L are rounded outward once more (axis_images).  A
+// candidate's box fl(x -+ H) and the node boxes, which hold them, are moved out by 2^-20 of their
+// bounds as in the open walk and must meet, per axis, the box or one of its two images.  So no
+// sphere with wrapped d2 < fl(H H) is culled; what passes through an image it does not belong to
+// fails the containment test.
+//   Two wave-uniform fast paths.  A packet whose shifted boxes miss the root's box (moved out like
+// every node box, so it holds every candidate's box) tests against the box itself.  And per axis
+// the centres x with bhi - h <= x <= blo + h (both bounds moved inward by 2^-20, far more than their
+// rounding) have |p - x| <= h exactly for every p in [blo, bhi], hence |fl(p - x)| <= h and no wrap:
+// a cluster whose survivors all lie there on every axis runs the open loop, with the same bits.
+// Bricks and Morton cells are narrow against h, so this is the common case.
 #include "packet_walk.hpp"
 #include "sph_kernel_f.hpp"
 
@@ -51,10 +77,41 @@ struct InterpArgs : PacketPoints, PacketScene {
     unsigned long long* tests;   // measurement hook: survivor tests (lanes x survivors), or null
 };
 
-// NW = channels of this walk (0: counts only).
-template <int KIND, int NW>
-__global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs a)
+// The packet's point box on one axis of a periodic box, moved out by L 2^-22 and by 2^-20 of its bounds,
+// with its images at -L and +L (wave-uniform).
+__device__ __forceinline__ AxisImages point_images(const float plo, const float phi, const float L)
 {
+    float lo, hi, unused;
+    query_bounds(plo, L * 0.25f * PW_SLACK, true, lo, unused);
+    query_bounds(phi, L * 0.25f * PW_SLACK, true, unused, hi);
+    return axis_images(uniform(lo), uniform(hi), L);
+}
+
+// [lo, hi] moved out by 2^-20 of each bound meets the box or one of its images.
+__device__ __forceinline__ bool meets_widened(const AxisImages& b, const float lo, const float hi)
+{
+    return b.meets(lo - fabsf(lo) * PW_SLACK, hi + fabsf(hi) * PW_SLACK);
+}
+
+// The centres that no point of [blo, bhi] wraps against: [bhi - h, blo + h], moved inward (open axis: all).
+struct NoWrap {
+    float lo, hi;
+    __device__ __forceinline__ bool holds(const float x) const { return x >= lo && x <= hi; }
+};
+__device__ __forceinline__ NoWrap no_wrap(const AxisImages& b, const float h)
+{
+    const float l = b.hi - h, u = b.lo + h;
+    const bool open = !(h < __int_as_float(0x7f800000));
+    return { open ? __int_as_float(0xff800000) : uniform(l + fabsf(l) * PW_SLACK),
+             open ? __int_as_float(0x7f800000) : uniform(u - fabsf(u) * PW_SLACK) };
+}
+
+// NW = channels of this walk (0: counts only).  Args: InterpArgs, or Periodic<InterpArgs> for the
+// periodic walk.
+template <int KIND, int NW, typename Args>
+__global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
+{
+    constexpr bool PERIODIC = is_periodic<Args>::value;
     constexpr int NS = NW > 0 ? NW : 1;
     __shared__ float4 s_rec[PW_WAVES][64];               // survivors: {x, y, z, H^2}
     __shared__ float2 s_inv[PW_WAVES][NW > 0 ? 64 : 1];  // {1/H, 1/H^3}
@@ -91,6 +148,29 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs 
     const float plo_x = wave_min(px), phi_x = wave_max(px);
     const float plo_y = wave_min(py), phi_y = wave_max(py);
     const float plo_z = wave_min(pz), phi_z = wave_max(pz);
+    // periodic: the box's images, the centres no point wraps against, whether any image meets the root's box
+    AxisImages bx = {}, by = {}, bz = {};
+    NoWrap nx = {}, ny = {}, nz = {};
+    bool images = true, plain = true;
+    float hx = 0.0f, hy = 0.0f, hz = 0.0f;
+    if constexpr (PERIODIC) {
+        hx = a.per.h[0]; hy = a.per.h[1]; hz = a.per.h[2];
+        bx = point_images(plo_x, phi_x, a.per.L[0]);
+        by = point_images(plo_y, phi_y, a.per.L[1]);
+        bz = point_images(plo_z, phi_z, a.per.L[2]);
+        nx = no_wrap(bx, hx); ny = no_wrap(by, hy); nz = no_wrap(bz, hz);
+        const int rt = *a.root;
+        if (rt >= 0 && rt < a.n_nodes) {                  // (the root's box: the union of its children's)
+            const float4* np = a.nodes + 4 * size_t(rt);
+            const float4 L = np[1], R = np[2], Z = np[3];
+            const float dlo_x = fminf(L.x, R.x), dhi_x = fmaxf(L.y, R.y), dlo_y = fminf(L.z, R.z), dhi_y = fmaxf(L.w, R.w);
+            const float dlo_z = fminf(Z.x, Z.z), dhi_z = fmaxf(Z.y, Z.w);
+            images = overlaps_widened(dlo_x, dhi_x, bx.mlo, bx.mhi) || overlaps_widened(dlo_x, dhi_x, bx.plo, bx.phi)
+                || overlaps_widened(dlo_y, dhi_y, by.mlo, by.mhi) || overlaps_widened(dlo_y, dhi_y, by.plo, by.phi)
+                || overlaps_widened(dlo_z, dhi_z, bz.mlo, bz.mhi) || overlaps_widened(dlo_z, dhi_z, bz.plo, bz.phi);
+            images = __builtin_amdgcn_readfirstlane(int(images)) != 0;
+        }
+    }
 
     // ---- class sums ----
     float acc[NS];
@@ -115,10 +195,23 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs 
         if (idx < a.n_nodes) {
             const float4* np = a.nodes + 4 * size_t(idx);
             const float4 n0 = np[0], L = np[1], R = np[2], Z = np[3];
-            const bool hit_l = overlaps_widened(L.x, L.y, plo_x, phi_x) && overlaps_widened(L.z, L.w, plo_y, phi_y)
-                && overlaps_widened(Z.x, Z.y, plo_z, phi_z);
-            const bool hit_r = overlaps_widened(R.x, R.y, plo_x, phi_x) && overlaps_widened(R.z, R.w, plo_y, phi_y)
-                && overlaps_widened(Z.z, Z.w, plo_z, phi_z);
+            bool hit_l, hit_r;
+            if constexpr (PERIODIC) {
+                if (images) {
+                    hit_l = meets_widened(bx, L.x, L.y) && meets_widened(by, L.z, L.w) && meets_widened(bz, Z.x, Z.y);
+                    hit_r = meets_widened(bx, R.x, R.y) && meets_widened(by, R.z, R.w) && meets_widened(bz, Z.z, Z.w);
+                } else {
+                    hit_l = overlaps_widened(L.x, L.y, bx.lo, bx.hi) && overlaps_widened(L.z, L.w, by.lo, by.hi)
+                        && overlaps_widened(Z.x, Z.y, bz.lo, bz.hi);
+                    hit_r = overlaps_widened(R.x, R.y, bx.lo, bx.hi) && overlaps_widened(R.z, R.w, by.lo, by.hi)
+                        && overlaps_widened(Z.z, Z.w, bz.lo, bz.hi);
+                }
+            } else {
+                hit_l = overlaps_widened(L.x, L.y, plo_x, phi_x) && overlaps_widened(L.z, L.w, plo_y, phi_y)
+                    && overlaps_widened(Z.x, Z.y, plo_z, phi_z);
+                hit_r = overlaps_widened(R.x, R.y, plo_x, phi_x) && overlaps_widened(R.z, R.w, plo_y, phi_y)
+                    && overlaps_widened(Z.z, Z.w, plo_z, phi_z);
+            }
             if (hit_r) push(__float_as_int(n0.y));
             if (hit_l) push(__float_as_int(n0.x));       // popped first: ascending primitive order
             continue;
@@ -126,9 +219,23 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs 
         const int4 lf = a.leaves[idx - a.n_nodes];
         sweep_clusters(a.spheres, lf.x, lf.x + lf.y, lane,
             [&](const bool in, const float4& s) {
-                return in && overlaps_widened(s.x - s.w, s.x + s.w, plo_x, phi_x)
-                    && overlaps_widened(s.y - s.w, s.y + s.w, plo_y, phi_y)
-                    && overlaps_widened(s.z - s.w, s.z + s.w, plo_z, phi_z);
+                if constexpr (PERIODIC) {
+                    // a sphere above half a period is off (NaN H: no box test is true)
+                    const bool on = in && !(s.w > hx || s.w > hy || s.w > hz);
+                    const bool kept = on && (images
+                        ? meets_widened(bx, s.x - s.w, s.x + s.w) && meets_widened(by, s.y - s.w, s.y + s.w)
+                            && meets_widened(bz, s.z - s.w, s.z + s.w)
+                        : overlaps_widened(s.x - s.w, s.x + s.w, bx.lo, bx.hi)
+                            && overlaps_widened(s.y - s.w, s.y + s.w, by.lo, by.hi)
+                            && overlaps_widened(s.z - s.w, s.z + s.w, bz.lo, bz.hi));
+                    const bool wraps = kept && !(nx.holds(s.x) && ny.holds(s.y) && nz.holds(s.z));
+                    plain = __builtin_amdgcn_ballot_w64(wraps) == 0ull;
+                    return kept;
+                } else {
+                    return in && overlaps_widened(s.x - s.w, s.x + s.w, plo_x, phi_x)
+                        && overlaps_widened(s.y - s.w, s.y + s.w, plo_y, phi_y)
+                        && overlaps_widened(s.z - s.w, s.z + s.w, plo_z, phi_z);
+                }
             },
             [&](const int pos, const float4& s, const int j) {
                 s_rec[wv][pos] = make_float4(s.x, s.y, s.z, s.w * s.w);
@@ -155,7 +262,14 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs 
                 tests += uint64_t(n_surv);
                 for (int j = 0; j < n_surv; ++j) {
                     const float4 r = s_rec[wv][j];
-                    const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
+                    float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
+                    if constexpr (PERIODIC) {
+                        if (!plain) {                              // (wave-uniform)
+                            dx = wrap_sep(dx, a.per.L[0], hx);
+                            dy = wrap_sep(dy, a.per.L[1], hy);
+                            dz = wrap_sep(dz, a.per.L[2], hz);
+                        }
+                    }
                     const float d2 = (dx * dx + dy * dy) + dz * dz;
                     if (d2 < r.w) {
                         ++count;
@@ -193,14 +307,15 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const InterpArgs 
 unsigned long long* g_tests = nullptr;
 bool g_stats = false;
 
-grace_status launch_walk(const InterpArgs& a, int kind, int nw, hipStream_t stream)
+template <typename Args>
+grace_status launch_walk(const Args& a, int kind, int nw, hipStream_t stream)
 {
     const int blocks = ceil_div(size_t(a.n_packets), PW_WAVES);
     if (nw == 0) {
-        interpolate_kernel<GRACE_SPH_KERNEL_CUBIC, 0><<<blocks, PW_BLOCK, 0, stream>>>(a);
+        interpolate_kernel<GRACE_SPH_KERNEL_CUBIC, 0, Args><<<blocks, PW_BLOCK, 0, stream>>>(a);
     } else {
         with_kernel(kind, nw, [&](auto k, auto n) {
-            interpolate_kernel<decltype(k)::value, decltype(n)::value><<<blocks, PW_BLOCK, 0, stream>>>(a);
+            interpolate_kernel<decltype(k)::value, decltype(n)::value, Args><<<blocks, PW_BLOCK, 0, stream>>>(a);
         });
     }
     GRACE_CHECK_LAUNCH();
@@ -239,7 +354,8 @@ grace_status interp_hook(InterpArgs& a, hipStream_t stream)
 }
 
 // The walks of one call: channels four at a time, counts with the first walk.
-grace_status interp_walks(InterpArgs a, int kind, const float* d_weights, int n_channels, float* d_out,
+template <typename Args>
+grace_status interp_walks(Args a, int kind, const float* d_weights, int n_channels, float* d_out,
                           int* d_counts, hipStream_t stream)
 {
     if (!d_out) {
@@ -255,44 +371,42 @@ grace_status interp_walks(InterpArgs a, int kind, const float* d_weights, int n_
     return GRACE_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points, int elems_per_point,
-                                         const float* d_spheres, size_t n_spheres, const int* d_nodes,
-                                         size_t n_nodes, const int* d_leaves, const int* d_root,
-                                         const float* d_weights, int n_channels,
-                                         float* d_out, int* d_counts, grace_stream stream)
+// grace_interpolate_points_f4 and its periodic form: `a` is zero but for a period.
+template <typename Args>
+grace_status interpolate_points(Args a, const float* d_points, size_t n_points, int elems_per_point,
+                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                const float* d_weights, int n_channels,
+                                float* d_out, int* d_counts, grace_stream stream)
 {
     GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "interpolate: elements per point must be 3..16");
     GRACE_REQUIRE(n_points < (size_t(1) << 31), "interpolate: too many points");
     if (n_points == 0) return GRACE_OK;   // (before the output checks: a caller's empty arrays may be null)
     GRACE_REQUIRE(d_points, "interpolate: null points");
-    InterpArgs a = {};
     TraceState* ts = nullptr;
     GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
                             d_out, d_counts, &ts));
     const hipStream_t stream_ = as_stream(stream);
     GRACE_TRY(interp_hook(a, stream_));
     return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                      [&](InterpArgs w, size_t max_packets) -> grace_status {
+                      [&](Args w, size_t max_packets) -> grace_status {
         w.n_packets = int(max_packets);
         return interp_walks(w, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_);
     });
 }
 
-grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
-                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
-                                       size_t n_nodes, const int* d_leaves, const int* d_root,
-                                       const float* d_weights, int n_channels,
-                                       float* d_out, int* d_counts, grace_stream stream)
+// grace_interpolate_grid_f4 and its periodic form.
+template <typename Args>
+grace_status interpolate_grid(Args a, const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                              const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                              size_t n_nodes, const int* d_leaves, const int* d_root,
+                              const float* d_weights, int n_channels,
+                              float* d_out, int* d_counts, grace_stream stream)
 {
     GRACE_REQUIRE(h_origin3 && h_uvw9 && h_dims3, "interpolate_grid: null lattice argument");
     GRACE_REQUIRE(h_dims3[0] > 0 && h_dims3[1] > 0 && h_dims3[2] > 0, "interpolate_grid: dimensions must be positive");
     const size_t n = size_t(h_dims3[0]) * size_t(h_dims3[1]) * size_t(h_dims3[2]);
     GRACE_REQUIRE(n < (size_t(1) << 31), "interpolate_grid: too many lattice points");
-    InterpArgs a = {};
     TraceState* ts = nullptr;
     GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
                             d_out, d_counts, &ts));
@@ -313,6 +427,56 @@ grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uv
     return timed_walks(a, *ts, stream_, [&] {  // (a lattice has no packets to make)
         return interp_walks(a, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_);
     });
+}
+
+} // namespace
+
+extern "C" {
+
+grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                         const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                         size_t n_nodes, const int* d_leaves, const int* d_root,
+                                         const float* d_weights, int n_channels,
+                                         float* d_out, int* d_counts, grace_stream stream)
+{
+    return interpolate_points(InterpArgs(), d_points, n_points, elems_per_point, d_spheres, n_spheres, d_nodes, n_nodes,
+                              d_leaves, d_root, d_weights, n_channels, d_out, d_counts, stream);
+}
+
+grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                       const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                       size_t n_nodes, const int* d_leaves, const int* d_root,
+                                       const float* d_weights, int n_channels,
+                                       float* d_out, int* d_counts, grace_stream stream)
+{
+    return interpolate_grid(InterpArgs(), h_origin3, h_uvw9, h_dims3, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves,
+                            d_root, d_weights, n_channels, d_out, d_counts, stream);
+}
+
+grace_status grace_interpolate_points_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                  const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                  size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                  const float* d_weights, int n_channels,
+                                                  float* d_out, int* d_counts, const float* h_period3,
+                                                  grace_stream stream)
+{
+    Periodic<InterpArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, nullptr));
+    return interpolate_points(a, d_points, n_points, elems_per_point, d_spheres, n_spheres, d_nodes, n_nodes,
+                              d_leaves, d_root, d_weights, n_channels, d_out, d_counts, stream);
+}
+
+grace_status grace_interpolate_grid_periodic_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                const float* d_weights, int n_channels,
+                                                float* d_out, int* d_counts, const float* h_period3,
+                                                grace_stream stream)
+{
+    Periodic<InterpArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, nullptr));
+    return interpolate_grid(a, h_origin3, h_uvw9, h_dims3, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves,
+                            d_root, d_weights, n_channels, d_out, d_counts, stream);
 }
 
 grace_status grace_interpolate_enable_stats(int enabled)

@@ -69,8 +69,6 @@
 #include "packet_walk.hpp"
 
 #include <cmath>
-#include <limits>
-#include <type_traits>
 
 namespace {
 
@@ -79,52 +77,6 @@ struct WalkArgs : PacketPoints, PacketScene {
     const float* radii;          // per point, caller's order, or null: `radius` for all
     float radius;
 };
-
-// A periodic box: per axis the period L (0: open) and h = fl(0.5 L) (open: +inf).
-struct WalkPeriod {
-    float L[3];
-    float h[3];
-};
-
-// Args with a period beside them: what the periodic kernels take (walk() below picks the walk).
-template <typename Base>
-struct Periodic : Base {
-    WalkPeriod per;
-};
-template <typename T> struct is_periodic : std::false_type {};
-template <typename Base> struct is_periodic<Periodic<Base>> : std::true_type {};
-
-// The union box on one axis and its images shifted by -L and +L, rounded outward (wave-uniform).
-struct AxisImages {
-    float lo, hi, mlo, mhi, plo, phi;
-    __device__ __forceinline__ bool meets(const float blo, const float bhi) const
-    {
-        return overlaps(blo, bhi, lo, hi) || overlaps(blo, bhi, mlo, mhi) || overlaps(blo, bhi, plo, phi);
-    }
-    __device__ __forceinline__ bool direct(const float x) const { return x >= lo && x <= hi; }
-    __device__ __forceinline__ bool holds(const float x) const
-    {
-        return direct(x) || (x >= mlo && x <= mhi) || (x >= plo && x <= phi);
-    }
-};
-
-__device__ __forceinline__ float uniform(const float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-__device__ __forceinline__ AxisImages axis_images(const float ulo, const float uhi, const float L)
-{
-    const float ml = ulo - L, mh = uhi - L, pl = ulo + L, ph = uhi + L;
-    return { ulo, uhi, uniform(ml - fabsf(ml) * PW_SLACK), uniform(mh + fabsf(mh) * PW_SLACK),
-             uniform(pl - fabsf(pl) * PW_SLACK), uniform(ph + fabsf(ph) * PW_SLACK) };
-}
-
-// One component of the periodic separation: at most one wrap (open axis: h = +inf, none).
-__device__ __forceinline__ float wrap_sep(const float d, const float L, const float h)
-{
-    return d > h ? d - L : (d < -h ? d + L : d);
-}
 
 // One packet.  s_rec: the wave's 64 survivor records.  PERIODIC: the separation wraps by `per`.
 template <typename Visitor, bool PERIODIC = false>
@@ -293,22 +245,6 @@ __device__ __forceinline__ void walk(const Args& a, const int packet, const int 
 {
     if constexpr (is_periodic<Args>::value) walk_packet<Visitor, true>(a, packet, lane, s_rec, v, a.per);
     else walk_packet(a, packet, lane, s_rec, v);
-}
-
-// A caller's period (three host floats) as the walk takes it, checked before anything is enqueued.
-// radius: the call's host radius, which must not exceed half a period (NULL: the radii are per point
-// and the walk switches such points off).
-grace_status walk_period(WalkPeriod& per, const float* h_period3, const float* radius)
-{
-    GRACE_REQUIRE(h_period3, "periodic query: null period");
-    for (int d = 0; d < 3; ++d) {
-        const float L = h_period3[d];
-        GRACE_REQUIRE(std::isfinite(L) && L >= 0.0f, "periodic query: a period must be finite and not negative (0: open)");
-        per.L[d] = L > 0.0f ? L : 0.0f;
-        per.h[d] = L > 0.0f ? 0.5f * L : std::numeric_limits<float>::infinity();
-        GRACE_REQUIRE(!radius || !(*radius > per.h[d]), "periodic query: the radius exceeds half a period");
-    }
-    return GRACE_OK;
 }
 
 // The checks every entry point over this walk shares (before anything is enqueued), the radii and

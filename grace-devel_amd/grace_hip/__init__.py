@@ -799,32 +799,39 @@ def _interp_scene(spheres, tree):
             _ptr(tree.leaves), _ptr(tree.root_index))
 
 
-def interpolate_sph(points, spheres, tree, weights=None, out=None, counts=None, check=False):
+def interpolate_sph(points, spheres, tree, weights=None, out=None, counts=None, check=False, period=None):
     """The SPH field at points (an extension the reference lacks):
     out[p, c] = sum over spheres i containing point p of fl32(weights[i, c] * W(|p - x_i|, H_i)), with
     the context's SPH kernel (set_sph_kernel; a custom table is refused), summed per channel in the
     class order of the column densities; counts[p] = the number of spheres containing p.
     points: float32 [n, 3..16] (x y z first); weights: float32 [n_spheres] or [n_spheres, C]
     (1 <= C <= 64) in the order of `spheres` (tree order: build_tree(want_perm=True)), or None for
-    counts only.  Returns out (None without weights) and counts (allocated when weights is None or
-    counts is given)."""
+    counts only.  period: None, or (Lx, Ly, Lz) for a periodic box (0 leaves an axis open): every
+    component of p - x is wrapped once into [-L/2, L/2] before it is squared, and a sphere whose H exceeds
+    half a period contributes nothing (include/grace_hip.h, "Periodic boxes").  Returns out (None without
+    weights) and counts (allocated when weights is None or counts is given)."""
     if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
         raise ValueError("points must be float32 of shape [n, 3..16]")
     points = points.contiguous()
     n_ch, out, counts = _interp_outputs(len(points), len(spheres), weights, out, counts, points.device)
-    _check(_lib.grace_interpolate_points_f4(_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
-                                            *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch),
-                                            _ptr(out), _ptr(counts), _stream()))
+    args = (_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]), *_interp_scene(spheres, tree),
+            _ptr(weights), C.c_int(n_ch), _ptr(out), _ptr(counts))
+    if period is None:
+        _check(_lib.grace_interpolate_points_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_interpolate_points_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
     return out, counts
 
 
 def interpolate_grid_sph(origin, u, v, w, dims, spheres, tree, weights=None, out=None, counts=None,
-                         check=False):
+                         check=False, period=None):
     """interpolate_sph over the lattice p(i, j, k) = origin + i u + j v + k w (fp32, per component
     fl(fl(fl(o + fl(i u)) + fl(j v)) + fl(k w))), dims = (nx, ny, nz); nz = 1 is a slice (oblique
-    ones too).  out: float32 [nz, ny, nx] or [nz, ny, nx, C]; counts: int32 [nz, ny, nx]."""
+    ones too).  out: float32 [nz, ny, nx] or [nz, ny, nx, C]; counts: int32 [nz, ny, nx].  period: as for
+    interpolate_sph (a mesh over a periodic box keeps the mass of the spheres that stick out of a face)."""
     nx, ny, nz = (int(d) for d in dims)
     if min(nx, ny, nz) <= 0:
         raise ValueError("grid dimensions must be positive")
@@ -836,8 +843,13 @@ def interpolate_grid_sph(origin, u, v, w, dims, spheres, tree, weights=None, out
     o3 = (C.c_float * 3)(*[float(x) for x in origin])
     uvw = (C.c_float * 9)(*[float(x) for x in (*u, *v, *w)])
     d3 = (C.c_int * 3)(nx, ny, nz)
-    _check(_lib.grace_interpolate_grid_f4(o3, uvw, d3, *_interp_scene(spheres, tree), _ptr(weights),
-                                          C.c_int(n_ch), _ptr(flat_out), _ptr(flat_counts), _stream()))
+    args = (o3, uvw, d3, *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch), _ptr(flat_out),
+            _ptr(flat_counts))
+    if period is None:
+        _check(_lib.grace_interpolate_grid_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_interpolate_grid_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
     grid = lambda t: None if t is None else t.view(nz, ny, nx, *t.shape[1:])
@@ -856,11 +868,13 @@ def interpolate_last_stats():
     return v.value
 
 
-def nearest_neighbours_sph(points, spheres, tree, k, indices=None, d2=None, check=False):
+def nearest_neighbours_sph(points, spheres, tree, k, indices=None, d2=None, check=False, period=None):
     """The k nearest sphere centres of each point (an extension the reference lacks): spheres are
     ranked by (d2, tree index), d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in fp32; row p holds
     the first k.  Slots beyond the number of spheres, and every slot of a point with a non-finite
-    coordinate, are -1 / +inf.  points: float32 [n, 3..16] (x y z first); 1 <= k <= 64.
+    coordinate, are -1 / +inf.  points: float32 [n, 3..16] (x y z first); 1 <= k <= 64.  period: None, or
+    (Lx, Ly, Lz) for a periodic box (0 leaves an axis open): every component of p - x is wrapped once
+    into [-L/2, L/2] before it is squared (include/grace_hip.h, "Periodic boxes"); there is no radius limit.
     Returns (indices int32 [n, k], d2 float32 [n, k])."""
     if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
         raise ValueError("points must be float32 of shape [n, 3..16]")
@@ -877,26 +891,35 @@ def nearest_neighbours_sph(points, spheres, tree, k, indices=None, d2=None, chec
         raise ValueError("indices must be int32 of shape %s" % (shape,))
     if d2.dtype != torch.float32 or tuple(d2.shape) != shape:
         raise ValueError("d2 must be float32 of shape %s" % (shape,))
-    _check(_lib.grace_nearest_neighbours_f4(_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]),
-                                            *_interp_scene(spheres, tree), C.c_int(k), _ptr(indices), _ptr(d2),
-                                            _stream()))
+    args = (_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]), *_interp_scene(spheres, tree),
+            C.c_int(k), _ptr(indices), _ptr(d2))
+    if period is None:
+        _check(_lib.grace_nearest_neighbours_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_nearest_neighbours_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
     return indices, d2
 
 
-def smoothing_lengths_sph(spheres, tree, k, eta=1.0, out=None, check=False):
+def smoothing_lengths_sph(spheres, tree, k, eta=1.0, out=None, check=False, period=None):
     """Smoothing lengths from the k-th nearest neighbour: h[i] = fl(eta * sqrt(D_i)), D_i the d2 of
     slot k-1 of nearest_neighbours_sph at sphere i's own centre (it is its own first neighbour).
     Returns h float32 [n] in tree order (the order of `spheres`, which is only read); to use it as
-    H, write it into spheres[:, 3] and build the tree again.  1 <= k <= min(64, n); eta > 0."""
+    H, write it into spheres[:, 3] and build the tree again.  1 <= k <= min(64, n); eta > 0.  period: as for
+    nearest_neighbours_sph (a snapshot's BoxSize: particles near a face count their neighbours beyond it)."""
     n = len(spheres)
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=spheres.device)
     if out.dtype != torch.float32 or tuple(out.shape) != (n,):
         raise ValueError("out must be float32 of shape [%d]" % n)
-    _check(_lib.grace_smoothing_lengths_f4(*_interp_scene(spheres, tree), C.c_int(int(k)), C.c_float(float(eta)),
-                                           _ptr(out), _stream()))
+    args = (*_interp_scene(spheres, tree), C.c_int(int(k)), C.c_float(float(eta)), _ptr(out))
+    if period is None:
+        _check(_lib.grace_smoothing_lengths_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_smoothing_lengths_periodic_f4(*args, *_period_tail(period)))
     if check:
         trace_status()
     return out

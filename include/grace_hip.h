@@ -874,7 +874,8 @@ grace_status grace_trace_hits_f4_f64(const void* d_rays, size_t n_rays, const fl
  * elems_per_point, channel count, dimension or scene, or a custom SPH kernel table (there is no
  * f(q)).  Zero points: GRACE_OK, nothing written.  A packet that exhausts its 128-entry stack sets
  * the status word of grace_trace_status (GRACE_STACK_OVERFLOW); nothing is written out of bounds.
- * Stream-ordered, no host synchronisation, no allocation (the context workspace): capturable. */
+ * Stream-ordered, no host synchronisation, no allocation (the context workspace): capturable.
+ * Periodic boxes: grace_interpolate_points_periodic_f4 / grace_interpolate_grid_periodic_f4 below. */
 grace_status grace_interpolate_points_f4(const float* d_points, size_t n_points, int elems_per_point,
                                          const float* d_spheres, size_t n_spheres, const int* d_nodes,
                                          size_t n_nodes, const int* d_leaves, const int* d_root,
@@ -922,7 +923,8 @@ grace_status grace_interpolate_last_stats(unsigned long long* h_survivor_tests);
  * cover exactly [0, n_spheres), as build_tree and build_ALBVH give; node boxes built with any H >= 0 contain the centres.  A packet that exhausts
  * its 128-entry stack sets the status word of grace_trace_status (GRACE_STACK_OVERFLOW); nothing is
  * written out of bounds.  Stream-ordered, no host synchronisation, no allocation (the context
- * workspace): capturable.  grace_trace_enable_timing / grace_trace_last_kernel_ms time the walk. */
+ * workspace): capturable.  grace_trace_enable_timing / grace_trace_last_kernel_ms time the walk.
+ * Periodic boxes: grace_nearest_neighbours_periodic_f4 / grace_smoothing_lengths_periodic_f4 below. */
 grace_status grace_nearest_neighbours_f4(const float* d_points, size_t n_points, int elems_per_point,
                                          const float* d_spheres, size_t n_spheres, const int* d_nodes,
                                          size_t n_nodes, const int* d_leaves, const int* d_root,
@@ -1120,9 +1122,9 @@ grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int el
                                   unsigned long long* d_totals, int* d_counts, float* d_sums,
                                   grace_stream stream);
 
-/* ---- Periodic boxes for the range queries, friends-of-friends and pair counts -------------------
- * (an extension the reference lacks)
- * The three families above on a torus: a cosmological snapshot is a periodic box, and a halo that
+/* ---- Periodic boxes for the point queries: range queries, friends-of-friends, pair counts, nearest
+ * neighbours, smoothing lengths and interpolation (an extension the reference lacks)
+ * The five families above on a torus: a cosmological snapshot is a periodic box, and a halo that
  * straddles a face, the pairs across it and the neighbours beyond it belong to the answer.  Each
  * function below takes the arguments of its open counterpart plus h_period3 before the stream, and
  * is that counterpart in everything this block does not restate: arguments, outputs, order, off
@@ -1151,19 +1153,37 @@ grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int el
  * scalar (`radius` with d_radii NULL, the linking length, the last edge), a value above
  * fl(0.5 * L_a) on a periodic axis is GRACE_INVALID_ARGUMENT, nothing written.
  *
+ * Nearest neighbours and smoothing lengths (grace_nearest_neighbours_periodic_f4 /
+ * grace_smoothing_lengths_periodic_f4, extending grace_nearest_neighbours_f4 /
+ * grace_smoothing_lengths_f4): there is no radius, so no limit.  Every centre is ranked once, by
+ * the pair (wrapped d2, tree index); a k-th distance above half a period is legal and is the
+ * one-wrap d2 above (beyond half a period it is no longer the distance to the nearest image).
+ * d_h[i] = fl(eta * sqrt_rn(D_i)) with D_i the wrapped d2 of slot k-1; k, eta, off points, padding
+ * with -1 / +inf and the outputs are the open call's.
+ *
+ * Interpolation (grace_interpolate_points_periodic_f4 / grace_interpolate_grid_periodic_f4,
+ * extending grace_interpolate_points_f4 / grace_interpolate_grid_f4): the radius belongs to the
+ * sphere, so the rule above applies to it: a sphere whose H exceeds fl(0.5 * L_a) on a periodic axis
+ * is OFF -- it contributes to no point and to no count (more than one of its images could contain a
+ * point); H == fl(0.5 * L_a) is on.  Every other sphere is tested once per point, never per image:
+ * containment is wrapped d2 < fl(H * H), W = fl(K(fl(sqrt_rn(d2) * ih)) * fl(fl(ih * ih) * ih)) with
+ * that d2, and the class order of the sums, the lattice's positions and the outputs are the open
+ * call's.
+ *
  * Identities, bit for bit: L = (0, 0, 0) gives the open function's output; so does any finite L larger
- * than twice the extent of points and centres together on every axis (no |d| exceeds h).  Lists and
- * running sums are in ascending tree index, as above.  The result is a function of the points, the
- * radii (edges, linking length), the centres, the weights and L only: not of the H the tree was
- * built with (any H >= 0), of max_per_leaf, of the packets or of the stream.
+ * than twice the extent of points and centres together on every axis (no |d| exceeds h; for the
+ * interpolation, where no H exceeds half of it either).  Lists and running sums are in ascending
+ * tree index, as above.  The result is a function of the points, the radii (edges, linking length,
+ * k and eta; for the interpolation the spheres' own H), the centres, the weights and L only: not of
+ * the H the tree was built with (any H >= 0; the interpolation's tree is built with the spheres'
+ * H), of max_per_leaf, of the packets, of the order of the points or of the stream.
  *
  * GRACE_INVALID_ARGUMENT, nothing written: a NULL h_period3, a bad period, a host radius above half
  * a period, and whatever the open counterpart refuses.  (The period is checked first by the range
- * queries and friends-of-friends, after the edges by the pair counts.)  Zero points or spheres: as
- * the open counterpart, after the period's check.
- * Not provided: periodic ray traces, interpolation (grace_interpolate_*) and nearest neighbours
- * (grace_nearest_neighbours_f4 / grace_smoothing_lengths_f4); a box origin (none is needed);
- * radii above half a period (more than one image of a centre in range). */
+ * queries, friends-of-friends, the neighbours and the interpolation, after the edges by the pair
+ * counts.)  Zero points or spheres: as the open counterpart, after the period's check.
+ * Not provided: periodic ray traces; a box origin (none is needed); radii above half a period
+ * (more than one image of a centre in range, or of a sphere around a point). */
 grace_status grace_range_counts_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
                                             const float* d_radii, float radius,
                                             const float* d_spheres, size_t n_spheres, const int* d_nodes,
@@ -1188,6 +1208,30 @@ grace_status grace_pair_counts_periodic_f4(const float* d_points, size_t n_point
                                            const float* d_weights, int n_channels,
                                            unsigned long long* d_totals, int* d_counts, float* d_sums,
                                            const float* h_period3, grace_stream stream);
+/* grace_nearest_neighbours_f4 / grace_smoothing_lengths_f4 in a periodic box ("Nearest neighbours and
+ * smoothing lengths" above). */
+grace_status grace_nearest_neighbours_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                  const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                  size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                  int k, int* d_indices, float* d_d2, const float* h_period3,
+                                                  grace_stream stream);
+grace_status grace_smoothing_lengths_periodic_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                 size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                 int k, float eta, float* d_h, const float* h_period3,
+                                                 grace_stream stream);
+/* grace_interpolate_points_f4 / grace_interpolate_grid_f4 in a periodic box ("Interpolation" above). */
+grace_status grace_interpolate_points_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                  const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                  size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                  const float* d_weights, int n_channels,
+                                                  float* d_out, int* d_counts, const float* h_period3,
+                                                  grace_stream stream);
+grace_status grace_interpolate_grid_periodic_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                const float* d_weights, int n_channels,
+                                                float* d_out, int* d_counts, const float* h_period3,
+                                                grace_stream stream);
 
 #ifdef __cplusplus
 }
