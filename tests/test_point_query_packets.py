@@ -427,70 +427,75 @@ def kernel_reset(gh):
     gh.set_sph_kernel("cubic")
 
 
-def run_counts(gh, inp, d, tree, cuda, shared=False, n_ch=5):
+def run_counts(gh, inp, d, tree, cuda, shared=False, n_ch=5, period=None):
     """range_counts_sph into pre-filled buffers -> (counts, sums or None)."""
     pd, rd, wd = inp["points"], inp["radii"], inp["w5"]
     m = len(pd)
     cnt = _i32((m,), cuda)
     if shared:
-        gh.range_counts_sph(pd, float(R_SHARED), d, tree, counts=cnt, check=True)
+        gh.range_counts_sph(pd, float(R_SHARED), d, tree, counts=cnt, check=True, period=period)
         return cnt.cpu().numpy(), None
     out = _f32((m, n_ch), cuda)
-    gh.range_counts_sph(pd, rd, d, tree, weights=wd, counts=cnt, out=out, check=True)
+    gh.range_counts_sph(pd, rd, d, tree, weights=wd, counts=cnt, out=out, check=True, period=period)
     return cnt.cpu().numpy(), out.cpu().numpy()
 
 
-def run_lists(gh, inp, d, tree, cuda, total):
+def run_lists(gh, inp, d, tree, cuda, total, period=None):
     """The count, scan, fill sequence of range_neighbours_sph through the C ABI, into pre-filled buffers of
-    the restated total -> (counts, offsets, indices, d2); stops after the counts if their sum is not `total`."""
+    the restated total -> (counts, offsets, indices, d2); stops after the counts if their sum is not `total`.
+    period: the periodic entry points (the period goes before the stream)."""
     import ctypes as C
     pd, rd = inp["points"], inp["radii"]
     m = len(pd)
     offsets = _i32((m + 1,), cuda)
     offsets[m] = 0
     args = (gh._ptr(pd), C.c_size_t(m), C.c_int(pd.shape[1]), gh._ptr(rd), C.c_float(0.0), *gh._interp_scene(d, tree))
-    assert gh._lib.grace_range_counts_f4(*args, gh._ptr(None), C.c_int(0), gh._ptr(offsets), gh._ptr(None),
-                                         gh._stream()) == gh.GRACE_OK
+    if period is None:
+        count_fn, fill_fn, tail = gh._lib.grace_range_counts_f4, gh._lib.grace_range_neighbours_f4, (gh._stream(),)
+    else:
+        per = np.ascontiguousarray(period, F32)
+        count_fn, fill_fn = gh._lib.grace_range_counts_periodic_f4, gh._lib.grace_range_neighbours_periodic_f4
+        tail = (per.ctypes.data_as(C.c_void_p), gh._stream())
+    assert count_fn(*args, gh._ptr(None), C.c_int(0), gh._ptr(offsets), gh._ptr(None), *tail) == gh.GRACE_OK
     counts = offsets[:m].cpu().numpy()
     if int(counts.astype(np.int64).sum()) != total or counts.min() < 0:
         return counts, None, None, None
     assert gh.exclusive_scan(offsets, offsets) == total
     idx, d2 = _i32((total + 64,), cuda), _f32((total + 64,), cuda)
-    assert gh._lib.grace_range_neighbours_f4(*args, gh._ptr(offsets), gh._ptr(idx), gh._ptr(d2),
-                                             gh._stream()) == gh.GRACE_OK
+    assert fill_fn(*args, gh._ptr(offsets), gh._ptr(idx), gh._ptr(d2), *tail) == gh.GRACE_OK
     gh.trace_status()
     gi, gd = idx.cpu().numpy(), d2.cpu().numpy()
     assert np.all(gi[total:] == -7) and np.all(gd[total:].view(np.uint32) == NAN_BITS)   # nothing past the end
     return counts, offsets.cpu().numpy(), gi[:total], gd[:total]
 
 
-def run_knn(gh, inp, d, tree, cuda, k=K_SMALL):
+def run_knn(gh, inp, d, tree, cuda, k=K_SMALL, period=None):
     pd = inp["points"]
     idx, d2 = _i32((len(pd), k), cuda), _f32((len(pd), k), cuda)
-    gh.nearest_neighbours_sph(pd, d, tree, k, indices=idx, d2=d2, check=True)
+    gh.nearest_neighbours_sph(pd, d, tree, k, indices=idx, d2=d2, check=True, period=period)
     return idx.cpu().numpy(), d2.cpu().numpy()
 
 
-def run_field(gh, inp, d, tree, cuda):
+def run_field(gh, inp, d, tree, cuda, period=None):
     pd = inp["points"]
     out, cnt = _f32((len(pd), 2), cuda), _i32((len(pd),), cuda)
-    gh.interpolate_sph(pd, d, tree, inp["w2"], out=out, counts=cnt, check=True)
+    gh.interpolate_sph(pd, d, tree, inp["w2"], out=out, counts=cnt, check=True, period=period)
     return out.cpu().numpy(), cnt.cpu().numpy()
 
 
-def run_pairs(gh, inp, d, tree, cuda, profiles=True):
+def run_pairs(gh, inp, d, tree, cuda, profiles=True, period=None):
     """(totals uint64 [E], counts int32 [m, E] or None, sums float32 [m, E, 2] or None) into pre-filled buffers."""
     import torch
     pd = inp["points"]
     m, ne = len(pd), len(EDGES)
     edges = gh._pair_edges(EDGES)
     totals = torch.full((ne,), -7, dtype=torch.int64, device=cuda)
-    gh._pair_call(pd, edges, d, tree, None, 0, totals, None, None, True)
+    gh._pair_call(pd, edges, d, tree, None, 0, totals, None, None, True, period)
     tot = totals.cpu().numpy().view(np.uint64)
     if not profiles:
         return tot, None, None
     cnt, sums = _i32((m, ne), cuda), _f32((m, ne, 2), cuda)
-    gh._pair_call(pd, edges, d, tree, inp["w2"], 2, None, cnt, sums, True)
+    gh._pair_call(pd, edges, d, tree, inp["w2"], 2, None, cnt, sums, True, period)
     return tot, cnt.cpu().numpy(), sums.cpu().numpy()
 
 
