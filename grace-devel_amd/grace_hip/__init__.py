@@ -1516,10 +1516,201 @@ def trace_sph_d4(rays, spheres, tree):
     return offsets, idx, integrals, dists
 
 
-def project_sph(spheres, n_side, max_per_leaf=32):
+# ---------------------------------------------------------------------------------------
+# Periodic boxes for traces (an extension the reference lacks): include/grace_hip.h,
+# "Periodic boxes for traces", has the definition.  The periodic trace IS the open trace of the
+# rays' segments over the spheres' images, folded back per ray.
+# ---------------------------------------------------------------------------------------
+def _box(lo, period):
+    """(lo, period) of a periodic box -> two arrays of three host floats (the library checks them)."""
+    period = _period(period)
+    if torch.is_tensor(lo):
+        lo = lo.detach().cpu().numpy()
+    lo = np.ascontiguousarray(np.asarray(lo, dtype=np.float32).reshape(-1))
+    if len(lo) != 3:
+        raise ValueError("lo must hold three values, the box origin")
+    return lo, period
+
+
+def _box_args(lo, period):
+    return lo.ctypes.data_as(C.c_void_p), period.ctypes.data_as(C.c_void_p)
+
+
+def _checked_total(offsets, what):
+    total = exclusive_scan(offsets, offsets)
+    if total > INT32_MAX:
+        raise ValueError("%s: %d entries exceed INT32_MAX; the int offsets cannot address them. "
+                         "Split the input into several calls." % (what, total))
+    return total
+
+
+def periodic_sphere_images(spheres, lo, period):
+    """The images of float4 spheres in a periodic box: a sphere that sticks out of a face of a periodic
+    axis is emitted again one period further on, for every subset of the faces it crosses (1, 2, 4 or 8
+    copies, the sphere itself first).  Counts, the library's scan, then the fill; synchronises to read
+    the total (ValueError above INT32_MAX, before any fill).  A centre outside the box or H above half a
+    period sets the status word (trace_status() raises ValueError) and the sphere is emitted once.
+    Returns (images float32 [total, 4], source int32 [total], offsets int32 [n + 1]); spheres is not
+    modified."""
+    _spheres(spheres)
+    lo, period = _box(lo, period)
+    n = len(spheres)
+    offsets = torch.zeros(n + 1, dtype=torch.int32, device=spheres.device)
+    _check(_lib.grace_periodic_image_counts_f4(_ptr(spheres), C.c_size_t(n), *_box_args(lo, period),
+                                               _ptr(offsets), _stream()))
+    total = _checked_total(offsets, "periodic_sphere_images") if n else 0
+    images = torch.empty((total, 4), dtype=torch.float32, device=spheres.device)
+    source = torch.empty(total, dtype=torch.int32, device=spheres.device)
+    if total:
+        _check(_lib.grace_periodic_images_f4(_ptr(spheres), C.c_size_t(n), *_box_args(lo, period),
+                                             _ptr(offsets), _ptr(images), _ptr(source), _stream()))
+    return images, source, offsets
+
+
+def periodic_ray_segments(rays, lo, period):
+    """The segments of rays in a periodic box: every ray cut where it crosses a face of the lattice of
+    boxes, every piece moved back into the box (fp64 arithmetic as stated in include/grace_hip.h).  Any
+    number of rays.  A ray with more than 65536 segments sets the status word and is emitted as itself.
+    Returns (segments float32 [total, 7], offsets int32 [n_rays + 1]): ray r's segments are rows
+    [offsets[r], offsets[r + 1]), in order along the ray.  Synchronises to read the total (ValueError
+    above INT32_MAX, before any fill)."""
+    _rays(rays)
+    lo, period = _box(lo, period)
+    n = len(rays)
+    offsets = torch.zeros(n + 1, dtype=torch.int32, device=rays.device)
+    _check(_lib.grace_periodic_segment_counts(_ptr(rays), C.c_size_t(n), *_box_args(lo, period),
+                                              _ptr(offsets), _stream()))
+    total = _checked_total(offsets, "periodic_ray_segments") if n else 0
+    segments = torch.empty((total, RAY_FLOATS), dtype=torch.float32, device=rays.device)
+    if total:
+        _check(_lib.grace_periodic_segments(_ptr(rays), C.c_size_t(n), *_box_args(lo, period),
+                                            _ptr(offsets), _ptr(segments), _stream()))
+    return segments, offsets
+
+
+class PeriodicScene:
+    """What periodic_scene returns: spheres (the images, in tree order), source (int32 per image: the
+    index of its sphere in the caller's array as passed), tree, lo and period (host float32 [3])."""
+
+    def __init__(self, spheres, source, tree, lo, period):
+        self.spheres, self.source, self.tree, self.lo, self.period = spheres, source, tree, lo, period
+
+
+def periodic_scene(spheres, lo, period, max_per_leaf=32, check=True):
+    """The scene of the periodic traces: the images of `spheres` (periodic_sphere_images) and their tree
+    (build_tree's steps: 30-bit keys, Euclidean deltas, ALBVH), the images' source indices carried
+    through the same stable sort as a payload of their own.  spheres is not modified.  check=True reads
+    the status word (a sphere outside the box or with H above half a period: ValueError)."""
+    images, source, _ = periodic_sphere_images(spheres, lo, period)
+    if check:
+        trace_status()
+    lo, period = _box(lo, period)
+    tree = Tree(len(images), max_per_leaf, device=images.device)
+    if len(images):
+        keys = torch.empty(len(images), dtype=torch.int32, device=images.device)
+        morton_keys_sph(images, keys)
+        source_keys = keys.clone()
+        sort_by_key(source_keys, source, 0, 30)
+        sort_by_key(keys, images, 0, 30)
+        deltas = torch.empty(len(images) + 1, dtype=torch.float32, device=images.device)
+        euclidean_deltas_sph(images, deltas)
+        ALBVH_sph(images, deltas, tree)
+    return PeriodicScene(images, source, tree, lo, period)
+
+
+def _periodic_trace(rays, scene, n_ch, dtype, out, shape, trace):
+    """Segments, the open trace `trace(args, per-segment output)`, then the fold into out."""
+    _rays(rays)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=rays.device)
+    if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("out must be contiguous %s of shape %s" % (dtype, shape))
+    if len(rays) == 0:
+        return out
+    segments, offsets = periodic_ray_segments(rays, scene.lo, scene.period)
+    per_segment = torch.empty((len(segments), n_ch), dtype=dtype, device=rays.device)
+    trace(_trace_args(segments, scene.spheres, scene.tree), per_segment)
+    fold = _lib.grace_periodic_fold_i32 if dtype == torch.int32 else _lib.grace_periodic_fold_f32
+    _check(fold(_ptr(per_segment), _ptr(offsets), C.c_size_t(len(rays)), C.c_int(n_ch), _ptr(out), _stream()))
+    return out
+
+
+def trace_hitcounts_periodic_sph(rays, scene, out=None, check=False):
+    """trace_hitcounts_sph in a periodic box: out[r] = the number of lattice images of the scene's
+    spheres that ray r hits = the sum of the open hit counts of its segments over scene.spheres.  Any
+    number of rays.  scene: periodic_scene(...)."""
+    out = _periodic_trace(rays, scene, 1, torch.int32, out, (len(rays),), lambda a, o: _check(
+        _lib.grace_trace_hitcounts_f4(*a, _ptr(o), _stream())))
+    if check:
+        trace_status()
+    return out
+
+
+def trace_cumulative_periodic_sph(rays, scene, out=None, check=False):
+    """trace_cumulative_sph in a periodic box: out[r] = the fp32 running sum, from 0 and in order along
+    the ray, of the open column densities of ray r's segments over scene.spheres."""
+    out = _periodic_trace(rays, scene, 1, torch.float32, out, (len(rays),), lambda a, o: _check(
+        _lib.grace_trace_cumulative_f4(*a, _ptr(o), _stream())))
+    if check:
+        trace_status()
+    return out
+
+
+def trace_cumulative_weighted_periodic_sph(rays, scene, weights, out=None, check=False):
+    """trace_cumulative_weighted_sph in a periodic box.  weights: float32 [n] or [n, C] (1 <= C <= 64) per
+    CALLER particle, in the order of the array given to periodic_scene: an image carries the weight row
+    of its source.  out: float32 [n_rays] or [n_rays, C]."""
+    if weights.dtype != torch.float32 or weights.dim() not in (1, 2):
+        raise ValueError("weights must be float32 of shape [n] or [n, C]")
+    n_ch = 1 if weights.dim() == 1 else weights.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("weights must have 1..64 channels")
+    n_img = len(scene.spheres)
+    if n_img and (len(weights) == 0 or int(scene.source.max()) >= len(weights)):
+        raise ValueError("weights must hold one row per sphere given to periodic_scene")
+    weights = weights.contiguous()
+    image_weights = torch.empty((n_img, n_ch), dtype=torch.float32, device=weights.device)
+    _check(_lib.grace_periodic_gather_rows_f32(_ptr(weights), _ptr(scene.source), C.c_size_t(n_img),
+                                               C.c_int(n_ch), _ptr(image_weights), _stream()))
+    shape = (len(rays),) if weights.dim() == 1 else (len(rays), n_ch)
+    out = _periodic_trace(rays, scene, n_ch, torch.float32, out, shape, lambda a, o: _check(
+        _lib.grace_trace_cumulative_weighted_f4(*a, _ptr(image_weights), C.c_int(n_ch), _ptr(o), _stream())))
+    if check:
+        trace_status()
+    return out
+
+
+def _project_periodic_sph(spheres, n_side, max_per_leaf, period, lo):
+    lo, period = _box(lo if lo is not None else (0.0, 0.0, 0.0), period)
+    if not (period[0] > 0 and period[0] == period[1]):
+        raise ValueError("project_sph: a periodic map needs Lx == Ly > 0 (square pixels over the box face); "
+                         "for other boxes make the rays yourself and use periodic_scene")
+    scene = periodic_scene(spheres, lo, period, max_per_leaf)
+    top = (lo + period).astype(np.float32)
+    if period[2] > 0:
+        z_top, length = top[2], period[2]
+    else:                                  # z open: the spheres' own extent
+        smin, smax = min_max_vec4(spheres)
+        z_top = np.float32(smax[2] + smax[3])
+        length = np.float32(z_top - (smin[2] - smax[3]))
+    camera = (np.float32((lo[0] + top[0]) / 2.), np.float32((lo[1] + top[1]) / 2.), z_top)
+    rays = orthographic_projection_rays(n_side, n_side, camera, (camera[0], camera[1], z_top - length),
+                                        (0.0, 1.0, 0.0), period[1], length, device=spheres.device)
+    out = trace_cumulative_periodic_sph(rays, scene)
+    return out.view(n_side, n_side), scene, rays
+
+
+def project_sph(spheres, n_side, max_per_leaf=32, period=None, lo=None):
     """The projection of tests/project_gadget/project_gadget.cu:58-81: bounds with
     w = 0, build_tree, orthogonal_rays_z, trace_cumulative_sph.  Sorts spheres in place.
-    Returns (image [n_side, n_side] float32, tree, rays)."""
+    Returns (image [n_side, n_side] float32, tree, rays).
+    period=(Lx, Ly, Lz) (lo: the box origin, default 0): the map of a periodic box instead -- the
+    frame is the box's z face [lo, lo + L] in x and y (Lx == Ly), the rays look down -z from the top
+    face and span one period (Lz == 0: the spheres' extent), and what sticks in through the four
+    side faces is included (periodic_scene, trace_cumulative_periodic_sph).  spheres is NOT modified;
+    returns (image, scene, rays)."""
+    if period is not None:
+        return _project_periodic_sph(spheres, n_side, max_per_leaf, period, lo)
     lo, hi = min_max_vec4(spheres)
     lo[3] = 0.0; hi[3] = 0.0
     tree = Tree(len(spheres), max_per_leaf, device=spheres.device)

@@ -1,5 +1,6 @@
 // grace/detail/front_end.h -- what the shared API bodies under grace/detail/ (build_sph.h,
-// trace_sph.h, scan.h, sort.h, gen_rays.h, interpolate_sph.h, neighbours_sph.h, range_sph.h, fof_sph.h, pairs_sph.h) are written
+// trace_sph.h, scan.h, sort.h, gen_rays.h, interpolate_sph.h, neighbours_sph.h, range_sph.h, fof_sph.h, pairs_sph.h,
+// periodic_trace.h) are written
 // against.
 // The library has two C++ front ends over the C ABI of grace_hip.h: the drop-in set
 // grace/cuda/*.cuh (thrust::device_vector, hipcc) and the HIP-free mirror grace/grace.h

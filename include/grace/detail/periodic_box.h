@@ -13,4 +13,12 @@ struct PeriodicBox {
     float lx, ly, lz;
 };
 
+// A periodic box with its origin, for the periodic traces (grace/detail/periodic_trace.h): unlike the
+// point queries, which wrap a separation, a trace has to know where the faces are.  The box is
+// [ox, ox + lx] x [oy, oy + ly] x [oz, oz + lz]; a period of 0 leaves that axis open.
+struct PeriodicDomain {
+    float ox, oy, oz;
+    PeriodicBox period;
+};
+
 } // namespace grace

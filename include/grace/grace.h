@@ -205,6 +205,7 @@ template <typename T> inline const T* raw(const device_vector<T>& v) { return v.
 #include "grace/detail/range_sph.h"
 #include "grace/detail/fof_sph.h"
 #include "grace/detail/pairs_sph.h"
+#include "grace/detail/periodic_trace.h"
 
 namespace grace {
 

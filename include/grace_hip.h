@@ -1182,7 +1182,7 @@ grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int el
  * a period, and whatever the open counterpart refuses.  (The period is checked first by the range
  * queries, friends-of-friends, the neighbours and the interpolation, after the edges by the pair
  * counts.)  Zero points or spheres: as the open counterpart, after the period's check.
- * Not provided: periodic ray traces; a box origin (none is needed); radii above half a period
+ * Periodic ray traces: the next block.  Not provided: a box origin (none is needed); radii above half a period
  * (more than one image of a centre in range, or of a sphere around a point). */
 grace_status grace_range_counts_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
                                             const float* d_radii, float radius,
@@ -1232,6 +1232,79 @@ grace_status grace_interpolate_grid_periodic_f4(const float* h_origin3, const fl
                                                 const float* d_weights, int n_channels,
                                                 float* d_out, int* d_counts, const float* h_period3,
                                                 grace_stream stream);
+
+/* ---- Periodic boxes for traces: sphere images, ray segments, folded results (an extension the
+ * reference lacks)
+ * The periodic trace is DEFINED as the open trace (grace_trace_hitcounts_f4, grace_trace_cumulative_f4,
+ * grace_trace_cumulative_weighted_f4: trace_sph.cuh:58-110, unchanged) of a stated set of ray SEGMENTS
+ * over a stated set of sphere IMAGES, folded back per ray.  The functions below make the two sets and
+ * fold; the front ends (grace::periodic_scene_sph, Python periodic_scene) call the open traces in
+ * between.  The definition is exact because sphere_hit (generic/intersect.h) owns a hit by the point
+ * of closest approach -- a pair hits iff b2 < w^2 and 0 <= dot < length -- so segments that tile
+ * [0, length) count every lattice image of a sphere exactly once, also one that straddles a cut.
+ *
+ * Box: h_lo3 and h_period3 are HOST arrays of three floats, the box origin lo and the periods L, read
+ * at call time.  L_k == 0 leaves axis k open.  A negative or non-finite period, a non-finite origin or
+ * a NULL array: GRACE_INVALID_ARGUMENT, nothing enqueued.  Unlike the point queries, traces need lo.
+ *
+ * Images (fp32, every operation rounded, none fused).  Sphere i = {x, H} gets, per periodic axis k,
+ * bit k of its crossing code if fl(x_k - H) < lo_k -- its image is at fl(x_k + L_k) -- or otherwise if
+ * fl(x_k + H) > fl(lo_k + L_k) -- its image is at fl(x_k - L_k).  It is emitted 2^popcount(code) times:
+ * every subset of the crossing axes shifted, in ascending subset code, subset 0 being the sphere
+ * itself bit for bit; w is copied; output order is ascending (i, subset); d_source[j] = i.
+ * A centre outside [lo_k, fl(lo_k + L_k)] or H > fl(0.5 L_k) on a periodic axis sets the status word
+ * (GRACE_INVALID_ARGUMENT from grace_trace_status) and the sphere is emitted once, unshifted; so is,
+ * without the status word, a sphere with a non-finite member.  All axes open: images == spheres,
+ * source == identity.
+ * grace_periodic_image_counts_f4 writes d_counts[i], i < n; the caller scans them (n + 1 entries,
+ * the last one 0: grace_scan_exclusive_i32) and passes the offsets and arrays of offsets[n] float4 /
+ * int to grace_periodic_images_f4.  A row whose length is not the sphere's count sets the status
+ * word; nothing is written outside a row.  d_source is an int per image: the payload of
+ * grace_sort_pairs_u32 beside the images' keys, so that it follows the images into tree order.
+ *
+ * Segments (fp64 from the widened fp32 members, every operation rounded, none fused).  Ray {d, o, l}.
+ * Per periodic axis u = (o_k - lo_k) / L_k; the starting cell is c_k = floor(u) if d_k >= 0,
+ * ceil(u) - 1 if d_k < 0; open axes c_k = 0.  Cuts of axis k: for d_k > 0 the planes m = c_k + 1,
+ * c_k + 2, ...; for d_k < 0 the planes m = c_k, c_k - 1, ...; none for d_k == +-0;
+ * t = ((lo_k + m L_k) - o_k) / d_k, evaluated for each m, never accumulated; a cut is kept while t > 0
+ * and t < l (the first plane that fails ends the axis).  All cuts of the three axes are ordered by
+ * (t, axis); equal t on two axes gives two cuts and a zero-length segment, which can hit nothing.  The
+ * segments are [0, t_1), [t_1, t_2), ..., [t_n, l); segment j is the Ray with the ray's direction bit
+ * for bit, origin fl32((o_k + t_j d_k) - cell_k L_k) -- cell the running cell: c, plus sign(d_k) per
+ * cut on k passed -- and length fl32(t_{j+1} - t_j) (t_0 = 0, t_{n+1} = l).  A ray without cuts in
+ * cell 0 is its own single segment bit for bit.  A ray with a non-finite member, or with more than
+ * 65536 segments, is emitted as itself, once; the second case also sets the status word.
+ * grace_periodic_segment_counts / grace_periodic_segments: counts, the caller's scan, fill, as for the
+ * images; d_segments holds offsets[n_rays] Rays.  The count is O(1) per axis (a closed form corrected
+ * against the predicate above: exact while |o - lo| / L stays below 2^40), the fill a three-axis walk
+ * that stops at the row's end; no loop runs more than 65536 times whatever the inputs hold.
+ *
+ * Results.  With s over a ray's segments (ascending) and the open traces run on (segments, images):
+ * hit_counts_periodic[r] = sum of the segments' hit counts (grace_periodic_fold_i32);
+ * cumulated_periodic[r, c] = the fp32 running sum, from 0, of the segments' (weighted) column
+ * densities (grace_periodic_fold_f32: d_values [n_segments * n_channels], d_out [n_rays * n_channels],
+ * rows of d_offsets longer than 65536 are cut there).  An image carries the weight row of its source:
+ * grace_periodic_gather_rows_f32 writes d_out[j * n_channels + c] = d_rows[d_source[j] * n_channels + c]
+ * (1 <= n_channels <= 64).  Open boxes, or a box much larger than the scene and the rays (no sphere
+ * crosses a face, every ray stays in cell 0), give the open outputs bit for bit.
+ * Not provided: the ordered traces (emission-absorption, deposits, spectra: the optical depth would
+ * have to be carried across segments), per-hit outputs, double4 spheres, H > L / 2. */
+grace_status grace_periodic_image_counts_f4(const float* d_spheres, size_t n, const float* h_lo3,
+                                            const float* h_period3, int* d_counts, grace_stream stream);
+grace_status grace_periodic_images_f4(const float* d_spheres, size_t n, const float* h_lo3,
+                                      const float* h_period3, const int* d_offsets, float* d_images,
+                                      int* d_source, grace_stream stream);
+grace_status grace_periodic_segment_counts(const void* d_rays, size_t n_rays, const float* h_lo3,
+                                           const float* h_period3, int* d_counts, grace_stream stream);
+grace_status grace_periodic_segments(const void* d_rays, size_t n_rays, const float* h_lo3,
+                                     const float* h_period3, const int* d_offsets, void* d_segments,
+                                     grace_stream stream);
+grace_status grace_periodic_fold_f32(const float* d_values, const int* d_offsets, size_t n_rays, int n_channels,
+                                     float* d_out, grace_stream stream);
+grace_status grace_periodic_fold_i32(const int* d_values, const int* d_offsets, size_t n_rays, int n_channels,
+                                     int* d_out, grace_stream stream);
+grace_status grace_periodic_gather_rows_f32(const float* d_rows, const int* d_source, size_t n_images,
+                                            int n_channels, float* d_out, grace_stream stream);
 
 #ifdef __cplusplus
 }
