@@ -79,8 +79,10 @@ __device__ __forceinline__ long long deposit_units(const double dep, const doubl
     return static_cast<long long>(s);
 }
 
-// TIER 0 / 1: arrays of CAP hits in LDS; TIER 2: in place in global memory.
-template <int T, int CAP, int TIER>
+// TIER 0 / 1: arrays of CAP hits in LDS; TIER 2: in place in global memory.  GROUPED: the ray's hits
+// are those of all its segments, ordered segment first, and X holds the caller's particle of every
+// hit (ordered_core.hpp): absorption and acc are indexed by it, luminosity and transmitted by the ray.
+template <int T, int CAP, int TIER, bool GROUPED>
 __global__ __launch_bounds__(T) void deposit_composite_kernel(const DepArgs a)
 {
     constexpr int WAVES = T / 64;
@@ -93,7 +95,8 @@ __global__ __launch_bounds__(T) void deposit_composite_kernel(const DepArgs a)
     int* X;
     int n;
     size_t r;
-    if (!ordered_load_sort<T, CAP, TIER>(a, s_d, s_x, s_i, D, X, I, n, r)) return;
+    OrdSpan span;
+    if (!ordered_load_sort<T, CAP, TIER, GROUPED>(a, s_d, s_x, s_i, D, X, I, n, r, span)) return;
 
     const int C = a.channels;
     for (int c0 = 0; c0 < C; c0 += 4) {
@@ -187,33 +190,46 @@ __global__ __launch_bounds__(256) void deposit_finish_kernel(const long long* __
         deposit[i] = static_cast<double>(acc[i]) * quantum[i % C];
 }
 
-} // namespace
-} // namespace grace_hip
+template <bool GROUPED>
+grace_status deposit_launch(const DepArgs& a, const int nb, const bool any_block, const bool any_global,
+                            const hipStream_t stream)
+{
+    deposit_composite_kernel<64, ORD_WAVE_MAX, 0, GROUPED><<<nb, 64, 0, stream>>>(a);
+    GRACE_CHECK_LAUNCH();
+    if (any_block) {
+        deposit_composite_kernel<256, ORD_BLOCK_MAX, 1, GROUPED><<<nb, 256, 0, stream>>>(a);
+        GRACE_CHECK_LAUNCH();
+    }
+    if (any_global) {
+        deposit_composite_kernel<256, 0, 2, GROUPED><<<nb, 256, 0, stream>>>(a);
+        GRACE_CHECK_LAUNCH();
+    }
+    return GRACE_OK;
+}
 
-using namespace grace_hip;
-
-extern "C" {
-
-grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
-                                               size_t n_spheres, const int* d_nodes, size_t n_nodes,
-                                               const int* d_leaves, const int* d_root,
-                                               const float* d_luminosity, const float* d_absorption,
-                                               int n_channels, double* d_deposit, float* d_transmitted,
-                                               double* d_quantum, grace_stream stream_)
+// The open call (grouped == null: the traced rays are the rays, the particles the spheres) and the
+// periodic one (the traced rays are the n_traced segments of n_rays rays, the spheres the images of
+// n_particles caller particles).  n_rays sets the quantum, n_particles sizes the deposit.
+grace_status absorption_deposit(const void* d_traced, size_t n_traced, const float* d_spheres, size_t n_spheres,
+                                const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                                size_t n_rays, size_t n_particles, const float* d_luminosity,
+                                const float* d_absorption, int n_channels, double* d_deposit, float* d_transmitted,
+                                double* d_quantum, grace_stream stream_, const OrdGroups* grouped)
 {
     GRACE_REQUIRE(n_channels >= 1 && n_channels <= DEP_MAX_CHANNELS, "trace_absorption_deposit: channels must be 1..64");
     GRACE_REQUIRE(d_deposit, "trace_absorption_deposit: null output");
-    GRACE_REQUIRE(n_spheres < (size_t(1) << 31), "trace_absorption_deposit: bad primitive count");
+    GRACE_REQUIRE(n_spheres < (size_t(1) << 31) && n_particles < (size_t(1) << 31),
+                  "trace_absorption_deposit: bad primitive count");
     const hipStream_t stream = as_stream(stream_);
-    const size_t C = size_t(n_channels), n_acc = n_spheres * C;
+    const size_t C = size_t(n_channels), n_acc = n_particles * C;
     if (n_rays == 0) {      // nothing is absorbed: unlike the per-ray outputs, the deposit is defined
         if (n_acc) GRACE_TRY_HIP(hipMemsetAsync(d_deposit, 0, n_acc * sizeof(double), stream));
         if (d_quantum) GRACE_TRY_HIP(hipMemsetAsync(d_quantum, 0, C * sizeof(double), stream));
         return GRACE_OK;
     }
     GRACE_REQUIRE(d_luminosity && d_absorption, "trace_absorption_deposit: null luminosity or absorption");
-    GRACE_REQUIRE(d_rays && d_spheres && d_nodes && d_leaves && d_root, "trace_absorption_deposit: null pointer");
-    GRACE_REQUIRE(n_rays < (size_t(1) << 31), "trace_absorption_deposit: bad ray count");
+    GRACE_REQUIRE(d_traced && d_spheres && d_nodes && d_leaves && d_root, "trace_absorption_deposit: null pointer");
+    GRACE_REQUIRE(n_rays < (size_t(1) << 31) && n_traced < (size_t(1) << 31), "trace_absorption_deposit: bad ray count");
     GRACE_REQUIRE(n_nodes >= 1 && n_nodes < (size_t(1) << 30), "trace_absorption_deposit: bad node count");
     GRACE_REQUIRE(n_spheres > 0, "trace_absorption_deposit: bad primitive count");
     int b = 0;                                          // ceil(log2(n_rays))
@@ -228,7 +244,7 @@ grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays
     a.transmitted = d_transmitted;
     FrameGuard frame;
     GRACE_TRY(ordered_run(
-        frame, d_rays, n_rays, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, front_bytes, stream,
+        frame, d_traced, n_traced, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, front_bytes, stream,
         [&](char* front) -> grace_status {
             a.acc = reinterpret_cast<long long*>(front);
             uint32_t* max_bits = reinterpret_cast<uint32_t*>(front + off_max);
@@ -243,21 +259,49 @@ grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays
         },
         [&](const OrdBatch& batch, const int nb, const bool any_block, const bool any_global) -> grace_status {
             static_cast<OrdBatch&>(a) = batch;
-            deposit_composite_kernel<64, ORD_WAVE_MAX, 0><<<nb, 64, 0, stream>>>(a);
-            GRACE_CHECK_LAUNCH();
-            if (any_block) {
-                deposit_composite_kernel<256, ORD_BLOCK_MAX, 1><<<nb, 256, 0, stream>>>(a);
-                GRACE_CHECK_LAUNCH();
-            }
-            if (any_global) {
-                deposit_composite_kernel<256, 0, 2><<<nb, 256, 0, stream>>>(a);
-                GRACE_CHECK_LAUNCH();
-            }
-            return GRACE_OK;
-        }));
+            return grouped ? deposit_launch<true>(a, nb, any_block, any_global, stream)
+                           : deposit_launch<false>(a, nb, any_block, any_global, stream);
+        },
+        grouped));
     deposit_finish_kernel<<<stream_grid(n_acc, 256), 256, 0, stream>>>(a.acc, a.quantum, n_acc, n_channels, d_deposit);
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
+}
+
+} // namespace
+} // namespace grace_hip
+
+using namespace grace_hip;
+
+extern "C" {
+
+grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                               size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                               const int* d_leaves, const int* d_root,
+                                               const float* d_luminosity, const float* d_absorption,
+                                               int n_channels, double* d_deposit, float* d_transmitted,
+                                               double* d_quantum, grace_stream stream_)
+{
+    return absorption_deposit(d_rays, n_rays, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, n_rays,
+                              n_spheres, d_luminosity, d_absorption, n_channels, d_deposit, d_transmitted, d_quantum,
+                              stream_, nullptr);
+}
+
+grace_status grace_trace_absorption_deposit_periodic_f4(const void* d_segments, size_t n_segments,
+                                                        const float* d_images, size_t n_images, const int* d_nodes,
+                                                        size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                        const int* d_segment_offsets, size_t n_rays,
+                                                        const int* d_source, size_t n_sources,
+                                                        const float* d_luminosity, const float* d_absorption,
+                                                        int n_channels, double* d_deposit, float* d_transmitted,
+                                                        double* d_quantum, grace_stream stream_)
+{
+    OrdGroups g = {};
+    if (n_rays != 0)
+        GRACE_TRY(ordered_groups(g, d_segments, n_segments, d_segment_offsets, n_rays, d_source, n_sources, nullptr));
+    return absorption_deposit(d_segments, n_segments, d_images, n_images, d_nodes, n_nodes, d_leaves, d_root, n_rays,
+                              n_sources, d_luminosity, d_absorption, n_channels, d_deposit, d_transmitted, d_quantum,
+                              stream_, &g);
 }
 
 } // extern "C"

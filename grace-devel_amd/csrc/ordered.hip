@@ -27,8 +27,10 @@ struct OrdArgs : OrdBatch {
     float* out; float* tau;
 };
 
-// TIER 0 / 1: arrays of CAP hits in LDS; TIER 2: in place in global memory.
-template <int T, int CAP, int TIER>
+// TIER 0 / 1: arrays of CAP hits in LDS; TIER 2: in place in global memory.  GROUPED: the ray's hits
+// are those of all its segments, ordered segment first (ordered_core.hpp); what follows the sort is
+// the same code.
+template <int T, int CAP, int TIER, bool GROUPED>
 __global__ __launch_bounds__(T) void ordered_composite_kernel(const OrdArgs a)
 {
     constexpr int WAVES = T / 64;
@@ -42,7 +44,8 @@ __global__ __launch_bounds__(T) void ordered_composite_kernel(const OrdArgs a)
     int* X;
     int n;
     size_t r;
-    if (!ordered_load_sort<T, CAP, TIER>(a, s_d, s_x, s_i, D, X, I, n, r)) return;
+    OrdSpan span;
+    if (!ordered_load_sort<T, CAP, TIER, GROUPED>(a, s_d, s_x, s_i, D, X, I, n, r, span)) return;
 
 
     // optical depths in front of every hit; the hit's factor replaces its (distance, integral) words
@@ -100,7 +103,9 @@ __global__ __launch_bounds__(T) void ordered_composite_kernel(const OrdArgs a)
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o);
-        if (WAVES > 1) {
+        // (GROUPED: through LDS in the wave tier too -- the same values; the open wave tier's select
+        // below becomes an indexed read of acc in scratch, 48 bytes a lane, which it keeps)
+        if (WAVES > 1 || GROUPED) {
             if (lane == 0)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) s_red[wave][j] = acc[j];
@@ -122,19 +127,29 @@ __global__ __launch_bounds__(T) void ordered_composite_kernel(const OrdArgs a)
     }
 }
 
-} // namespace
-} // namespace grace_hip
+template <bool GROUPED>
+grace_status composite_launch(const OrdArgs& a, const int nb, const bool any_block, const bool any_global,
+                              const hipStream_t stream)
+{
+    ordered_composite_kernel<64, ORD_WAVE_MAX, 0, GROUPED><<<nb, 64, 0, stream>>>(a);
+    GRACE_CHECK_LAUNCH();
+    if (any_block) {
+        ordered_composite_kernel<256, ORD_BLOCK_MAX, 1, GROUPED><<<nb, 256, 0, stream>>>(a);
+        GRACE_CHECK_LAUNCH();
+    }
+    if (any_global) {
+        ordered_composite_kernel<256, 0, 2, GROUPED><<<nb, 256, 0, stream>>>(a);
+        GRACE_CHECK_LAUNCH();
+    }
+    return GRACE_OK;
+}
 
-using namespace grace_hip;
-
-extern "C" {
-
-grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
-                                                size_t n_spheres, const int* d_nodes, size_t n_nodes,
-                                                const int* d_leaves, const int* d_root,
-                                                const float* d_emission, int n_channels,
-                                                const float* d_absorption, float* d_out, float* d_tau,
-                                                grace_stream stream_)
+// The open call (grouped == null) and the periodic one: d_rays are then the segments, the weights
+// are indexed by source.
+grace_status emission_absorption(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                                 const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                                 const float* d_emission, int n_channels, const float* d_absorption, float* d_out,
+                                 float* d_tau, grace_stream stream_, const OrdGroups* grouped)
 {
     GRACE_REQUIRE(n_channels >= 1 && n_channels <= 64, "trace_emission_absorption: channels must be 1..64");
     if (n_rays == 0) return GRACE_OK;   // an empty shard of a sharded batch: nothing to trace
@@ -154,20 +169,45 @@ grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_ray
         [](char*) -> grace_status { return GRACE_OK; },
         [&](const OrdBatch& batch, const int nb, const bool any_block, const bool any_global) -> grace_status {
             static_cast<OrdBatch&>(a) = batch;
-            ordered_composite_kernel<64, ORD_WAVE_MAX, 0><<<nb, 64, 0, stream>>>(a);
-            GRACE_CHECK_LAUNCH();
-            if (any_block) {
-                ordered_composite_kernel<256, ORD_BLOCK_MAX, 1><<<nb, 256, 0, stream>>>(a);
-                GRACE_CHECK_LAUNCH();
-            }
-            if (any_global) {
-                ordered_composite_kernel<256, 0, 2><<<nb, 256, 0, stream>>>(a);
-                GRACE_CHECK_LAUNCH();
-            }
-            return GRACE_OK;
-        });
+            return grouped ? composite_launch<true>(a, nb, any_block, any_global, stream)
+                           : composite_launch<false>(a, nb, any_block, any_global, stream);
+        },
+        grouped);
 }
 
+} // namespace
+} // namespace grace_hip
+
+using namespace grace_hip;
+
+extern "C" {
+
+grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
+                                                size_t n_spheres, const int* d_nodes, size_t n_nodes,
+                                                const int* d_leaves, const int* d_root,
+                                                const float* d_emission, int n_channels,
+                                                const float* d_absorption, float* d_out, float* d_tau,
+                                                grace_stream stream_)
+{
+    return emission_absorption(d_rays, n_rays, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_emission,
+                               n_channels, d_absorption, d_out, d_tau, stream_, nullptr);
+}
+
+grace_status grace_trace_emission_absorption_periodic_f4(const void* d_segments, size_t n_segments,
+                                                         const float* d_images, size_t n_images, const int* d_nodes,
+                                                         size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                         const int* d_segment_offsets, size_t n_rays,
+                                                         const int* d_source, size_t n_sources,
+                                                         const float* d_emission, int n_channels,
+                                                         const float* d_absorption, float* d_out, float* d_tau,
+                                                         grace_stream stream_)
+{
+    if (n_rays == 0) return GRACE_OK;
+    OrdGroups g;
+    GRACE_TRY(ordered_groups(g, d_segments, n_segments, d_segment_offsets, n_rays, d_source, n_sources, nullptr));
+    return emission_absorption(d_segments, n_segments, d_images, n_images, d_nodes, n_nodes, d_leaves, d_root,
+                               d_emission, n_channels, d_absorption, d_out, d_tau, stream_, &g);
+}
 
 grace_status grace_trace_set_ordered_budget(size_t bytes)
 {

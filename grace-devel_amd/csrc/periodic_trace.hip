@@ -2,12 +2,15 @@
 // trace into an open one.  The periodic trace is DEFINED as the open trace of a stated set of ray
 // segments over a stated set of sphere images (include/grace_hip.h, "Periodic boxes for traces");
 // this file makes the two sets and folds the per-segment results back per ray.  The traversal, its
-// caches and its kernels are not touched: the front ends call the open traces in between.
+// caches and its kernels are not touched: the front ends call the open traces in between.  (The
+// depth-ordered traces are no fold; their periodic form is in ordered_core.hpp.)
 //
 //   images    one thread per sphere: the crossing code (which faces the sphere sticks out of), then
 //             2^popcount(code) copies, every subset of the crossing axes shifted by one period;
 //   segments  one thread per ray: the ray cut where it crosses a face of the lattice of boxes, every
 //             piece moved back into the box.  fp64 from the widened fp32 members, nothing fused;
+//   starts    one thread per ray: every segment's starting parameter along its ray, from the same walk
+//             (the periodic ordered traces' spectra need a hit's distance from the ray's origin);
 //   fold      per ray and channel, the running sum of its segments' results in segment order;
 //   gather    an image's weight row is its source's.
 //
@@ -184,26 +187,12 @@ __global__ __launch_bounds__(PT_BLOCK) void segment_counts_kernel(const float* _
     counts[r] = p.total;
 }
 
-// A three-axis DDA over the cuts, ordered by (t, axis); it stops at the row's end.
-__global__ __launch_bounds__(PT_BLOCK) void segments_kernel(const float* __restrict__ rays, const int n_rays,
-                                                            const Box b, const int* __restrict__ offsets,
-                                                            float* __restrict__ segments, int* __restrict__ status)
+// A three-axis DDA over the cuts, ordered by (t, axis), of a ray that is not emitted as itself:
+// emit(j, t, t_next, cell) for segment j = 0 .. n - 1, [t, t_next) in the running cell.  Both fills
+// walk through here, so a segment and its starting parameter come from the same arithmetic.
+template <typename Emit>
+__device__ __forceinline__ void walk_segments(const SegmentPlan& p, const int n, Emit emit)
 {
-    const int r = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (r >= n_rays) return;
-    const float* ray = rays + size_t(r) * RAY_FLOATS;
-    const SegmentPlan p = segment_plan(ray, b);
-    const int row = offsets[r], row_end = offsets[r + 1];
-    if (p.refused || row_end - row != p.total) atomicMax(status, int(GRACE_INVALID_ARGUMENT));
-    if (row < 0 || row >= row_end) return;
-    const bool plain = !p.finite || p.refused
-                       || (p.total == 1 && p.cell[0] == 0.0 && p.cell[1] == 0.0 && p.cell[2] == 0.0);
-    if (plain) {                                               // the ray itself, bit for bit
-        float* out = segments + size_t(row) * RAY_FLOATS;
-#pragma unroll
-        for (int c = 0; c < RAY_FLOATS; ++c) out[c] = ray[c];
-        return;
-    }
     const double inf = double(INFINITY);
     int used[3] = { 0, 0, 0 };
     double next[3], cell[3];                                   // the running cell; p.cell stays the starting one
@@ -213,7 +202,6 @@ __global__ __launch_bounds__(PT_BLOCK) void segments_kernel(const float* __restr
         cell[k] = p.cell[k];
     }
     double t = 0.0;
-    const int n = min(p.total, row_end - row);                 // never outside the row; <= MAX_SEGMENTS
     for (int j = 0; j < n; ++j) {
         int axis = -1;
         double t_next = p.len;
@@ -223,13 +211,7 @@ __global__ __launch_bounds__(PT_BLOCK) void segments_kernel(const float* __restr
             if (next[2] < next[axis]) axis = 2;
             t_next = next[axis];
         }
-        float* out = segments + size_t(row + j) * RAY_FLOATS;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            out[k] = ray[k];
-            out[3 + k] = float(p.o[k] + t * p.d[k] - cell[k] * p.L[k]);
-        }
-        out[6] = float(t_next - t);
+        emit(j, t, t_next, cell);
         if (axis >= 0) {
             // (no dynamic indexing of the small arrays: they stay in registers)
 #pragma unroll
@@ -242,6 +224,59 @@ __global__ __launch_bounds__(PT_BLOCK) void segments_kernel(const float* __restr
             t = t_next;
         }
     }
+}
+
+// A ray emitted as itself, bit for bit: one with a non-finite member, a refused one, or one without
+// cuts in cell 0.
+__device__ __forceinline__ bool emitted_as_itself(const SegmentPlan& p)
+{
+    return !p.finite || p.refused || (p.total == 1 && p.cell[0] == 0.0 && p.cell[1] == 0.0 && p.cell[2] == 0.0);
+}
+
+// It stops at the row's end.
+__global__ __launch_bounds__(PT_BLOCK) void segments_kernel(const float* __restrict__ rays, const int n_rays,
+                                                            const Box b, const int* __restrict__ offsets,
+                                                            float* __restrict__ segments, int* __restrict__ status)
+{
+    const int r = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (r >= n_rays) return;
+    const float* ray = rays + size_t(r) * RAY_FLOATS;
+    const SegmentPlan p = segment_plan(ray, b);
+    const int row = offsets[r], row_end = offsets[r + 1];
+    if (p.refused || row_end - row != p.total) atomicMax(status, int(GRACE_INVALID_ARGUMENT));
+    if (row < 0 || row >= row_end) return;
+    if (emitted_as_itself(p)) {
+        float* out = segments + size_t(row) * RAY_FLOATS;
+#pragma unroll
+        for (int c = 0; c < RAY_FLOATS; ++c) out[c] = ray[c];
+        return;
+    }
+    const int n = min(p.total, row_end - row);                 // never outside the row; <= MAX_SEGMENTS
+    walk_segments(p, n, [&](const int j, const double t, const double t_next, const double (&cell)[3]) {
+        float* out = segments + size_t(row + j) * RAY_FLOATS;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            out[k] = ray[k];
+            out[3 + k] = float(p.o[k] + t * p.d[k] - cell[k] * p.L[k]);
+        }
+        out[6] = float(t_next - t);
+    });
+}
+
+// t0[s] of every segment: the t at which segments_kernel starts it; 0 for a ray emitted as itself.
+__global__ __launch_bounds__(PT_BLOCK) void segment_starts_kernel(const float* __restrict__ rays, const int n_rays,
+                                                                  const Box b, const int* __restrict__ offsets,
+                                                                  double* __restrict__ t0, int* __restrict__ status)
+{
+    const int r = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (r >= n_rays) return;
+    const SegmentPlan p = segment_plan(rays + size_t(r) * RAY_FLOATS, b);
+    const int row = offsets[r], row_end = offsets[r + 1];
+    if (p.refused || row_end - row != p.total) atomicMax(status, int(GRACE_INVALID_ARGUMENT));
+    if (row < 0 || row >= row_end) return;
+    if (emitted_as_itself(p)) { t0[row] = 0.0; return; }
+    const int n = min(p.total, row_end - row);                 // never outside the row; <= MAX_SEGMENTS
+    walk_segments(p, n, [&](const int j, const double t, const double, const double (&)[3]) { t0[row + j] = t; });
 }
 
 // ---- results -------------------------------------------------------------------------------------
@@ -390,6 +425,24 @@ grace_status grace_periodic_segments(const void* d_rays, size_t n_rays, const fl
     segments_kernel<<<ceil_div(n_rays, PT_BLOCK), PT_BLOCK, 0, st>>>(static_cast<const float*>(d_rays), int(n_rays), b,
                                                                      d_offsets, static_cast<float*>(d_segments),
                                                                      status);
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+grace_status grace_periodic_segment_starts(const void* d_rays, size_t n_rays, const float* h_lo3,
+                                           const float* h_period3, const int* d_offsets, double* d_t0,
+                                           grace_stream stream)
+{
+    Box b;
+    GRACE_TRY(make_box(b, h_lo3, h_period3));
+    GRACE_REQUIRE(n_rays < (size_t(1) << 31), "periodic_segment_starts: more than INT32_MAX rays");
+    if (n_rays == 0) return GRACE_OK;
+    GRACE_REQUIRE(d_rays && d_offsets && d_t0, "periodic_segment_starts: null pointer");
+    const hipStream_t st = as_stream(stream);
+    int* status = nullptr;
+    GRACE_TRY(status_word(&status, st));
+    segment_starts_kernel<<<ceil_div(n_rays, PT_BLOCK), PT_BLOCK, 0, st>>>(static_cast<const float*>(d_rays),
+                                                                           int(n_rays), b, d_offsets, d_t0, status);
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
 }

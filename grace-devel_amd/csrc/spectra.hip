@@ -45,7 +45,11 @@ struct SpecArgs : OrdBatch {
     float* column;              // [n_rays * C], or null
 };
 
-template <int T, int CAP, int TIER, int BINS>
+// GROUPED: the ray's hits are those of all its segments, ordered segment first, and X holds the
+// caller's particle of every hit (ordered_core.hpp); a.rays are the SEGMENTS.  The direction is the
+// ray's first segment's (every segment has the ray's, bit for bit), and hit k's distance from the
+// ray's origin is seg_t0[its segment] + its distance within the segment, in fp64.
+template <int T, int CAP, int TIER, int BINS, bool GROUPED>
 __global__ __launch_bounds__(T) void spectra_kernel(const SpecArgs a)
 {
     constexpr int WAVES = T / 64;
@@ -61,11 +65,15 @@ __global__ __launch_bounds__(T) void spectra_kernel(const SpecArgs a)
     int* X;
     int n;
     size_t r;
-    if (!ordered_load_sort<T, CAP, TIER>(a, s_d, s_x, s_i, D, X, I, n, r)) return;
+    OrdSpan span;
+    if (!ordered_load_sort<T, CAP, TIER, GROUPED>(a, s_d, s_x, s_i, D, X, I, n, r, span)) return;
 
     const int C = a.channels, nb = a.n_bins;
-    const float* ray = reinterpret_cast<const float*>(a.rays + r * 28);
-    const double dx = static_cast<double>(ray[0]), dy = static_cast<double>(ray[1]), dz = static_cast<double>(ray[2]);
+    double dx = 0.0, dy = 0.0, dz = 0.0;
+    if (!GROUPED || span.g0 < span.g1) {        // (a ray without segments has no hits either)
+        const float* ray = reinterpret_cast<const float*>(a.rays + (GROUPED ? size_t(span.g0) : r) * 28);
+        dx = static_cast<double>(ray[0]); dy = static_cast<double>(ray[1]); dz = static_cast<double>(ray[2]);
+    }
     const double v0 = a.v0, dv = a.dv;
     const int per = (nb + WAVES - 1) / WAVES;                       // the wave's bins: [j0, j1)
     const int j0 = wave * per < nb ? wave * per : nb, j1 = j0 + per < nb ? j0 + per : nb;
@@ -79,7 +87,8 @@ __global__ __launch_bounds__(T) void spectra_kernel(const SpecArgs a)
             if (tid < cn) {
                 const int k = base + tid, x = X[k];
                 const double Ik = static_cast<double>(__uint_as_float(I[k]));
-                const double d = static_cast<double>(dist_from_key(D[k]));
+                double d = static_cast<double>(dist_from_key(D[k]));
+                if constexpr (GROUPED) d = a.seg_t0[ordered_segment_of(a, span, k)] + d;
                 const float* vel = a.velocity + size_t(x) * 3;
                 const double v = a.hubble * d + ((static_cast<double>(vel[0]) * dx + static_cast<double>(vel[1]) * dy)
                                                  + static_cast<double>(vel[2]) * dz);
@@ -140,35 +149,39 @@ __global__ __launch_bounds__(T) void spectra_kernel(const SpecArgs a)
     }
 }
 
-template <int BINS>
+template <int BINS, bool GROUPED>
 grace_status spectra_launch(const SpecArgs& a, const int nb, const bool any_block, const bool any_global,
                             const hipStream_t stream)
 {
-    spectra_kernel<64, ORD_WAVE_MAX, 0, BINS><<<nb, 64, 0, stream>>>(a);
+    spectra_kernel<64, ORD_WAVE_MAX, 0, BINS, GROUPED><<<nb, 64, 0, stream>>>(a);
     GRACE_CHECK_LAUNCH();
     if (any_block) {
-        spectra_kernel<256, ORD_BLOCK_MAX, 1, BINS><<<nb, 256, 0, stream>>>(a);
+        spectra_kernel<256, ORD_BLOCK_MAX, 1, BINS, GROUPED><<<nb, 256, 0, stream>>>(a);
         GRACE_CHECK_LAUNCH();
     }
     if (any_global) {
-        spectra_kernel<256, 0, 2, BINS><<<nb, 256, 0, stream>>>(a);
+        spectra_kernel<256, 0, 2, BINS, GROUPED><<<nb, 256, 0, stream>>>(a);
         GRACE_CHECK_LAUNCH();
     }
     return GRACE_OK;
 }
 
-} // namespace
-} // namespace grace_hip
+template <bool GROUPED>
+grace_status spectra_launch_bins(const SpecArgs& a, const int nb, const bool any_block, const bool any_global,
+                                 const hipStream_t stream)
+{
+    return a.n_bins <= SPEC_BINS_SMALL ? spectra_launch<SPEC_BINS_SMALL, GROUPED>(a, nb, any_block, any_global, stream)
+         : a.n_bins <= SPEC_BINS_MID ? spectra_launch<SPEC_BINS_MID, GROUPED>(a, nb, any_block, any_global, stream)
+                                     : spectra_launch<SPEC_MAX_BINS, GROUPED>(a, nb, any_block, any_global, stream);
+}
 
-using namespace grace_hip;
-
-extern "C" {
-
-grace_status grace_trace_spectra_f4(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
-                                    const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
-                                    const float* d_amount, const float* d_width, const float* d_velocity,
-                                    int n_channels, const grace_spectrum_grid* grid, float* d_tau, float* d_column,
-                                    grace_stream stream_)
+// The open call (grouped == null) and the periodic one: d_rays are then the segments, the
+// per-particle arrays are indexed by source, the outputs by ray.
+grace_status spectra(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                     const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                     const float* d_amount, const float* d_width, const float* d_velocity,
+                     int n_channels, const grace_spectrum_grid* grid, float* d_tau, float* d_column,
+                     grace_stream stream_, const OrdGroups* grouped)
 {
     GRACE_REQUIRE(n_channels >= 1 && n_channels <= SPEC_MAX_CHANNELS, "trace_spectra: channels must be 1..16");
     GRACE_REQUIRE(grid, "trace_spectra: null grid");
@@ -197,11 +210,45 @@ grace_status grace_trace_spectra_f4(const void* d_rays, size_t n_rays, const flo
         [](char*) -> grace_status { return GRACE_OK; },
         [&](const OrdBatch& batch, const int nb, const bool any_block, const bool any_global) -> grace_status {
             static_cast<OrdBatch&>(a) = batch;
-            return a.n_bins <= SPEC_BINS_SMALL ? spectra_launch<SPEC_BINS_SMALL>(a, nb, any_block, any_global, stream)
-                 : a.n_bins <= SPEC_BINS_MID ? spectra_launch<SPEC_BINS_MID>(a, nb, any_block, any_global, stream)
-                                             : spectra_launch<SPEC_MAX_BINS>(a, nb, any_block, any_global, stream);
-        }));
+            return grouped ? spectra_launch_bins<true>(a, nb, any_block, any_global, stream)
+                           : spectra_launch_bins<false>(a, nb, any_block, any_global, stream);
+        },
+        grouped));
     return GRACE_OK;
+}
+
+} // namespace
+} // namespace grace_hip
+
+using namespace grace_hip;
+
+extern "C" {
+
+grace_status grace_trace_spectra_f4(const void* d_rays, size_t n_rays, const float* d_spheres, size_t n_spheres,
+                                    const int* d_nodes, size_t n_nodes, const int* d_leaves, const int* d_root,
+                                    const float* d_amount, const float* d_width, const float* d_velocity,
+                                    int n_channels, const grace_spectrum_grid* grid, float* d_tau, float* d_column,
+                                    grace_stream stream_)
+{
+    return spectra(d_rays, n_rays, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_amount, d_width,
+                   d_velocity, n_channels, grid, d_tau, d_column, stream_, nullptr);
+}
+
+grace_status grace_trace_spectra_periodic_f4(const void* d_segments, size_t n_segments, const float* d_images,
+                                             size_t n_images, const int* d_nodes, size_t n_nodes,
+                                             const int* d_leaves, const int* d_root, const int* d_segment_offsets,
+                                             size_t n_rays, const int* d_source, size_t n_sources,
+                                             const double* d_segment_t0, const float* d_amount, const float* d_width,
+                                             const float* d_velocity, int n_channels,
+                                             const grace_spectrum_grid* grid, float* d_tau, float* d_column,
+                                             grace_stream stream_)
+{
+    if (n_rays == 0) return GRACE_OK;
+    GRACE_REQUIRE(d_segment_t0, "trace_spectra_periodic: null segment starts");
+    OrdGroups g;
+    GRACE_TRY(ordered_groups(g, d_segments, n_segments, d_segment_offsets, n_rays, d_source, n_sources, d_segment_t0));
+    return spectra(d_segments, n_segments, d_images, n_images, d_nodes, n_nodes, d_leaves, d_root, d_amount, d_width,
+                   d_velocity, n_channels, grid, d_tau, d_column, stream_, &g);
 }
 
 } // extern "C"

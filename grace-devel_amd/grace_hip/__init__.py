@@ -1567,13 +1567,14 @@ def periodic_sphere_images(spheres, lo, period):
     return images, source, offsets
 
 
-def periodic_ray_segments(rays, lo, period):
+def periodic_ray_segments(rays, lo, period, want_t0=False):
     """The segments of rays in a periodic box: every ray cut where it crosses a face of the lattice of
     boxes, every piece moved back into the box (fp64 arithmetic as stated in include/grace_hip.h).  Any
     number of rays.  A ray with more than 65536 segments sets the status word and is emitted as itself.
     Returns (segments float32 [total, 7], offsets int32 [n_rays + 1]): ray r's segments are rows
-    [offsets[r], offsets[r + 1]), in order along the ray.  Synchronises to read the total (ValueError
-    above INT32_MAX, before any fill)."""
+    [offsets[r], offsets[r + 1]), in order along the ray.  want_t0: a third value, float64 [total], every
+    segment's starting parameter along its ray (0 for a ray emitted as itself), from the same walk as the
+    segments.  Synchronises to read the total (ValueError above INT32_MAX, before any fill)."""
     _rays(rays)
     lo, period = _box(lo, period)
     n = len(rays)
@@ -1585,15 +1586,23 @@ def periodic_ray_segments(rays, lo, period):
     if total:
         _check(_lib.grace_periodic_segments(_ptr(rays), C.c_size_t(n), *_box_args(lo, period),
                                             _ptr(offsets), _ptr(segments), _stream()))
-    return segments, offsets
+    if not want_t0:
+        return segments, offsets
+    t0 = torch.empty(total, dtype=torch.float64, device=rays.device)
+    if total:
+        _check(_lib.grace_periodic_segment_starts(_ptr(rays), C.c_size_t(n), *_box_args(lo, period),
+                                                  _ptr(offsets), _ptr(t0), _stream()))
+    return segments, offsets, t0
 
 
 class PeriodicScene:
     """What periodic_scene returns: spheres (the images, in tree order), source (int32 per image: the
-    index of its sphere in the caller's array as passed), tree, lo and period (host float32 [3])."""
+    index of its sphere in the caller's array as passed), tree, lo and period (host float32 [3]), and
+    n_sources, the number of spheres in the caller's array."""
 
-    def __init__(self, spheres, source, tree, lo, period):
+    def __init__(self, spheres, source, tree, lo, period, n_sources=None):
         self.spheres, self.source, self.tree, self.lo, self.period = spheres, source, tree, lo, period
+        self.n_sources = n_sources
 
 
 def periodic_scene(spheres, lo, period, max_per_leaf=32, check=True):
@@ -1615,7 +1624,7 @@ def periodic_scene(spheres, lo, period, max_per_leaf=32, check=True):
         deltas = torch.empty(len(images) + 1, dtype=torch.float32, device=images.device)
         euclidean_deltas_sph(images, deltas)
         ALBVH_sph(images, deltas, tree)
-    return PeriodicScene(images, source, tree, lo, period)
+    return PeriodicScene(images, source, tree, lo, period, len(spheres))
 
 
 def _periodic_trace(rays, scene, n_ch, dtype, out, shape, trace):
@@ -1678,6 +1687,149 @@ def trace_cumulative_weighted_periodic_sph(rays, scene, weights, out=None, check
     if check:
         trace_status()
     return out
+
+
+# The depth-ordered traces in a periodic box (include/grace_hip.h, "Periodic boxes for traces", "Ordered
+# traces").  No fold defines them: they are the open call's composite applied per ray to the hits of all
+# the ray's segments over the scene's images, ordered by (segment along the ray, fp32 distance within the
+# segment, image index), every hit standing for its source -- the caller's particle.
+def _periodic_ordered_args(rays, scene, want_t0=False):
+    """The arguments every periodic ordered entry point starts with; the tensors they point into."""
+    _rays(rays)
+    n_sources = scene.n_sources
+    if n_sources is None:
+        raise ValueError("the scene must come from periodic_scene (it carries n_sources)")
+    keep = periodic_ray_segments(rays, scene.lo, scene.period, want_t0)
+    segments, offsets = keep[0], keep[1]
+    args = _trace_args(segments, scene.spheres, scene.tree) + (
+        _ptr(offsets), C.c_size_t(len(rays)), _ptr(scene.source), C.c_size_t(n_sources))
+    if want_t0:
+        args += (_ptr(keep[2]),)
+    return args, keep
+
+
+def _per_ray_out(out, shape, dtype, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError("%s must be contiguous %s of shape %s" % (what, dtype, tuple(shape)))
+    return out
+
+
+def trace_emission_absorption_periodic_sph(rays, scene, emission, absorption, out=None, tau=None, check=False):
+    """trace_emission_absorption_sph in a periodic box.  A ray's hit list is that of all its segments
+    (periodic_ray_segments) over scene.spheres, ordered by (segment along the ray, fp32 distance within
+    the segment, image index); hit k stands for the particle i_k = scene.source[image]; then, in fp64 and
+    as in the open call, out[r, c] = sum_k emission[i_k, c] I_k phi(a_k) exp(-tau_k), a_k =
+    absorption[i_k] I_k, tau[r] = sum_k a_k, over the ray's whole list.  A ray longer than a period
+    meets a particle once per lattice image.  emission: float32 [n] or [n, C] (1 <= C <= 64),
+    absorption: float32 [n], per CALLER particle in the order of the array given to periodic_scene.
+    Any number of rays.  With open axes, or a box nothing crosses, the open call bit for bit."""
+    if emission.dtype != torch.float32 or absorption.dtype != torch.float32:
+        raise ValueError("emission and absorption must be float32")
+    n = scene.n_sources
+    if emission.dim() not in (1, 2) or emission.shape[0] != n:
+        raise ValueError("emission must have shape [n] or [n, C], one row per sphere given to periodic_scene")
+    if tuple(absorption.shape) != (n,):
+        raise ValueError("absorption must have shape [n], one value per sphere given to periodic_scene")
+    n_ch = 1 if emission.dim() == 1 else emission.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("emission must have 1..64 channels")
+    shape = (len(rays),) if emission.dim() == 1 else (len(rays), n_ch)
+    out = _per_ray_out(out, shape, torch.float32, rays.device, "out")
+    if tau is not None:
+        _per_ray_out(tau, (len(rays),), torch.float32, rays.device, "tau")
+    if len(rays) == 0:
+        return out
+    emission, absorption = emission.contiguous(), absorption.contiguous()
+    args, keep = _periodic_ordered_args(rays, scene)
+    _check(_lib.grace_trace_emission_absorption_periodic_f4(*args, _ptr(emission), C.c_int(n_ch), _ptr(absorption),
+                                                            _ptr(out), _ptr(tau), _stream()))
+    if check:
+        trace_status()
+    return out
+
+
+def trace_absorption_deposit_periodic_sph(rays, scene, luminosity, absorption, deposit=None, transmitted=None,
+                                          quantum=None, check=False):
+    """trace_absorption_deposit_sph in a periodic box: the hit list and its order as in
+    trace_emission_absorption_periodic_sph; ray r's luminosity[r, c] is absorbed hit by hit along ALL its
+    segments (a segment starts with what its predecessor left), deposit[i, c] sums what particle i
+    absorbs through any of its images, from all rays, and transmitted[r, c] is what is left at the ray's
+    end.  The quantum's n_rays is the number of rays, not of segments, so deposit stays bit-identical for
+    any order of the rays.  luminosity: float32 [n_rays] or [n_rays, C]; absorption: float32 [n] or
+    [n, C] and deposit: float64 [n] or [n, C], per CALLER particle in the order of the array given to
+    periodic_scene.  Any number of rays."""
+    _rays(rays)
+    if luminosity.dtype != torch.float32 or absorption.dtype != torch.float32:
+        raise ValueError("luminosity and absorption must be float32")
+    if luminosity.dim() not in (1, 2) or luminosity.shape[0] != len(rays):
+        raise ValueError("luminosity must have shape [n_rays] or [n_rays, C]")
+    n_ch = 1 if luminosity.dim() == 1 else luminosity.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("luminosity must have 1..64 channels")
+    n = scene.n_sources
+    shape = (n,) if luminosity.dim() == 1 else (n, n_ch)
+    if tuple(absorption.shape) != shape:
+        raise ValueError("absorption must be float32 of shape %s, one row per sphere given to periodic_scene" % (shape,))
+    deposit = _per_ray_out(deposit, shape, torch.float64, rays.device, "deposit")
+    if transmitted is not None:
+        _per_ray_out(transmitted, tuple(luminosity.shape), torch.float32, rays.device, "transmitted")
+    if quantum is not None:
+        _per_ray_out(quantum, (n_ch,), torch.float64, rays.device, "quantum")
+    luminosity, absorption = luminosity.contiguous(), absorption.contiguous()
+    if len(rays) == 0:
+        deposit.zero_()
+        if quantum is not None:
+            quantum.zero_()
+        return deposit
+    args, keep = _periodic_ordered_args(rays, scene)
+    _check(_lib.grace_trace_absorption_deposit_periodic_f4(*args, _ptr(luminosity), _ptr(absorption), C.c_int(n_ch),
+                                                           _ptr(deposit), _ptr(transmitted), _ptr(quantum),
+                                                           _stream()))
+    if check:
+        trace_status()
+    return deposit
+
+
+def trace_spectra_periodic_sph(rays, scene, amount, width, velocity, v0, dv, n_bins, periodic=False, hubble=0.0,
+                               tau=None, column=None, check=False):
+    """trace_spectra_sph in a periodic box (a sightline through a cosmological snapshot, starting
+    anywhere and as long as wanted): the hit list and its order as in
+    trace_emission_absorption_periodic_sph; hit k's distance from the RAY's origin is d_k = t0 + d in
+    fp64 -- t0 its segment's starting parameter (periodic_ray_segments(..., want_t0=True)), d its fp32
+    distance within the segment -- and v_k = hubble d_k + velocity[i_k] . direction; the rest is the open
+    call's.  amount, width: float32 [n] or [n, C] (1 <= C <= 16), velocity: float32 [n, 3], per CALLER
+    particle in the order of the array given to periodic_scene.  `periodic` is the VELOCITY grid's, as
+    in the open call.  Any number of rays.  Returns tau, float32 [n_rays, C, n_bins]."""
+    if amount.dtype != torch.float32 or width.dtype != torch.float32 or velocity.dtype != torch.float32:
+        raise ValueError("amount, width and velocity must be float32")
+    n = scene.n_sources
+    if amount.dim() not in (1, 2) or amount.shape[0] != n:
+        raise ValueError("amount must have shape [n] or [n, C], one row per sphere given to periodic_scene")
+    n_ch = 1 if amount.dim() == 1 else amount.shape[1]
+    if not 1 <= n_ch <= 16:
+        raise ValueError("amount must have 1..16 channels")
+    if tuple(width.shape) != tuple(amount.shape):
+        raise ValueError("width must be float32 of shape %s" % (tuple(amount.shape),))
+    if tuple(velocity.shape) != (n, 3):
+        raise ValueError("velocity must be float32 of shape [n, 3], one row per sphere given to periodic_scene")
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 4096:
+        raise ValueError("n_bins must be 1..4096")
+    tau = _per_ray_out(tau, (len(rays), n_ch, n_bins), torch.float32, rays.device, "tau")
+    if column is not None:
+        _per_ray_out(column, (len(rays), n_ch), torch.float32, rays.device, "column")
+    if len(rays) == 0:
+        return tau
+    amount, width, velocity = amount.contiguous(), width.contiguous(), velocity.contiguous()
+    grid = _SpectrumGrid(float(v0), float(dv), n_bins, 1 if periodic else 0, float(hubble))
+    args, keep = _periodic_ordered_args(rays, scene, want_t0=True)
+    _check(_lib.grace_trace_spectra_periodic_f4(*args, _ptr(amount), _ptr(width), _ptr(velocity), C.c_int(n_ch),
+                                                C.byref(grid), _ptr(tau), _ptr(column), _stream()))
+    if check:
+        trace_status()
+    return tau
 
 
 def _project_periodic_sph(spheres, n_side, max_per_leaf, period, lo):

@@ -327,7 +327,8 @@ grace_status grace_trace_cumulative_weighted_f4(const void* d_rays, size_t n_ray
  * workspace and one fused sort-and-composite kernel; it synchronises the stream once, to read the
  * batch ends (not the per-ray counts).  The total number of hits is not limited to INT32_MAX.
  * GRACE_INVALID_ARGUMENT for n_channels outside 1..64, null emission / absorption or null d_out
- * (checked before any launch); zero rays: GRACE_OK, nothing written. */
+ * (checked before any launch); zero rays: GRACE_OK, nothing written.
+ * Periodic boxes: grace_trace_emission_absorption_periodic_f4 below. */
 grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
                                                 size_t n_spheres, const int* d_nodes, size_t n_nodes,
                                                 const int* d_leaves, const int* d_root,
@@ -380,7 +381,8 @@ grace_status grace_trace_emission_absorption_f4(const void* d_rays, size_t n_ray
  * of grace_trace_emission_absorption_f4; the int64 accumulators (8 bytes per sphere and channel) live
  * in the workspace for the length of the call.  GRACE_INVALID_ARGUMENT for n_channels outside 1..64,
  * null d_luminosity / d_absorption / d_deposit and counts out of range, checked before any launch;
- * zero rays: GRACE_OK, d_deposit and d_quantum zeroed (d_luminosity may then be null). */
+ * zero rays: GRACE_OK, d_deposit and d_quantum zeroed (d_luminosity may then be null).
+ * Periodic boxes: grace_trace_absorption_deposit_periodic_f4 below. */
 grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays, const float* d_spheres,
                                                size_t n_spheres, const int* d_nodes, size_t n_nodes,
                                                const int* d_leaves, const int* d_root,
@@ -432,7 +434,8 @@ grace_status grace_trace_absorption_deposit_f4(const void* d_rays, size_t n_rays
  * GRACE_INVALID_ARGUMENT, before any launch, for n_channels outside 1..16, n_bins outside 1..4096, dv
  * not a positive finite number, non-finite v0 or hubble, null grid / d_amount / d_width / d_velocity /
  * d_tau and counts out of range; zero rays: GRACE_OK, nothing written.
- * Not here: Voigt (damped) profiles, double4 spheres, fp64 outputs. */
+ * Not here: Voigt (damped) profiles, double4 spheres, fp64 outputs.
+ * Periodic boxes (of the SCENE; `periodic` below is the velocity grid's): grace_trace_spectra_periodic_f4 below. */
 typedef struct grace_spectrum_grid {
     double v0;        /* lower edge of bin 0 */
     double dv;        /* bin width, > 0 */
@@ -1287,8 +1290,43 @@ grace_status grace_interpolate_grid_periodic_f4(const float* h_origin3, const fl
  * grace_periodic_gather_rows_f32 writes d_out[j * n_channels + c] = d_rows[d_source[j] * n_channels + c]
  * (1 <= n_channels <= 64).  Open boxes, or a box much larger than the scene and the rays (no sphere
  * crosses a face, every ray stays in cell 0), give the open outputs bit for bit.
- * Not provided: the ordered traces (emission-absorption, deposits, spectra: the optical depth would
- * have to be carried across segments), per-hit outputs, double4 spheres, H > L / 2. */
+ *
+ * Ordered traces (grace_trace_emission_absorption_periodic_f4, grace_trace_absorption_deposit_periodic_f4,
+ * grace_trace_spectra_periodic_f4, extending grace_trace_emission_absorption_f4,
+ * grace_trace_absorption_deposit_f4 and grace_trace_spectra_f4 above).  A fold of per-segment results
+ * does not define them -- a deposit's segment needs the luminosity its predecessor left, a spectrum's
+ * hit its distance from the ray's origin -- so they are the open call's composite applied PER RAY to
+ * this hit list:
+ * 1. Segments: those of grace_periodic_segments, unchanged.  Segment s has the starting parameter
+ *    t0_s (fp64): the t above at which it starts, 0 for a ray emitted as itself;
+ *    grace_periodic_segment_starts writes d_t0[offsets[n_rays]] with the arithmetic of
+ *    grace_periodic_segments (one walk serves both).
+ * 2. Hits: those of the open per-hit trace (grace_trace_hits_f4) of segment s over the images: image
+ *    index j, integral I, local distance d with 0 <= d < length_s.
+ * 3. Order: by (segment ordinal along the ray, fp32 d, image index j).  Within a segment a ray hits an
+ *    image once, so the keys are distinct.  A ray may hit the same SOURCE several times, once per
+ *    lattice image.  The segment comes first because two lattice images of one particle can have
+ *    closest approaches arbitrarily close in t when H is near L / 2: absolute distance and particle
+ *    index are no total order.
+ * 4. Composite: hit k's particle is i = d_source[j], the caller's index.  Every per-particle input
+ *    (emission, absorption, amount, width, velocity) and output (deposit) is indexed by i, in the
+ *    caller's order, n_sources rows; nothing is gathered per image.  The arithmetic is the open
+ *    call's, every addition placed as a function of k and n with n the ray's total over all segments.
+ *    Spectra: d_k = t0_s + (double)d in fp64, v_k = hubble d_k + ...  Deposit: the quantum's n_rays
+ *    is the number of rays, not of segments.
+ * Arguments: d_segments [n_segments] and d_segment_offsets [n_rays + 1] as grace_periodic_segments made
+ * them; d_images, the tree over them and d_source [n_images] (in tree order) as the front ends'
+ * periodic scene holds them; d_segment_t0 [n_segments] (spectra); then the open call's own arguments,
+ * per-ray arrays holding n_rays rows.  Any number of rays.  With every axis open, or a box so large that
+ * no ray is cut and no sphere imaged, the hit list is the open one, d_source the identity and all
+ * outputs equal the open calls' bit for bit.  Batches are cut at ray boundaries; one ray's hits over all
+ * its segments must fit a batch's 32-bit offsets: if not, GRACE_INVALID_ARGUMENT before any batch is
+ * traced (found on the device, reported with the batch table).  d_segment_offsets is checked on the
+ * device first -- it must start at 0, not decrease, end at n_segments and give a ray at most 65536
+ * segments: otherwise GRACE_INVALID_ARGUMENT and the status word, nothing traced.  An image whose
+ * d_source is outside [0, n_sources) contributes nothing and sets the status word.  n_rays == 0 returns
+ * at once (the deposit: zeroed, as the open call's).
+ * Not provided: per-hit outputs, double4 spheres, H > L / 2. */
 grace_status grace_periodic_image_counts_f4(const float* d_spheres, size_t n, const float* h_lo3,
                                             const float* h_period3, int* d_counts, grace_stream stream);
 grace_status grace_periodic_images_f4(const float* d_spheres, size_t n, const float* h_lo3,
@@ -1299,12 +1337,42 @@ grace_status grace_periodic_segment_counts(const void* d_rays, size_t n_rays, co
 grace_status grace_periodic_segments(const void* d_rays, size_t n_rays, const float* h_lo3,
                                      const float* h_period3, const int* d_offsets, void* d_segments,
                                      grace_stream stream);
+grace_status grace_periodic_segment_starts(const void* d_rays, size_t n_rays, const float* h_lo3,
+                                           const float* h_period3, const int* d_offsets, double* d_t0,
+                                           grace_stream stream);
 grace_status grace_periodic_fold_f32(const float* d_values, const int* d_offsets, size_t n_rays, int n_channels,
                                      float* d_out, grace_stream stream);
 grace_status grace_periodic_fold_i32(const int* d_values, const int* d_offsets, size_t n_rays, int n_channels,
                                      int* d_out, grace_stream stream);
 grace_status grace_periodic_gather_rows_f32(const float* d_rows, const int* d_source, size_t n_images,
                                             int n_channels, float* d_out, grace_stream stream);
+/* grace_trace_emission_absorption_f4 in a periodic box ("Ordered traces" above). */
+grace_status grace_trace_emission_absorption_periodic_f4(const void* d_segments, size_t n_segments,
+                                                         const float* d_images, size_t n_images, const int* d_nodes,
+                                                         size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                         const int* d_segment_offsets, size_t n_rays,
+                                                         const int* d_source, size_t n_sources,
+                                                         const float* d_emission, int n_channels,
+                                                         const float* d_absorption, float* d_out, float* d_tau,
+                                                         grace_stream stream);
+/* grace_trace_absorption_deposit_f4 in a periodic box: d_absorption and d_deposit hold n_sources rows. */
+grace_status grace_trace_absorption_deposit_periodic_f4(const void* d_segments, size_t n_segments,
+                                                        const float* d_images, size_t n_images, const int* d_nodes,
+                                                        size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                        const int* d_segment_offsets, size_t n_rays,
+                                                        const int* d_source, size_t n_sources,
+                                                        const float* d_luminosity, const float* d_absorption,
+                                                        int n_channels, double* d_deposit, float* d_transmitted,
+                                                        double* d_quantum, grace_stream stream);
+/* grace_trace_spectra_f4 in a periodic box: d_segment_t0 from grace_periodic_segment_starts. */
+grace_status grace_trace_spectra_periodic_f4(const void* d_segments, size_t n_segments, const float* d_images,
+                                             size_t n_images, const int* d_nodes, size_t n_nodes,
+                                             const int* d_leaves, const int* d_root, const int* d_segment_offsets,
+                                             size_t n_rays, const int* d_source, size_t n_sources,
+                                             const double* d_segment_t0, const float* d_amount, const float* d_width,
+                                             const float* d_velocity, int n_channels,
+                                             const grace_spectrum_grid* grid, float* d_tau, float* d_column,
+                                             grace_stream stream);
 
 #ifdef __cplusplus
 }
