@@ -42,7 +42,8 @@ def _assert_twins(sc):
     assert h.all() and m.all(), "a twin is not on its side of the boundary"
 
 
-def _build(gh, cuda, sc, mpl=8):
+def _build(gh, cuda, sc, mpl=8, want_perm=False):
+    """want_perm (float spheres): also the caller's index of every sorted sphere."""
     s = sc.spheres
     if sc.prec == "d4":
         d = torch.from_numpy(np.ascontiguousarray(s)).to(cuda)
@@ -51,6 +52,9 @@ def _build(gh, cuda, sc, mpl=8):
     else:
         d = torch.from_numpy(np.ascontiguousarray(s)).to(cuda)
         tree = gh.Tree(len(s), mpl, device=cuda)
+        if want_perm:
+            tree, perm = gh.build_tree(d, tree, tuple(s[:, :3].min(axis=0)), tuple(s[:, :3].max(axis=0)), want_perm=True)
+            return d, tree, perm.cpu().numpy().astype(np.int64)
         gh.build_tree(d, tree, tuple(s[:, :3].min(axis=0)), tuple(s[:, :3].max(axis=0)))
     return d, tree
 
@@ -89,7 +93,7 @@ def _check_hits(got, ref, sub, real):
 
 def _run_f32(gh, O, cuda, sc, k, modes):
     rays = torch.from_numpy(sc.rays).to(cuda)
-    d, tree = _build(gh, cuda, sc, k.get("mpl", 8))
+    d, tree, perm = _build(gh, cuda, sc, k.get("mpl", 8), want_perm=True)
     ss = d.cpu().numpy()                                    # sorted by the build
     rr = sc.rays[sc.sub]
     R = len(rays)
@@ -122,8 +126,9 @@ def _run_f32(gh, O, cuda, sc, k, modes):
         gh.set_exact_integrals(False)
     if "weighted" in modes:
         from test_weighted_column_density import restate
-        rng = np.random.default_rng(7)
-        w = rng.uniform(-2, 2, (len(ss), 2)).astype(F32)
+        # spotlight weights: channels 1 and 2 are 0 on everything but the radius and the range twins,
+        # whose grazing terms (<= 5.64e-11 / h^2) no other sum can see; brought into tree order
+        w = B.spotlight_weights(sc, 4, seed=7)[perm]
         ro, ri, rw, _ = O.brute_hits(rr, ss)
         ref32, _, _ = restate(len(rr), ro, ri, rw, w)
         gh.set_exact_integrals(True)

@@ -127,3 +127,95 @@ def test_generator_scenes_are_sharp():
     sc = B.lattice_scene("unit", seed=1, n_background=1000)
     assert B.sharpness(sc) == 1.0
     assert set(sc.lattice_cols.tolist()) >= {0, 7} and set(sc.lattice_rows.tolist()) >= {0, 7}
+
+
+# ---- the scenes of test_trace_plan_boundaries.py ---------------------------------------------------
+def _digest(sc):
+    import hashlib
+    h = hashlib.sha256()
+    for a in (sc.rays, sc.spheres, sc.hit.astype(np.int64), sc.miss.astype(np.int64)):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def test_existing_scenes_are_unchanged():
+    """Digests (rays, spheres, hit and miss twins) taken before `ragged="one"`, `drop_last` and the
+    `width` argument of axis_rays were added: calls that do not use them draw the same numbers."""
+    assert _digest(B.boundary_scene("axis", "unit", "f32", seed=0)) == \
+        "de7b1cc53887d05b782263e8272e3a1e56b03f7c762ce223461dac85401ef929"
+    assert _digest(B.lattice_scene("unit", seed=0)) == \
+        "2f7c927df993e1461e487dccde4db591aed82cdab02fe2e99bca587f33016917"
+
+
+def test_one_ragged_pair_per_packet_and_a_partial_last_packet():
+    """ragged="one": per packet one ray ends and one other starts in the middle half of the box,
+    every other ray crosses it; the range twins against those two rays lie in that middle half;
+    every twin sits on its side.  drop_last=32: 4064 rays, and the partial last packet has twins
+    against its own rays."""
+    for axis, sense, scale in ((2, 1, "1e3"), (0, -1, "1e5")):
+        sc = B.boundary_scene("axis", scale, "f32", seed=9, axis=axis, sense=sense, ragged="one", n_background=1000)
+        h, m = B.twin_outcomes(sc)
+        assert h.all() and m.all()
+        lo, size, _ = B.SCALES[scale]
+        depth0 = (sc.rays[:, 3 + axis] - lo[axis]) / size if sense > 0 else (lo[axis] + size - sc.rays[:, 3 + axis]) / size
+        depth1 = depth0 + sc.rays[:, 6] / size
+        for pk in B._packets(len(sc.rays), 64):
+            short = pk[depth1[pk] < 1.0]; late = pk[depth0[pk] > 0.0]
+            assert len(short) == 1 and len(late) == 1 and short[0] != late[0]
+            assert 0.25 <= depth1[short[0]] <= 0.75 and 0.25 <= depth0[late[0]] <= 0.75
+            assert pk[np.argmin(sc.rays[pk, 6])] == short[0]
+        nr = sc.n_radius
+        along = (sc.spheres[sc.hit[nr:], axis] - lo[axis]) / size
+        # one at an end and one at a start per packet (the third, random, ray may be the late one again)
+        assert 2 * 64 <= np.sum((along > 0.24) & (along < 0.76)) <= 2 * 64 + 8
+        assert B.sharpness(sc) == 1.0
+    sc = B.boundary_scene("axis", "unit", "f32", seed=9, drop_last=32, n_background=1000)
+    h, m = B.twin_outcomes(sc)
+    assert len(sc.rays) == 4064 and h.all() and m.all()
+    last = sc.target_hit >= 4032
+    assert last[:sc.n_radius].sum() >= 3 and last[sc.n_radius:].sum() >= 2
+    assert sc.target_hit.max() < 4064 and sc.sub.max() < 4064
+
+
+def _plan_scenes():
+    return [("case %d" % c, lambda c=c: B.plan_case_scene(c)) for c in range(len(B.PLAN_CASES))] + \
+        [("lattice " + s, lambda s=s: B.plan_lattice_scene(s)) for s in B.PLAN_LATTICE_SCALES]
+
+
+def test_plan_scenes_have_visible_radius_twins_and_full_range_twins(oracle):
+    """What keeps test_trace_plan_boundaries.py from being blind: a grazing radius twin's term is at
+    most 5.64e-11 / h^2 and often exactly 0 (the table position rounds onto the table's end), so a
+    scene must have enough hit twins whose term is nonzero: at least 100 in every scene that file
+    traces.  Every range twin on the inner side (c_in) contributes a full, nonzero term.  Every
+    twin on its side."""
+    for name, make in _plan_scenes():
+        sc = make()
+        h, m = B.twin_outcomes(sc)
+        assert h.all() and m.all(), name
+        terms = B.twin_terms(sc, oracle)
+        vis = B.visible_twins(sc, oracle)
+        assert len(vis) == sc.n_radius and vis.sum() >= 100, (name, int(vis.sum()))
+        assert np.array_equal(vis, terms[:sc.n_radius] != 0)
+        hh = sc.spheres[sc.hit[:sc.n_radius], 3].astype(F64)
+        assert (terms[:sc.n_radius] * hh * hh).max() < 6e-11, name       # no radius twin is more than grazing
+        assert np.all(terms[sc.n_radius:] != 0), name
+        if not name.startswith("lattice"):
+            assert len(sc.hit) - sc.n_radius >= 100, name
+
+
+def test_spotlight_weights():
+    sc = B.boundary_scene("axis", "unit", "f32", seed=2, n_background=500)
+    nr, n = sc.n_radius, len(sc.spheres)
+    w = B.spotlight_weights(sc, 5, seed=7)
+    assert w.shape == (n, 5) and w.dtype == F32
+    assert np.all(w[:, 0] == 1)
+    radius = np.zeros(n, bool); radius[sc.hit[:nr]] = True; radius[sc.miss[:nr]] = True
+    rng_ = np.zeros(n, bool); rng_[sc.hit[nr:]] = True; rng_[sc.miss[nr:]] = True
+    assert np.array_equal(w[:, 1], radius.astype(F32)) and np.array_equal(w[:, 2], rng_.astype(F32))
+    assert radius.sum() == 2 * nr and rng_.sum() == 2 * (len(sc.hit) - nr) and not (radius & rng_).any()
+    assert w[:, 3].min() >= -2 and w[:, 3].max() <= 2 and len(np.unique(w[:, 3])) > n // 2
+    assert np.array_equal(w[:, 4], w[:, 1] * F32(0.5))
+    for c in (2, 3, 4):
+        assert np.array_equal(B.spotlight_weights(sc, c, seed=7), w[:, :c])
+    assert np.array_equal(B.spotlight_weights(sc, 1, seed=7), w[:, 1:2])
+    assert not np.array_equal(B.spotlight_weights(sc, 4, seed=8)[:, 3], w[:, 3])

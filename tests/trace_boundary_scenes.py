@@ -152,9 +152,13 @@ class Scene:
         self.__dict__.update(kw)
 
 
-def axis_rays(side, axis, sense, lo, size, rng, neg_zero=False, ragged=False):
+def axis_rays(side, axis, sense, lo, size, rng, neg_zero=False, ragged=False, width=64):
     """side x side rays along sense * e_axis over the face of the box [lo, lo + size]^3, in tiles;
-    ragged: per-ray starts and lengths (the lean test's len_lo / noda bounds then differ per ray)."""
+    ragged: per-ray starts and lengths (the lean test's len_lo / noda bounds then differ per ray);
+    ragged="one": every ray crosses the whole box, except that in each packet (run of `width`
+    rays) one ray ends inside the box and one other starts inside it, both at depths drawn per
+    packet in the middle half of the box -- the packet's len_lo and its latest start then lie
+    inside dense background, and only the rounds around them need a range test."""
     i, j = _morton_tile_order(side)
     perp = [k for k in range(3) if k != axis]
     sp = size / side
@@ -164,7 +168,15 @@ def axis_rays(side, axis, sense, lo, size, rng, neg_zero=False, ragged=False):
     r[:, axis] = sense
     r[:, 3 + perp[0]] = (lo[perp[0]] + (i + 0.5) * sp).astype(F32)
     r[:, 3 + perp[1]] = (lo[perp[1]] + (j + 0.5) * sp).astype(F32)
-    if ragged:
+    if isinstance(ragged, str):
+        assert ragged == "one"
+        start = np.full(len(r), -0.1 * size)
+        r[:, 6] = F32(1.2 * size)
+        for pk in _packets(len(r), width):
+            short, late = pk[rng.choice(len(pk), 2, replace=False)]
+            r[short, 6] = F32((0.1 + rng.uniform(0.25, 0.75)) * size)     # ends at that depth
+            start[late] = rng.uniform(0.25, 0.75) * size                  # starts at this one
+    elif ragged:
         start = rng.uniform(-0.1, 0.4, len(r)) * size
         r[:, 6] = (rng.uniform(0.3, 1.2, len(r)) * size).astype(F32)
     else:
@@ -350,16 +362,21 @@ def range_twins(ray, t0, w, prec):
 
 
 def boundary_scene(kind, scale, prec="f32", seed=0, side=64, axis=2, sense=1, width=64,
-                   n_background=60000, neg_zero=False, ragged=False, rim=True, max_twins=600):
+                   n_background=60000, neg_zero=False, ragged=False, rim=True, max_twins=600, drop_last=0):
     """A scene of `n_background` random spheres in the scale's box plus radius and range twins
     against the extreme rays of every packet (kind: "axis", "pinhole", "iso", "healpix",
-    "general").  prec: the hit test the twins are exact for ("f32", "f4d", "d4")."""
+    "general").  prec: the hit test the twins are exact for ("f32", "f4d", "d4").  drop_last: that
+    many rays (a multiple of 32, as ray counts are) are removed from the end before the twins are
+    placed: the last packet is then partial and gets twins against its own extreme rays."""
     rng = np.random.default_rng(seed)
     lo, size, (hlo, hhi) = SCALES[scale]
     ct = F64 if prec == "d4" else F32
     pencil = kind in ("pinhole", "iso", "healpix")
     if kind == "axis":
-        rays, sp = axis_rays(side, axis, sense, lo, size, rng, neg_zero=neg_zero, ragged=ragged)
+        rays, sp = axis_rays(side, axis, sense, lo, size, rng, neg_zero=neg_zero, ragged=ragged, width=width)
+        if drop_last:
+            assert drop_last % 32 == 0 and 0 < drop_last < len(rays)
+            rays = np.ascontiguousarray(rays[:len(rays) - drop_last])
         places = extreme_placements(rays, "axis", width, rng, sp)
         t_range = (0.15, 0.85)
     elif pencil:
@@ -434,6 +451,44 @@ def twin_outcomes(sc):
     return h, ~m
 
 
+def spotlight_weights(sc, n_channels, seed):
+    """float32 [n, C] weights in the scene's caller order that make single twins visible in a
+    weighted column density: channel 0 is 1 everywhere (the unweighted trace), channel 1 is 1 on
+    the radius twins (hit and miss) and 0 elsewhere, channel 2 the same for the range twins (in and
+    out), channel 3 uniform in [-2, 2], channel 4 half of channel 1.  Fewer channels: a prefix,
+    except that one channel is channel 1 alone.  With 0 on everything else, channel 1 of a ray is
+    exactly the fp32 sum of its twins' terms: a dropped hit twin turns a nonzero value into 0 (or
+    changes its bits), a counted miss twin adds a term the reference does not have."""
+    assert 1 <= n_channels <= 5
+    n, nr = len(sc.spheres), sc.n_radius
+    w = np.zeros((n, 5), F32)
+    w[:, 0] = 1
+    w[sc.hit[:nr], 1] = 1; w[sc.miss[:nr], 1] = 1
+    w[sc.hit[nr:], 2] = 1; w[sc.miss[nr:], 2] = 1
+    w[:, 3] = np.random.default_rng(seed).uniform(-2, 2, n).astype(F32)
+    w[:, 4] = w[:, 1] * F32(0.5)
+    return np.ascontiguousarray(w[:, 1:2] if n_channels == 1 else w[:, :n_channels])
+
+
+def twin_terms(sc, oracle):
+    """Per hit twin, the oracle's per-hit integral of the twin traced alone by its target ray
+    (float32; 0 where the oracle counts no hit)."""
+    out = np.zeros(len(sc.hit), F32)
+    for k, (sid, r) in enumerate(zip(sc.hit, sc.target_hit)):
+        _, idx, integ, _ = oracle.brute_hits(sc.rays[r:r + 1], sc.spheres[sid:sid + 1].astype(F32))
+        if len(idx):
+            out[k] = integ[0]
+    return out
+
+
+def visible_twins(sc, oracle):
+    """Mask over the radius hit twins (sc.hit[:sc.n_radius]): those whose per-hit integral
+    against their target ray is nonzero according to the oracle.  (A grazing twin's table position
+    is within a few ulp of the table's end, where the line integral is 0: many terms are exactly 0
+    and such a twin cannot be seen in any sum.)"""
+    return twin_terms(sc, oracle)[:sc.n_radius] != 0
+
+
 def sharpness(sc):
     """Fraction of hit twins that no other ray of their packet (runs of sc.width) hits."""
     fn = RESTATE[sc.prec]
@@ -483,3 +538,45 @@ def lattice_scene(scale="unit", seed=0, side=64, n_background=20000, max_places=
     return Scene(rays=rays, spheres=spheres, hit=hit_ids, miss=miss_ids, target_hit=tgt, target_miss=tgt,
                  n_radius=len(c), sub=np.unique(np.concatenate([tgt, extra])), prec="f32", kind="axis",
                  scale=scale, box=(lo, lo + size), width=64, lattice_cols=i[tgt] % TILE, lattice_rows=j[tgt] % TILE)
+
+
+# ---- the scenes of tests/test_trace_plan_boundaries.py -------------------------------------------
+# (scale, axis, sense, scene options, knobs, weight channels -- each case also runs the unweighted
+# trace); the knobs are covered pairwise, not as their full product.  The seeds are chosen so that
+# every scene has at least 100 visible radius hit twins (tests/test_trace_boundary_scenes.py).
+PLAN_CASES = [
+    ("unit", 0, 1, dict(), dict(width=64, reorder=False, split=-1, mpl=8), 4),
+    ("1e3", 0, -1, dict(neg_zero=True), dict(width=32, reorder=True, split=2, mpl=8), 1),
+    ("1e5", 1, 1, dict(ragged=True), dict(width=16, reorder=False, split=8, mpl=8), 5),
+    ("1e-3", 1, -1, dict(ragged=True), dict(width=-1, reorder=True, split=-1, mpl=8), 2),
+    ("1e5", 2, 1, dict(neg_zero=True), dict(width=32, reorder=False, split=-1, mpl=1), 3),
+    ("unit", 2, -1, dict(ragged=True), dict(width=-1, reorder=False, split=2, mpl=32), 4),
+    ("1e3", 2, 1, dict(ragged="one"), dict(width=64, reorder=True, split=-1, mpl=8), 4),
+    ("1e5", 0, -1, dict(ragged="one"), dict(width=64, reorder=False, split=4, mpl=8), 1),
+    ("unit", 2, 1, dict(drop_last=32), dict(width=64, reorder=False, split=-1, mpl=8), 4),
+]
+PLAN_BACKGROUND = 20000
+PLAN_LATTICE_SCALES = ("unit", "1e3", "1e5", "1e-3")
+
+
+def plan_case_width(case):
+    """The packet width the library runs row `case` at, which the twins are placed against: the
+    knob's where it is set; with the automatic width, a column-density batch of 4096 rays runs
+    packets of 16 rays (fewer than 512 packets of any wider kind) unless the split is set by hand,
+    which keeps 64 (row 6)."""
+    knobs = PLAN_CASES[case][4]
+    if knobs["width"] > 0:
+        return knobs["width"]
+    return 64 if knobs["split"] > 0 else 16
+
+
+def plan_case_scene(case, n_background=PLAN_BACKGROUND):
+    """The scene of row `case` of PLAN_CASES.  (The twins are placed before the background is
+    drawn: they do not depend on n_background.)"""
+    scale, axis, sense, opts, knobs, _ = PLAN_CASES[case]
+    return boundary_scene("axis", scale, "f32", seed=300 + case, axis=axis, sense=sense,
+                          width=plan_case_width(case), n_background=n_background, max_twins=600, **opts)
+
+
+def plan_lattice_scene(scale, n_background=PLAN_BACKGROUND):
+    return lattice_scene(scale, seed=320 + PLAN_LATTICE_SCALES.index(scale), n_background=n_background)
