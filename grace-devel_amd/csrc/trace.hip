@@ -75,10 +75,11 @@
 //     granule boundaries, once per culling round at most.  Hit counts split the same way
 //     (integers);
 //   * packet plan: once the scene records and the ray order both come out of their validated
-//     caches, the cull of every axis-aligned packet -- per class the list of its non-empty rounds,
-//     {cluster, survivor mask, lean / fat bits} -- is recorded beside them (trace_planned.hip) and
-//     the column-density calls that follow run the PLANNED instantiation: survivor loops only,
-//     entries by scalar loads; re-recorded on the device when a signature has moved;
+//     caches, the cull of every axis-aligned packet -- per class the list of its survivors'
+//     indices, with a {count, lean / fat bits} header per dense round -- is recorded beside them
+//     (trace_planned.hip) and the column-density calls that follow run the PLANNED instantiation:
+//     one gather per round and the survivor loops, headers by scalar loads; re-recorded on the
+//     device when a signature has moved;
 //   * per-hit outputs (ordered per ray): large batches stage hits per lane in LDS and drain
 //     them eight entries per ray; small batches split a packet over K waves by contiguous
 //     chunk ranges with per-(ray, chunk) output offsets from a counting walk (hits_plan_kernel);
@@ -598,9 +599,10 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
             GRACE_TRY(plan_fill(ts, b.plan_key, a, stream));
         ts.last_plan_ctl = nullptr;
         if (b.plan_eligible && pp.valid && pp.key == b.plan_key) {
-            a.plan_entries = pp.entries; a.plan_spans = pp.spans; a.plan_counts = pp.counts;
+            a.plan_idx = pp.idx; a.plan_hdr = pp.hdr; a.plan_spans = pp.spans; a.plan_counts = pp.counts;
             a.plan_usable = &pp.ctl->usable;
             ts.last_plan_ctl = pp.ctl; ts.last_plan_stream = stream;
+            ts.last_plan_fuses = !weighted(MODE) && p.fast_b;   // (the kernel that fuses: trace_kernel.hpp, FUSE)
         }
     }
     return timed(ts, stream, [&] {
@@ -1015,6 +1017,24 @@ grace_status grace_trace_plan_stats(unsigned long long* h_stats)
     return GRACE_OK;
 }
 
+grace_status grace_trace_plan_loops(unsigned long long* h_loops)
+{
+    GRACE_REQUIRE(h_loops, "null output");
+    h_loops[0] = h_loops[1] = 0;
+    GRACE_TRACE_STATE();
+    if (ts.last_plan_ctl) {
+        PlanCtl h = {};
+        GRACE_TRY_HIP(hipStreamSynchronize(ts.last_plan_stream));
+        GRACE_TRY_HIP(hipMemcpy(&h, ts.last_plan_ctl, sizeof(h), hipMemcpyDeviceToHost));
+        if (h.usable != 0u) {
+            // (a kernel that does not fuse runs one loop per dense round)
+            h_loops[0] = ts.last_plan_fuses ? h.loops : h.stats[2];
+            h_loops[1] = ts.last_plan_fuses ? h.largest_loop : h.largest_round;
+        }
+    }
+    return GRACE_OK;
+}
+
 grace_status grace_trace_set_plan(int on)
 {
     GRACE_TRACE_STATE();
@@ -1036,7 +1056,7 @@ grace_status grace_trace_plan_bytes(size_t* h_bytes)
     GRACE_REQUIRE(h_bytes, "null output");
     GRACE_TRACE_STATE();
     const PacketPlan& pp = ts.plan;
-    *h_bytes = pp.valid ? (pp.n_entries + 4) * sizeof(uint4) + pp.n_lists * (sizeof(int) + sizeof(int2)) + sizeof(PlanCtl) : 0;
+    *h_bytes = pp.valid ? pp.bytes() : 0;
     return GRACE_OK;
 }
 

@@ -244,6 +244,7 @@ __global__ void choose_variants_kernel(const uint32_t* __restrict__ ext12, int n
             pc.sig[2] = gate.rays->sig[0]; pc.sig[3] = gate.rays->sig[1];
             for (int k = 0; k < 6; ++k) pc.stats[k] = 0ull;   // (the re-record tallies afresh)
             pc.largest_round = 0u;
+            pc.loops = 0ull; pc.largest_loop = 0u;
         }
     }
 }

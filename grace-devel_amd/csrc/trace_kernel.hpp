@@ -306,11 +306,13 @@ __device__ __forceinline__ bool cluster_may_hit(const float4 blo, const float4 b
     }
 }
 
-// The packet plan is read through the constant address space: written by an earlier launch, never
-// during this one, and every address is wave-uniform -- so the entries arrive by scalar loads into
-// SGPRs (a global pointer gave vector loads of one address, twelve VGPRs and a readfirstlane each).
-typedef uint32_t plan_u32x4 __attribute__((ext_vector_type(4)));
-typedef int plan_i32x2 __attribute__((ext_vector_type(2)));
+// The packet plan's spans, counts and round headers are read through the constant address space:
+// written by an earlier launch, never during this one, and every address is wave-uniform -- so
+// they arrive by scalar loads into SGPRs (a global pointer gave vector loads of one address, VGPRs
+// and a readfirstlane each).  The index words are per lane: ordinary vector loads.
+typedef int plan_i32x4 __attribute__((ext_vector_type(4)));
+// (four round headers from any header on: a scalar load asks for 4-byte alignment only)
+typedef uint32_t plan_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 template <typename T>
 __device__ __forceinline__ const __attribute__((address_space(4))) T* plan_const(const void* p)
 {
@@ -336,12 +338,14 @@ struct WeightedB {
 // class-split kernels registers they do not have, and the frame kernel 2 %, so scenes without
 // sub-spacing spheres must not carry it.
 // PLANNED: the packet-plan consumer (PacketPlan, trace_state.hpp) of the class-split column-density
-// kernels: each wave walks the recorded lists of its classes one DENSE ROUND at a time -- the
-// consecutive entries the recorder grouped (at most 64 survivors, one lean / fat class), read
-// through scalar loads four entries ahead; their survivors are gathered from all the round's
-// clusters, one per lane (gather_round, in the sweep) -- and runs the survivor loops of the axis
-// path as they are, once per dense round.  It makes no group pass, no cluster test, no cull, keeps
-// no stack and has no LAT variant (the recorded masks hold the lattice cull's result).
+// kernels: each wave walks the recorded lists of its classes one DENSE ROUND at a time -- at most
+// 64 survivors of one lean / fat class, the headers read through scalar loads four ahead; lane l
+// loads the round's l-th index word (two rounds ahead) and with it that survivor's records
+// (gather_round, in the sweep) -- and runs the survivor loops of the axis path as they are, once
+// per dense round; the unweighted kernel with the fast integral (FUSE) runs consecutive test-free
+// rounds of equal bits as ONE loop of up to 128 survivors (planned_fuses, trace_state.hpp), the
+// second 64 gathered from the next 64 index words.  It makes no group pass, no cluster test, no
+// cull, keeps no stack and has no LAT variant (the recorded indices hold the lattice cull's result).
 template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false, bool PLANNED = false>
 // The one-wave-per-packet hit-count / column-density kernels are held to 6 waves per SIMD (<= 80
 // VGPRs): left to itself the register allocator drifts between 77 and 102 VGPRs from one edit of
@@ -372,6 +376,9 @@ void trace_kernel(const TraceArgs a)
     constexpr int NW = channels(MODE), WP = WEIGHTED ? (NW + 1) / 2 : 0;
     // A survivor's 1/h terms -- and, weighted, its NW staged weights
     using BRec = std::conditional_t<WEIGHTED, WeightedB<NW>, float2>;
+    // The planned kernel that fuses test-free rounds (the weighted ones do not: their occupancy is
+    // set by LDS; the exact integral has no test-free loop)
+    constexpr bool FUSE = PLANNED && !WEIGHTED && FAST;
     __shared__ double2 s_lut[FAST ? 1 : N_TABLE];
     // Fast integral: entry i = (y_i - i dy_i, dy_i), so that the lerp at table position b is ONE fma,
     // fma(dy_i, b, y_i - i dy_i) with i = int(b) -- no fractional part to extract.  Entries from
@@ -387,7 +394,10 @@ void trace_kernel(const TraceArgs a)
     // (plane base + 8 j) serves all of a survivor's reads through immediate offsets.
     // (66 slots: the survivor loop reads up to two slots past the round's last survivor)
     // Weighted sums add WP planes of staged weights (channels 2p, 2p + 1 in plane 3 + p).
-    __shared__ __align__(16) float2 s_tile[LDS_TILE ? TRACE_BLOCK / 64 : 1][LDS_TILE ? 3 + WP : 1][LDS_TILE ? 66 : 1];
+    // FUSE: a fourth plane, so that the tile holds a fused loop's 128 + 2 sixteen-byte records
+    // (2080 of 2112 bytes).
+    __shared__ __align__(16) float2 s_tile[LDS_TILE ? TRACE_BLOCK / 64 : 1][LDS_TILE ? (FUSE ? 4 : 3 + WP) : 1][LDS_TILE ? 66 : 1];
+    static_assert(!FUSE || 4 * 66 * sizeof(float2) >= (PLAN_LOOP_MAX + 2) * sizeof(float4), "the fused loop's tile");
     // *_D4 modes: the round's candidates as doubles, lane-indexed: {x, y, z, w w, 1/w, (1/w)^2}
     // (the division is done once per candidate by its lane, not once per survivor by the wave).
     __shared__ double s_tile_d[D4 ? TRACE_BLOCK / 64 : 1][D4 ? 64 : 1][D4 ? 6 : 1];
@@ -794,9 +804,10 @@ void trace_kernel(const TraceArgs a)
     if (flat && groups_kept > FLAT_MAX_GROUPS) flat = false;
     if (!flat && !PLANNED) push(*a.root, ~0ull);
     // PLANNED: the list being walked (wave-uniform) and the next class of this wave
-    const __attribute__((address_space(4))) plan_u32x4* plan_at = nullptr;
+    const __attribute__((address_space(4))) uint32_t* plan_hdr_at = nullptr;   // its round headers
+    const uint32_t* plan_idx_at = nullptr;                                     // its index words
     int plan_n = 0, plan_cls = own_lo;
-    (void)plan_at; (void)plan_n; (void)plan_cls;
+    (void)plan_hdr_at; (void)plan_idx_at; (void)plan_n; (void)plan_cls;
     unsigned long long st_walk = 0, st_cluster = 0, st_cull = 0, st_surv = 0, st_rounds = 0, st_nsurv = 0;
     const unsigned long long st_begin = STAMP_NOW();
     (void)st_walk; (void)st_cluster; (void)st_cull; (void)st_surv; (void)st_rounds; (void)st_nsurv; (void)st_begin;
@@ -808,9 +819,11 @@ void trace_kernel(const TraceArgs a)
         if constexpr (PLANNED) {
             if (plan_cls >= own_hi) break;
             const int list = packet * SUM_CLASSES + plan_cls++;
-            plan_n = plan_const<int>(a.plan_counts)[list];
+            plan_n = plan_const<plan_i32x4>(a.plan_counts)[list].x;   // (dense rounds)
             if (plan_n <= 0) continue;
-            plan_at = plan_const<plan_u32x4>(a.plan_entries) + plan_const<plan_i32x2>(a.plan_spans)[list].x;
+            const plan_i32x4 span = plan_const<plan_i32x4>(a.plan_spans)[list];
+            plan_idx_at = a.plan_idx + span.x;
+            plan_hdr_at = plan_const<uint32_t>(a.plan_hdr) + span.y;
             enter_granule((plan_cls - 1) << GRANULE_SHIFT);   // the list's class accumulator (granule g is of class g & 7)
             sweep = true; sweep_count = a.n_prims;
         } else if (flat) {
@@ -999,12 +1012,54 @@ void trace_kernel(const TraceArgs a)
                 if (cmask == 0ull) continue;
                 int cnext = cg + __builtin_ctzll(cmask);
                 cmask &= cmask - 1ull;
-                // PLANNED: entries plan_i .. plan_i + 3 of the list (wave-uniform: scalar loads; the plan
-                // is padded so that reading past a list's end stays inside it)
-                plan_u32x4 e0 = { 0u, 0u, 0u, 0u }, e1 = e0, e2 = e0, e3 = e0;
-                int plan_i = 0;
-                (void)plan_i;
-                if constexpr (PLANNED) { e0 = plan_at[0]; e1 = plan_at[1]; e2 = plan_at[2]; e3 = plan_at[3]; }
+                // PLANNED: the headers of rounds plan_i .. plan_i + 3 of the list (wave-uniform: one
+                // scalar load), the loop formed from the rounds before them -- its survivors (0: none
+                // left), its bits, its first index word -- and lane l's index words of that loop,
+                // l and 64 + l (the plan is padded so that reading past a list's end stays inside it)
+                plan_u32x4 plan_h = { 0u, 0u, 0u, 0u };
+                uint32_t plan_word = 0u, plan_word2 = 0u;
+                int plan_i = 0, plan_w = 0, loop_n = 0, loop_bits = 0;
+                (void)plan_h; (void)plan_word; (void)plan_word2; (void)plan_i; (void)plan_w; (void)loop_n; (void)loop_bits;
+                const uint32_t lane4 = uint32_t(lane) << 2;
+                (void)lane4;
+                auto headers_at = [&](const int round) {   // (four headers from `round` on: one scalar load)
+                    return *reinterpret_cast<const __attribute__((address_space(4))) plan_u32x4*>(plan_hdr_at + round);
+                };
+                (void)headers_at;
+                // Forms the next loop from the headers at hand: the list's next round and, FUSE, the
+                // rounds after it that planned_fuses lets join; then fetches the headers after them
+                // and the loop's index words.
+                auto form_loop = [&]() {
+                    if constexpr (PLANNED) {
+                        loop_n = 0;
+                        if (plan_i < plan_n) {
+                            loop_n = plan_header_count(plan_h.x);
+                            loop_bits = plan_header_bits(plan_h.x);
+                            ++plan_i;
+                            if constexpr (FUSE) {
+                                int k = 1;   // headers at hand that are used up
+                                for (;;) {
+                                    // (a loop of more rounds than are at hand waits for four more: rare)
+                                    if (k == 4) { plan_h = headers_at(plan_i); k = 0; }
+                                    const uint32_t next = k == 0 ? plan_h.x : k == 1 ? plan_h.y : k == 2 ? plan_h.z : plan_h.w;
+                                    if (!(plan_i < plan_n && planned_fuses(loop_n, loop_bits, next))) break;
+                                    loop_n += plan_header_count(next);
+                                    ++plan_i; ++k;
+                                }
+                            }
+                        }
+                        plan_h = headers_at(plan_i);
+                        // (a wave-uniform base and a 32-bit lane offset: the load's scalar-base form)
+                        const char* const base = reinterpret_cast<const char*>(plan_idx_at + plan_w);
+                        plan_word = *reinterpret_cast<const uint32_t*>(base + lane4);
+                        if constexpr (FUSE)
+                            if (loop_n > 64) plan_word2 = *reinterpret_cast<const uint32_t*>(base + 256 + lane4);
+                    }
+                };
+                if constexpr (PLANNED) {
+                    plan_h = headers_at(0);
+                    form_loop();
+                }
                 // A round's 64 candidates are fetched one round ahead (vector loads, 16 B/lane,
                 // coalesced) so that their latency hides behind the previous round's survivors.
                 // (Round 3, measured and rejected: two register sets taking turns with the round
@@ -1016,54 +1071,41 @@ void trace_kernel(const TraceArgs a)
                 // the rounds without a loop leave the prefetch no time.)
                 float4 mine_next;
                 float2 mineb_next = make_float2(0.f, 0.f);
-                // PLANNED: a DENSE round -- the survivors of the list's next entries up to the one
-                // the recorder marked (at most 64, one lean / fat class).  Invert: entry by entry on
-                // the scalar unit, the lanes its mask names store their candidate's index at the
-                // round's running survivor count + their rank in the mask.  Gather: lane l reads
-                // index l and fetches that survivor's records -- one record per lane in flight
-                // however many clusters the round draws on.  Leaves the round's survivor count and
-                // bits in round_n_next / round_bits_next.  The 64 indices pass through the first
-                // 256 bytes of the wave's tile: the previous round's loop has read its survivors,
-                // this round's are staged after the gather, and a wave's LDS accesses keep their order.
+                // PLANNED: the loop that form_loop formed -- a DENSE round, the recorder's next at
+                // most 64 survivors of one lean / fat class, or (FUSE) several test-free ones, at most
+                // 128 survivors.  Lane l clamps the index word it holds and fetches that survivor's
+                // records (FUSE, past 64 survivors: also survivor 64 + l's) -- one record per lane in
+                // flight however many clusters the loop draws on.  Leaves the loop's survivor count
+                // and bits in round_n_next / round_bits_next, then forms the loop after it and
+                // fetches that loop's index words and the headers behind it: a whole survivor loop
+                // before the gather that needs them, so that no loop waits on two dependent loads.
                 int round_n_next = 0;
                 uint32_t round_bits_next = 0u;
-                (void)round_n_next; (void)round_bits_next;
+                float4 mine2_next = make_float4(0.f, 0.f, 0.f, 0.f);   // FUSE: survivor 64 + lane's records
+                float2 mine2b_next = make_float2(0.f, 0.f);
+                (void)round_n_next; (void)round_bits_next; (void)mine2_next; (void)mine2b_next;
                 auto gather_round = [&]() {
                     if constexpr (PLANNED) {
-                        float* const idx = &s_tile[wv][0][0].x;
-                        int p = 0;
-                        round_bits_next = e0.w;
-                        // One entry: false once the round is complete (the entry may then be left for
-                        // the next round).
-                        auto take = [&](const plan_u32x4 ent) {
-                            const uint32_t m_lo = uint32_t(__builtin_amdgcn_readfirstlane(int(ent.y)));
-                            const uint32_t m_hi = uint32_t(__builtin_amdgcn_readfirstlane(int(ent.z)));
-                            const unsigned long long m = (unsigned long long)m_lo | ((unsigned long long)m_hi << 32);
-                            const int n_e = __builtin_popcountll(m);
-                            if (p + n_e > 64) return false;   // (never a round's first entry; a sound plan never gets here)
-                            if (__builtin_amdgcn_inverse_ballot_w64(m))
-                                idx[p + int(__builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, 0u)))] =
-                                    __uint_as_float((uint32_t(__builtin_amdgcn_readfirstlane(int(ent.x))) << 6) + uint32_t(lane));
-                            p += n_e;
-                            ++plan_i;
-                            return (uint32_t(__builtin_amdgcn_readfirstlane(int(ent.w))) & 4u) == 0u && plan_i < plan_n;
-                        };
-                        // Four entries are at hand (fetched when the previous round was gathered: a
-                        // whole survivor loop ago); a longer round fetches four more at a time.
-                        while (take(e0) && take(e1) && take(e2) && take(e3)) {
-                            e0 = plan_at[plan_i]; e1 = plan_at[plan_i + 1]; e2 = plan_at[plan_i + 2]; e3 = plan_at[plan_i + 3];
-                        }
-                        e0 = plan_at[plan_i]; e1 = plan_at[plan_i + 1]; e2 = plan_at[plan_i + 2]; e3 = plan_at[plan_i + 3];
-                        round_n_next = p;
-                        // (lanes past the round's survivors read what an earlier round left: clamped
-                        // as unsigned like the rest, so in range whatever the slot or the plan holds)
-                        const int pj = int(min(__float_as_uint(idx[lane]), uint32_t(r_hi - 1)));
+                        round_n_next = loop_n;
+                        round_bits_next = uint32_t(loop_bits);
+                        // (lanes past the loop's survivors hold the next round's words, slack or
+                        // padding: clamped as unsigned like the rest, so in range whatever the plan holds)
+                        const int pj = int(min(plan_word, uint32_t(r_hi - 1)));
                         mine_next = a.A[pj];
                         if (NEED_B) mineb_next = a.B[pj];
                         if constexpr (WEIGHTED) {
 #pragma unroll
                             for (int c = 0; c < NW; ++c) mw_next[c] = a.weights[size_t(pj) * a.w_stride + c];
                         }
+                        if constexpr (FUSE) {
+                            if (loop_n > 64) {
+                                const int pj2 = int(min(plan_word2, uint32_t(r_hi - 1)));
+                                mine2_next = a.A[pj2];
+                                mine2b_next = a.B[pj2];
+                            }
+                        }
+                        plan_w += loop_n;
+                        form_loop();
                     }
                 };
                 if constexpr (PLANNED) gather_round();
@@ -1085,9 +1127,12 @@ void trace_kernel(const TraceArgs a)
                     const int round_n = round_n_next;
                     const uint32_t round_bits = round_bits_next;
                     (void)round_n; (void)round_bits;
+                    const float4 mine2 = mine2_next;
+                    const float2 mine2b = mine2b_next;
+                    (void)mine2; (void)mine2b;
                     if constexpr (PLANNED) {
-                        more = plan_i < plan_n;
-                        if (more) gather_round();   // the next round's inversion and loads, ahead of this round's loop
+                        more = loop_n > 0;
+                        if (more) gather_round();   // the next loop's loads, ahead of this loop's survivors
                     } else if (more) {
                         cnext = cg + __builtin_ctzll(cmask);
                         cmask &= cmask - 1ull;
@@ -1198,6 +1243,12 @@ void trace_kernel(const TraceArgs a)
                             if (NW > 1 && keep) tile4[66 + slot] = make_float4(sw[1], sw[2], sw[3], 0.f);
                         } else {
                         if (keep) tile4[slot] = make_float4(s1, s2, mineb.x, mineb.y);
+                        if constexpr (FUSE) {
+                            // a fused loop's survivors 64 .. round_n - 1, behind the first 64
+                            if (round_n > 64 && lane < round_n - 64)
+                                tile4[64 + lane] = make_float4(AX == 0 ? mine2.y : mine2.x, AX == 2 ? mine2.y : mine2.z,
+                                                               mine2b.x, mine2b.y);
+                        }
                         }
                     } else if (!COMPACT || keep) {
                         s_tile[wv][0][slot] = make_float2(mine.x, mine.y);
@@ -1504,7 +1555,8 @@ void trace_kernel(const TraceArgs a)
                     // instruction with the chip's clocks under this load, not by latency.)
                     constexpr bool FAT = decltype(fat_tag)::value;
                     float4 c0, c1, c2;
-                    int left = __builtin_popcountll(todo);
+                    // (FUSE: a loop of up to 128 survivors -- todo names the first 64)
+                    int left = FUSE ? round_n : __builtin_popcountll(todo);
                     const float4* t4 = tile4;
                     if constexpr (WEIGHTED && NW > 1) {
                         // weighted, several channels: the second record ({w_1, w_2, w_3} / h^2)

@@ -12,8 +12,10 @@
 // for a miss), as long as the lean and fat bits are decided on the recorded survivors, which they
 // are.  The lattice cull is applied wherever the packet's origins form a lattice, whatever the
 // batch-level flag says.
-// The recorder also groups each list's consecutive entries into dense rounds (PLAN_ROUND_END on a
-// round's last entry) and tallies what it formed in PlanCtl::stats.
+// The recorder also groups each list's consecutive entries (one cluster's survivor mask each) into
+// dense rounds and tallies what it formed in PlanCtl::stats.  It stores the cull inverted: the
+// survivors' primitive indices, contiguous per list in list order, and one header per dense round
+// (plan_header) -- the planned kernel's lane l takes index word `round's first + l`.
 #include "trace_kernel.hpp"
 
 #include <vector>
@@ -23,9 +25,10 @@ using namespace grace_hip;
 namespace {
 
 struct PlanRef {
-    uint4* entries;
-    const int2* spans;   // null: sizing pass (counts only)
-    int* counts;
+    uint32_t* idx;
+    uint32_t* hdr;
+    const int4* spans;   // null: sizing pass (counts only)
+    int4* counts;
     PlanCtl* ctl;
     int force;           // record whatever ctl->record says (the first fill)
 };
@@ -44,12 +47,24 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
     const int axis = packet_axis(ray.dx, ray.dy, ray.dz);
     const float4* const group_boxes = a.C + 2 * ((size_t(a.n_prims) + 63) >> 6) + 1;
     const int covered = min(__float_as_int(group_boxes[-1].y), a.n_prims);
-    int cnt = 0;     // lane c < SUM_CLASSES: entries of class c so far
+    int cnt = 0;     // lane c < SUM_CLASSES: entries of class c so far (t_surv: its survivors,
+                     // t_rounds: its closed rounds)
     // Rounds (the planned kernel runs one survivor loop per round): consecutive entries of a list,
     // at most 64 survivors together, all with the same lean / fat bits.  Lane c holds the open
     // round of class c -- its survivors and its bits -- and the class's tallies for PlanCtl.
     int round_n = 0, round_bits = 0;
     int t_surv = 0, t_rounds = 0, t_full = 0, t_cap = 0, t_flag = 0, t_max = 0;
+    // ... and the survivor loop of the fused consumer that the class's closed rounds have opened
+    // (planned_fuses; FUSED: the fast integral -- the exact one runs a loop per round)
+    int loop_n = 0, loop_bits = 0, t_loops = 0, t_lmax = 0;
+    auto round_closed = [&](const int n, const int bits) {   // (on the class's own lane)
+        if (FUSED && loop_n > 0 && planned_fuses(loop_n, loop_bits, plan_header(n, bits))) {
+            loop_n += n;
+        } else {
+            if (loop_n > 0) { t_loops += 1; t_lmax = max(t_lmax, loop_n); }
+            loop_n = n; loop_bits = bits;
+        }
+    };
     bool failed = axis < 0 || covered < 0;   // not an axis-aligned flat packet: no plan for this batch
     if (!failed) {
         const AxisRay ar = axis_ray(axis, ray);
@@ -143,14 +158,19 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
                         const bool close_flag = n > 0 && !close_cap && open_bits != bits;
                         const bool close = close_cap || close_flag;
                         if (pl.spans) {
-                            const int2 span = pl.spans[packet * SUM_CLASSES + cls];
-                            if (n < span.y) {
-                                if (lane == 0) {
-                                    // (the round's last entry: n - 1 < span.y held when it was written)
-                                    if (close) pl.entries[size_t(span.x) + n - 1].w = uint32_t(open_bits) | PLAN_ROUND_END;
-                                    pl.entries[size_t(span.x) + n] =
-                                        make_uint4(uint32_t(c), uint32_t(rest), uint32_t(rest >> 32), uint32_t(bits));
-                                }
+                            const int4 span = pl.spans[packet * SUM_CLASSES + cls];
+                            const int surv_at = __builtin_amdgcn_readlane(t_surv, cls);
+                            const int closed = __builtin_amdgcn_readlane(t_rounds, cls);
+                            // room for the entry's survivors, and for the header of the round it is
+                            // in (round closed + 1 if it closes one: written when that round closes)
+                            if (surv_at + n_surv <= span.z && closed + (close ? 1 : 0) < span.w) {
+                                if (close && lane == 0) pl.hdr[size_t(span.y) + closed] = plan_header(open_n, open_bits);
+                                // the lanes the mask names, at the list's running count + their rank
+                                if ((rest >> lane) & 1ull)
+                                    pl.idx[size_t(span.x) + surv_at
+                                           + int(__builtin_amdgcn_mbcnt_hi(uint32_t(rest >> 32),
+                                                                           __builtin_amdgcn_mbcnt_lo(uint32_t(rest), 0u)))] =
+                                        uint32_t(pbase + lane);
                             } else {
                                 failed = true;   // the list has outgrown its room
                             }
@@ -160,6 +180,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
                                 t_rounds += 1; t_full += open_n == 64 ? 1 : 0;
                                 t_cap += close_cap ? 1 : 0; t_flag += close_flag ? 1 : 0;
                                 t_max = max(t_max, open_n);
+                                round_closed(open_n, open_bits);
                                 round_n = 0;
                             }
                             round_n += n_surv; round_bits = bits;
@@ -175,33 +196,35 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
         cnt = 0;
         if (lane == 0) { pl.ctl->unusable = 1u; pl.ctl->usable = 0u; }
     }
-    if (lane < SUM_CLASSES) pl.counts[packet * SUM_CLASSES + lane] = cnt;
+    // (c) the end of a list closes its round (its header had room: see the entries' test)
+    if (lane < SUM_CLASSES && cnt > 0) {
+        if (pl.spans && !failed)
+            pl.hdr[size_t(pl.spans[packet * SUM_CLASSES + lane].y) + t_rounds] = plan_header(round_n, round_bits);
+        t_rounds += 1; t_full += round_n == 64 ? 1 : 0;
+        t_max = max(t_max, round_n);
+        round_closed(round_n, round_bits);
+        t_loops += 1; t_lmax = max(t_lmax, loop_n);   // ... and its loop
+    }
+    if (lane < SUM_CLASSES) pl.counts[packet * SUM_CLASSES + lane] = failed ? make_int4(0, 0, 0, 0) : make_int4(t_rounds, t_surv, cnt, 0);
     if (pl.spans && !failed) {
-        // (c) the end of a list closes its round; then the packet's tallies (the recording pass only:
-        // not a hot path, and the planned kernel never reads them)
-        for (int cls = 0; cls < SUM_CLASSES; ++cls) {
-            const int n = __builtin_amdgcn_readlane(cnt, cls);
-            const int open_bits = __builtin_amdgcn_readlane(round_bits, cls);
-            if (n > 0 && lane == 0)
-                pl.entries[size_t(pl.spans[packet * SUM_CLASSES + cls].x) + n - 1].w = uint32_t(open_bits) | PLAN_ROUND_END;
-        }
-        if (lane < SUM_CLASSES && cnt > 0) {
-            t_rounds += 1; t_full += round_n == 64 ? 1 : 0;
-            t_max = max(t_max, round_n);
-        }
+        // the packet's tallies (the recording pass only: not a hot path, and the planned kernel
+        // never reads them)
         if (lane >= SUM_CLASSES) cnt = 0;
-        int tally[6] = { cnt, t_surv, t_rounds, t_full, t_cap, t_flag };
+        int tally[7] = { cnt, t_surv, t_rounds, t_full, t_cap, t_flag, t_loops };
 #pragma unroll
         for (int off = 1; off < SUM_CLASSES; off <<= 1) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) tally[k] += __shfl_xor(tally[k], off);
+            for (int k = 0; k < 7; ++k) tally[k] += __shfl_xor(tally[k], off);
             t_max = max(t_max, __shfl_xor(t_max, off));
+            t_lmax = max(t_lmax, __shfl_xor(t_lmax, off));
         }
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 6; ++k)
                 if (tally[k]) atomicAdd(&pl.ctl->stats[k], (unsigned long long)tally[k]);
+            if (tally[6]) atomicAdd(&pl.ctl->loops, (unsigned long long)tally[6]);
             atomicMax(&pl.ctl->largest_round, uint32_t(t_max));
+            atomicMax(&pl.ctl->largest_loop, uint32_t(t_lmax));
         }
     }
 }
@@ -218,15 +241,15 @@ grace_status launch_record(const bool fast, const TraceArgs& a, const PlanRef& p
 
 grace_status plan_free_buffers(PacketPlan& pp)
 {
-    void* bufs[] = { pp.entries, pp.spans, pp.counts, pp.ctl };
+    void* bufs[] = { pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl };
     bool any = false;
     for (void* b : bufs) any = any || b;
     if (any) GRACE_TRY_HIP(hipDeviceSynchronize());
     for (void* b : bufs)
         if (b) GRACE_TRY_HIP(hipFree(b));
-    pp.entries = nullptr; pp.spans = nullptr; pp.counts = nullptr; pp.ctl = nullptr;
+    pp.idx = nullptr; pp.hdr = nullptr; pp.spans = nullptr; pp.counts = nullptr; pp.ctl = nullptr;
     pp.valid = false;
-    pp.n_lists = pp.n_entries = pp.recorded = 0;
+    pp.n_lists = pp.n_words = pp.n_hdrs = pp.recorded = 0;
     return GRACE_OK;
 }
 
@@ -258,41 +281,47 @@ grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, h
         ptr = nullptr;
         return false;
     };
-    if (n_lists * (sizeof(int) + sizeof(int2)) > ts.plan_budget) return GRACE_OK;
-    if (!alloc(pp.counts, n_lists * sizeof(int)) || !alloc(pp.spans, n_lists * sizeof(int2))
+    if (n_lists * (sizeof(int4) + sizeof(int4)) > ts.plan_budget) return GRACE_OK;
+    if (!alloc(pp.counts, n_lists * sizeof(int4)) || !alloc(pp.spans, n_lists * sizeof(int4))
         || !alloc(pp.ctl, sizeof(PlanCtl)))
         return plan_free_buffers(pp);
-    // 1. sizing pass: entries per list, and whether every packet can be planned at all
+    // 1. sizing pass: rounds, survivors and entries per list, and whether every packet can be planned at all
     GRACE_TRY_HIP(hipMemsetAsync(pp.ctl, 0, sizeof(PlanCtl), stream));
-    GRACE_TRY(launch_record(key.fast, a, PlanRef{ nullptr, nullptr, pp.counts, pp.ctl, 1 }, stream));
-    std::vector<int> counts(n_lists);
+    GRACE_TRY(launch_record(key.fast, a, PlanRef{ nullptr, nullptr, nullptr, pp.counts, pp.ctl, 1 }, stream));
+    std::vector<int4> counts(n_lists);
     PlanCtl seen = {};
-    GRACE_TRY_HIP(hipMemcpyAsync(counts.data(), pp.counts, n_lists * sizeof(int), hipMemcpyDeviceToHost, stream));
+    GRACE_TRY_HIP(hipMemcpyAsync(counts.data(), pp.counts, n_lists * sizeof(int4), hipMemcpyDeviceToHost, stream));
     GRACE_TRY_HIP(hipMemcpyAsync(&seen, pp.ctl, sizeof(seen), hipMemcpyDeviceToHost, stream));
     GRACE_TRY_HIP(hipStreamSynchronize(stream));
     if (seen.unusable) return plan_free_buffers(pp);
-    // 2. room per list: what it holds now and an eighth more, so that a re-record after a small
-    //    change of the scene or the rays still fits
-    std::vector<int2> spans(n_lists);
-    size_t total = 0, used = 0;
+    // 2. room per list, in survivors and in rounds: what it holds now and an eighth more, so that
+    //    a re-record after a small change of the scene or the rays still fits.  The rounds' room is
+    //    counted from the ENTRIES (a round holds at least one): a change that only moves lean /
+    //    fat bits, or shrinks spheres, splits rounds without adding entries, and must still fit.
+    std::vector<int4> spans(n_lists);
+    size_t words = 0, hdrs = 0, used = 0;
     for (size_t l = 0; l < n_lists; ++l) {
-        const size_t room = size_t(counts[l]) + size_t(counts[l]) / 8 + 2;
-        spans[l] = make_int2(int(total), int(room));
-        total += room;
-        used += size_t(counts[l]);
-        if (total >= (size_t(1) << 31)) return plan_free_buffers(pp);
+        const size_t surv = size_t(counts[l].y), entries = size_t(counts[l].z);
+        const size_t room_s = surv + surv / 8 + 2, room_r = entries + entries / 8 + 2;
+        spans[l] = make_int4(int(words), int(hdrs), int(room_s), int(room_r));
+        words += room_s;
+        hdrs += room_r;
+        used += surv;
+        if (words >= (size_t(1) << 31) - PLAN_IDX_PAD) return plan_free_buffers(pp);
     }
-    const size_t bytes = (total + 4) * sizeof(uint4) + n_lists * (sizeof(int) + sizeof(int2));
-    if (bytes > ts.plan_budget || !alloc(pp.entries, (total + 4) * sizeof(uint4))) return plan_free_buffers(pp);
-    GRACE_TRY_HIP(hipMemcpy(pp.spans, spans.data(), n_lists * sizeof(int2), hipMemcpyHostToDevice));
+    pp.n_lists = n_lists; pp.n_words = words; pp.n_hdrs = hdrs; pp.recorded = used;
+    if (pp.bytes() > ts.plan_budget || !alloc(pp.idx, (words + PLAN_IDX_PAD) * sizeof(uint32_t))
+        || !alloc(pp.hdr, (hdrs + PLAN_HDR_PAD) * sizeof(uint32_t)))
+        return plan_free_buffers(pp);
+    GRACE_TRY_HIP(hipMemcpy(pp.spans, spans.data(), n_lists * sizeof(int4), hipMemcpyHostToDevice));
     // (the padding the planned kernel may read past the last list)
-    GRACE_TRY_HIP(hipMemsetAsync(pp.entries + total, 0, 4 * sizeof(uint4), stream));
-    pp.n_lists = n_lists; pp.n_entries = total; pp.recorded = used;
+    GRACE_TRY_HIP(hipMemsetAsync(pp.idx + words, 0, PLAN_IDX_PAD * sizeof(uint32_t), stream));
+    GRACE_TRY_HIP(hipMemsetAsync(pp.hdr + hdrs, 0, PLAN_HDR_PAD * sizeof(uint32_t), stream));
     // 3. record
     GRACE_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&pp.ctl->usable), 1, 1, stream));
     GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[0], ts.scene.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
     GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[2], ts.rays.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
-    GRACE_TRY(launch_record(key.fast, a, PlanRef{ pp.entries, pp.spans, pp.counts, pp.ctl, 1 }, stream));
+    GRACE_TRY(launch_record(key.fast, a, PlanRef{ pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl, 1 }, stream));
     pp.valid = true;
     pp.dead = false;
     return GRACE_OK;
@@ -301,7 +330,7 @@ grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, h
 grace_status plan_record(const TraceState& ts, const TraceArgs& a, hipStream_t stream)
 {
     const PacketPlan& pp = ts.plan;
-    return launch_record(pp.key.fast, a, PlanRef{ pp.entries, pp.spans, pp.counts, pp.ctl, 0 }, stream);
+    return launch_record(pp.key.fast, a, PlanRef{ pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl, 0 }, stream);
 }
 
 grace_status launch_planned(const int mode, const bool fast, const int grid, const TraceArgs& a, hipStream_t stream)

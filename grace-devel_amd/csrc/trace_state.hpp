@@ -197,16 +197,18 @@ struct TraceArgs {
     // is enqueued; the prologue copies it into LDS (s_lut / s_lutf) and nothing else reads it.
     const double* kernel_table;
     // Packet plan (appended; see PacketPlan below; all null: no plan for this call).  List
-    // packet * SUM_CLASSES + class holds plan_counts[list] entries from plan_entries[plan_spans[list].x]
-    // on.  *plan_usable != 0: the planned kernel runs and the others return at once; 0: the reverse.
-    const uint4* plan_entries;
-    const int2* plan_spans;
-    const int* plan_counts;
+    // packet * SUM_CLASSES + class holds plan_counts[list].x dense rounds (.y survivors, .z entries): their headers from
+    // plan_hdr[plan_spans[list].y] on, their survivors' indices from plan_idx[plan_spans[list].x] on.
+    // *plan_usable != 0: the planned kernel runs and the others return at once; 0: the reverse.
+    const uint32_t* plan_idx;
+    const int4* plan_spans;
+    const int4* plan_counts;
     const uint32_t* plan_usable;
     // The planned kernel's own waves per packet (planned_split; the word next to *split_dev in the
     // call's frame; null: it takes split_dev / split like the ordinary kernels).  The combine pass
     // reads the one whose kernel ran.
     const int* plan_split_dev;
+    const uint32_t* plan_hdr;   // (appended: the fields above keep their offsets)
 };
 
 
@@ -273,12 +275,15 @@ struct RayOrder {
 // Packet plan (trace_planned.hip): the cull of an axis-aligned batch -- which groups, clusters and
 // candidates survive for each packet -- is a function of the ray order and the scene records alone,
 // the two things the caches above hold and validate.  Once both caches serve a call, the cull is
-// recorded: for every packet and summation class, the ordered list of its non-empty culling
-// rounds, 16 bytes each: {cluster, survivor mask lo, hi, flags (bit 0: lean round, bit 1: fat
-// round, bit 2: last entry of a dense round)}.  Consecutive entries of a list form a dense round:
-// at most 64 survivors together, all with the same lean / fat bits; the recorder marks each
-// round's last entry, and the planned kernel runs one survivor loop per dense round.  The planned
-// kernel (trace_kernel<.., PLANNED>) walks the lists of its classes and runs
+// recorded: for every packet and summation class, the survivors of its non-empty culling rounds
+// (entries: one cluster's survivor mask with its lean / fat bits), in list order.  Consecutive
+// entries of a list form a dense round: at most 64 survivors together, all with the same lean /
+// fat bits.  What is stored (format 3) is the cull already inverted: per list one contiguous run
+// of the survivors' primitive indices, 4 bytes each, and per dense round one 4-byte header
+// (plan_header: the round's survivor count and its bits) -- lane l of the planned kernel takes
+// index word `round's first + l`.  The planned
+// kernel (trace_kernel<.., PLANNED>) walks the lists of its classes, one coalesced index load and
+// one gather per dense round, and runs
 // the survivor loops; it makes no group pass, cluster test or cull.  The lists are per class
 // because a class is summed in ascending primitive order and nothing depends on the order between
 // classes: one plan serves every packet split K.
@@ -298,9 +303,23 @@ struct PlanCtl {                  // device memory
     // survivors, dense rounds, rounds of exactly 64 survivors, rounds closed because the next entry
     // would have passed 64, rounds closed because the next entry's lean / fat bits differed.
     unsigned long long stats[6];
+    // Survivor loops the fused consumer runs (planned_fuses) and the survivors of the largest
+    // (grace_trace_plan_loops; tallied with stats)
+    unsigned long long loops;
+    uint32_t largest_loop, pad;
 };
-constexpr uint32_t PLAN_ROUND_END = 4u;   // entry flag: the last entry of its dense round
-constexpr int PLAN_FORMAT = 2;            // 1: one round per entry; 2: dense rounds
+constexpr int PLAN_FORMAT = 3;            // 1: one round per entry; 2: dense rounds; 3: index lists
+// A dense round's header: its survivors (1 .. 64) and its bits (1: lean, 2: fat).
+__host__ __device__ inline uint32_t plan_header(const int n_surv, const int bits)
+{
+    return uint32_t(n_surv) | (uint32_t(bits) << 8);
+}
+// (the count is clamped to the wave's 64 lanes whatever the word holds: the consumer's own guard)
+__host__ __device__ inline int plan_header_count(const uint32_t h) { return int(h & 0xffu) < 64 ? int(h & 0xffu) : 64; }
+__host__ __device__ inline int plan_header_bits(const uint32_t h) { return int((h >> 8) & 3u); }
+// What the planned kernel may read past the end of a list: 64 index words with every gather (and
+// as many again for the gather issued ahead), the headers fetched ahead.
+constexpr size_t PLAN_IDX_PAD = 128, PLAN_HDR_PAD = 8;
 
 struct PlanKey {
     int format = PLAN_FORMAT;     // what the entries mean: a plan of another format is never consumed
@@ -320,12 +339,18 @@ struct PacketPlan {
     bool valid = false;           // the buffers hold a plan recorded under `key`
     bool dead = false;            // `key`'s batch cannot be planned (known on the host): nothing is launched for it
     PlanKey key;
-    uint4* entries = nullptr;     // n_entries + 4 (the planned kernel reads up to three entries ahead)
-    int2* spans = nullptr;        // per list {first entry, room}
-    int* counts = nullptr;        // per list
+    uint32_t* idx = nullptr;      // n_words + PLAN_IDX_PAD: the lists' survivor indices
+    uint32_t* hdr = nullptr;      // n_hdrs + PLAN_HDR_PAD: the lists' round headers
+    int4* spans = nullptr;        // per list {first index word, first header, room in survivors, room in rounds}
+    int4* counts = nullptr;       // per list {dense rounds, survivors, entries, -}
     PlanCtl* ctl = nullptr;
-    size_t n_lists = 0, n_entries = 0;
-    size_t recorded = 0;          // entries in use when the plan was sized
+    size_t n_lists = 0, n_words = 0, n_hdrs = 0;
+    size_t recorded = 0;          // survivors in use when the plan was sized
+    size_t bytes() const          // the device memory it takes (grace_trace_plan_bytes)
+    {
+        return (n_words + PLAN_IDX_PAD + n_hdrs + PLAN_HDR_PAD) * sizeof(uint32_t)
+            + n_lists * (sizeof(int4) + sizeof(int4)) + sizeof(PlanCtl);
+    }
 };
 
 // What the device-side gate of a call with a recorded plan needs (launch_choose_variants).
@@ -348,6 +373,21 @@ struct PlanGate {
 __host__ __device__ inline int planned_split(const int n_packets)
 {
     return n_packets <= 8192 ? SUM_CLASSES : SUM_CLASSES / 2;
+}
+
+// Survivor loops of the unweighted planned kernel with the fast integral: consecutive dense rounds
+// of a list run as ONE loop while they are test-free (lean), carry the same bits and hold at most
+// PLAN_LOOP_MAX survivors together -- a list's index words are contiguous, so the loop's second 64
+// are simply the next 64 words.  planned_fuses: does the round with header `next` join the open
+// loop of loop_n survivors and loop_bits?  The kernel forms its loops with it and the recorder
+// tallies them with it (PlanCtl::loops).  The weighted planned kernels (their occupancy is set by
+// LDS, and the longer tile would cost MODE_WCUM1 a wave per SIMD) and the exact integral (no
+// test-free loop) run one loop per dense round.
+constexpr int PLAN_LOOP_MAX = 128;
+__host__ __device__ inline bool planned_fuses(const int loop_n, const int loop_bits, const uint32_t next)
+{
+    return (loop_bits & 1) != 0 && plan_header_bits(next) == loop_bits
+        && loop_n + plan_header_count(next) <= PLAN_LOOP_MAX;
 }
 
 // trace_sph walks twice -- hit counts (for the offsets), then the per-hit pass -- and the split
@@ -401,6 +441,7 @@ struct TraceState {
     // Measurement hook (grace_trace_last_plan_used): the last class-sum launch's plan flags
     const PlanCtl* last_plan_ctl = nullptr;
     hipStream_t last_plan_stream = nullptr;
+    bool last_plan_fuses = false;          // ... and whether its planned kernel fuses rounds (planned_fuses)
 };
 
 // The TraceState of the calling thread's context (created on first use).

@@ -436,6 +436,14 @@ def plan_stats():
     return PlanStats(*[int(x) for x in v])
 
 
+def plan_loops():
+    """(loops, largest): the survivor loops the last column-density trace's planned kernel runs over
+    its plan and the survivors of the largest (zeros: it ran from none)."""
+    v = (C.c_ulonglong * 2)()
+    _check(_lib.grace_trace_plan_loops(v))
+    return int(v[0]), int(v[1])
+
+
 def set_lattice_split(k):
     _check(_lib.grace_trace_set_lattice_split(C.c_int(k)))
 
