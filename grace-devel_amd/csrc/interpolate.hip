@@ -53,6 +53,14 @@
 // rounding) have |p - x| <= h exactly for every p in [blo, bhi], hence |fl(p - x)| <= h and no wrap:
 // a cluster whose survivors all lie there on every axis runs the open loop, with the same bits.
 // Bricks and Morton cells are narrow against h, so this is the common case.
+//
+// Gradients (gradient_kernel, grace_interpolate_gradient_points_f4 / _grid_f4 and their periodic forms):
+// the same walk (interp_walk<..., GRAD = true>) -- packets, cull, staging, class swap, wrap -- with four
+// running sums per channel, {d/dx, d/dy, d/dz, value}: per contained hit one more divide (1 / r), the
+// unit vector fl(d_k / r), G = fl(f'(q) H^-4) (kernel_df, 1/H^4 staged beside 1/H and 1/H^3) and three
+// selected products per channel; at d2 == 0 the select gives +0.  GRAD_CHANNELS channels per walk
+// (DESIGN.md section 4 has the measurement behind the choice).  The value sum is the field kernel's
+// operation sequence, so the optional value output is the field call's, bit for bit.
 #include "packet_walk.hpp"
 #include "sph_kernel_f.hpp"
 
@@ -74,6 +82,8 @@ struct InterpArgs : PacketPoints, PacketScene {
     float* out;            // point p's channel c at out[p out_stride + c]
     int out_stride;
     int* counts;           // or null
+    float* grad;           // gradient walks: point p's channel c, component k at grad[(p grad_stride + c) 3 + k]
+    int grad_stride;
     unsigned long long* tests;   // measurement hook: survivor tests (lanes x survivors), or null
 };
 
@@ -106,16 +116,22 @@ __device__ __forceinline__ NoWrap no_wrap(const AxisImages& b, const float h)
              open ? __int_as_float(0x7f800000) : uniform(u - fabsf(u) * PW_SLACK) };
 }
 
-// NW = channels of this walk (0: counts only).  Args: InterpArgs, or Periodic<InterpArgs> for the
-// periodic walk.
-template <int KIND, int NW, typename Args>
-__global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
+// The walk of both kernels below.  NW = channels of this walk (0: counts only).  GRAD: every channel
+// carries four running sums {d/dx, d/dy, d/dz, value} (grace_hip.h, "SPH gradients at points") instead
+// of the value alone; sum c * NA + k of the lane is acc[c * NA + k].  Args: InterpArgs, or
+// Periodic<InterpArgs> for the periodic walk.
+template <int KIND, int NW, bool GRAD, typename Args>
+__device__ __forceinline__ void interp_walk(const Args& a)
 {
     constexpr bool PERIODIC = is_periodic<Args>::value;
-    constexpr int NS = NW > 0 ? NW : 1;
+    constexpr int NA = GRAD ? 4 : 1;                     // running sums per channel
+    constexpr int NS = NW > 0 ? NW * NA : 1;             // running sums per lane
+    constexpr int NC = NW > 0 ? NW : 1;
+    static_assert(!GRAD || NW > 0, "a gradient walk has channels");
     __shared__ float4 s_rec[PW_WAVES][64];               // survivors: {x, y, z, H^2}
     __shared__ float2 s_inv[PW_WAVES][NW > 0 ? 64 : 1];  // {1/H, 1/H^3}
-    __shared__ float s_w[PW_WAVES][NW > 0 ? 64 : 1][NS]; // weights
+    __shared__ float s_ih4[PW_WAVES][GRAD ? 64 : 1];     // 1/H^4
+    __shared__ float s_w[PW_WAVES][NW > 0 ? 64 : 1][NC]; // weights
     __shared__ float s_cls[PW_WAVES][NW > 0 ? 8 : 1][NS][64];   // class sums, per lane
 
     const PacketWave w = packet_wave();
@@ -180,7 +196,7 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
 #pragma unroll
         for (int k = 0; k < 8; ++k)
 #pragma unroll
-            for (int c = 0; c < NW; ++c) s_cls[wv][k][c][lane] = 0.0f;
+            for (int c = 0; c < NS; ++c) s_cls[wv][k][c][lane] = 0.0f;
     }
     int cur = 0;                                         // class of acc (wave-uniform)
     int count = 0;
@@ -242,6 +258,7 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
                 if constexpr (NW > 0) {
                     const float ih = 1.0f / s.w;
                     s_inv[wv][pos] = make_float2(ih, (ih * ih) * ih);
+                    if constexpr (GRAD) s_ih4[wv][pos] = (ih * ih) * (ih * ih);
 #pragma unroll
                     for (int c = 0; c < NW; ++c) s_w[wv][pos][c] = a.weights[size_t(j) * a.w_stride + c];
                 }
@@ -252,7 +269,7 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
                     const int cls = (cl >> (GRANULE_SHIFT - 6)) & (SUM_CLASSES - 1);
                     if (cls != cur) {
 #pragma unroll
-                        for (int c = 0; c < NW; ++c) {
+                        for (int c = 0; c < NS; ++c) {
                             s_cls[wv][cur][c][lane] = acc[c];
                             acc[c] = s_cls[wv][cls][c][lane];
                         }
@@ -273,7 +290,24 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
                     const float d2 = (dx * dx + dy * dy) + dz * dz;
                     if (d2 < r.w) {
                         ++count;
-                        if constexpr (NW > 0) {
+                        if constexpr (GRAD) {
+                            const float2 inv = s_inv[wv][j];
+                            const float r = sqrt_rn(d2);
+                            const float q = r * inv.x;
+                            const float W = kernel_f<KIND>(q) * inv.y;
+                            const float G = kernel_df<KIND>(q) * s_ih4[wv][j];
+                            const float ir = 1.0f / r;
+                            const float ux = dx * ir, uy = dy * ir, uz = dz * ir;
+                            const bool off = d2 > 0.0f;              // at the centre: +0, not 0 * inf
+#pragma unroll
+                            for (int c = 0; c < NW; ++c) {
+                                const float wc = s_w[wv][j][c], wG = wc * G;
+                                acc[c * NA + 0] = acc[c * NA + 0] + (off ? wG * ux : 0.0f);
+                                acc[c * NA + 1] = acc[c * NA + 1] + (off ? wG * uy : 0.0f);
+                                acc[c * NA + 2] = acc[c * NA + 2] + (off ? wG * uz : 0.0f);
+                                acc[c * NA + 3] = acc[c * NA + 3] + wc * W;
+                            }
+                        } else if constexpr (NW > 0) {
                             const float2 inv = s_inv[wv][j];
                             const float W = kernel_f<KIND>(sqrt_rn(d2) * inv.x) * inv.y;
 #pragma unroll
@@ -291,15 +325,51 @@ __global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
     if (a.counts) a.counts[slot] = count;
     if constexpr (NW > 0) {
 #pragma unroll
-        for (int c = 0; c < NW; ++c) s_cls[wv][cur][c][lane] = acc[c];
+        for (int c = 0; c < NS; ++c) s_cls[wv][cur][c][lane] = acc[c];
 #pragma unroll
-        for (int c = 0; c < NW; ++c) {
+        for (int c = 0; c < NS; ++c) {
             float t[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) t[k] = s_cls[wv][k][c][lane];
             const float s01 = t[0] + t[1], s23 = t[2] + t[3], s45 = t[4] + t[5], s67 = t[6] + t[7];
-            a.out[slot * a.out_stride + c] = (s01 + s23) + (s45 + s67);
+            const float sum = (s01 + s23) + (s45 + s67);
+            if constexpr (GRAD) {
+                if (c % NA < 3) a.grad[(slot * a.grad_stride + c / NA) * 3 + c % NA] = sum;
+                else if (a.out) a.out[slot * a.out_stride + c / NA] = sum;
+            } else {
+                a.out[slot * a.out_stride + c] = sum;
+            }
         }
+    }
+}
+
+template <int KIND, int NW, typename Args>
+__global__ __launch_bounds__(PW_BLOCK) void interpolate_kernel(const Args a)
+{
+    interp_walk<KIND, NW, false>(a);
+}
+
+// NG = gradient channels of this walk.
+template <int KIND, int NG, typename Args>
+__global__ __launch_bounds__(PW_BLOCK) void gradient_kernel(const Args a)
+{
+    interp_walk<KIND, NG, true>(a);
+}
+
+// grace_gradient_div_curl_f32: row p of g[n][3][3] is g_ck = d_k A_c.
+__global__ __launch_bounds__(256) void div_curl_kernel(const float* __restrict__ g, const int n,
+                                                       float* __restrict__ div, float* __restrict__ curl)
+{
+    const int p = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (p >= n) return;
+    float m[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) m[e] = g[size_t(p) * 9 + e];
+    if (div) div[p] = (m[0] + m[4]) + m[8];
+    if (curl) {
+        curl[size_t(p) * 3 + 0] = m[7] - m[5];           // g_zy - g_yz
+        curl[size_t(p) * 3 + 1] = m[2] - m[6];           // g_xz - g_zx
+        curl[size_t(p) * 3 + 2] = m[3] - m[1];           // g_yx - g_xy
     }
 }
 
@@ -322,14 +392,34 @@ grace_status launch_walk(const Args& a, int kind, int nw, hipStream_t stream)
     return GRACE_OK;
 }
 
-// Checks shared by both entry points, and the scene / output fields of the arguments.
+// Gradient channels per walk: GRAD_CHANNELS unless the measurement hook says otherwise
+// (grace_interpolate_gradient_channels_per_walk).
+constexpr int GRAD_CHANNELS = 2, GRAD_CHANNELS_MAX = 2;
+int g_grad_channels = GRAD_CHANNELS;
+
+template <typename Args>
+grace_status launch_gradient_walk(const Args& a, int kind, int ng, hipStream_t stream)
+{
+    const int blocks = ceil_div(size_t(a.n_packets), PW_WAVES);
+    with_kernel(kind, ng, [&](auto k, auto n) {
+        if constexpr (decltype(n)::value <= GRAD_CHANNELS_MAX)
+            gradient_kernel<decltype(k)::value, decltype(n)::value, Args><<<blocks, PW_BLOCK, 0, stream>>>(a);
+    });
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+// Checks shared by both entry points, and the scene / output fields of the arguments.  d_grad: the
+// gradient calls' (they need it, and weights); null for the field calls.
 grace_status interp_common(InterpArgs& a, const float* d_spheres, size_t n_spheres, const int* d_nodes,
                            size_t n_nodes, const int* d_leaves, const int* d_root, const float* d_weights,
-                           int n_channels, float* d_out, int* d_counts, TraceState** ts_out)
+                           int n_channels, float* d_out, int* d_counts, TraceState** ts_out,
+                           bool gradient = false, float* d_grad = nullptr)
 {
     PACKET_SCENE(a, "interpolate", false, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
-    GRACE_REQUIRE(d_out || d_counts, "interpolate: no output");
-    if (d_out) {
+    if (gradient) GRACE_REQUIRE(d_grad, "interpolate_gradient: null gradient output");
+    else GRACE_REQUIRE(d_out || d_counts, "interpolate: no output");
+    if (d_out || gradient) {
         GRACE_REQUIRE(n_channels >= 1 && n_channels <= 64, "interpolate: channels must be 1..64");
         GRACE_REQUIRE(d_weights, "interpolate: null weights");
     }
@@ -339,6 +429,7 @@ grace_status interp_common(InterpArgs& a, const float* d_spheres, size_t n_spher
                   "interpolate: a custom SPH kernel table has no kernel function f(q)");
     a.w_stride = n_channels;
     a.out_stride = n_channels;
+    a.grad_stride = n_channels;
     *ts_out = ts;
     return GRACE_OK;
 }
@@ -353,11 +444,22 @@ grace_status interp_hook(InterpArgs& a, hipStream_t stream)
     return GRACE_OK;
 }
 
-// The walks of one call: channels four at a time, counts with the first walk.
+// The walks of one call: channels four at a time, counts with the first walk.  A gradient call
+// (d_grad): g_grad_channels at a time, each walk with its channels' values (d_out, or null).
 template <typename Args>
 grace_status interp_walks(Args a, int kind, const float* d_weights, int n_channels, float* d_out,
-                          int* d_counts, hipStream_t stream)
+                          int* d_counts, hipStream_t stream, float* d_grad = nullptr)
 {
+    if (d_grad) {
+        for (int g = 0; g < n_channels; g += g_grad_channels) {
+            a.weights = d_weights + g;
+            a.grad = d_grad + 3 * size_t(g);
+            a.out = d_out ? d_out + g : nullptr;
+            a.counts = g == 0 ? d_counts : nullptr;
+            GRACE_TRY(launch_gradient_walk(a, kind, min(g_grad_channels, n_channels - g), stream));
+        }
+        return GRACE_OK;
+    }
     if (!d_out) {
         a.counts = d_counts;
         return launch_walk(a, kind, 0, stream);
@@ -371,13 +473,15 @@ grace_status interp_walks(Args a, int kind, const float* d_weights, int n_channe
     return GRACE_OK;
 }
 
-// grace_interpolate_points_f4 and its periodic form: `a` is zero but for a period.
+// grace_interpolate_points_f4, grace_interpolate_gradient_points_f4 (gradient: d_out is its d_value) and
+// their periodic forms: `a` is zero but for a period.
 template <typename Args>
 grace_status interpolate_points(Args a, const float* d_points, size_t n_points, int elems_per_point,
                                 const float* d_spheres, size_t n_spheres, const int* d_nodes,
                                 size_t n_nodes, const int* d_leaves, const int* d_root,
                                 const float* d_weights, int n_channels,
-                                float* d_out, int* d_counts, grace_stream stream)
+                                float* d_out, int* d_counts, grace_stream stream,
+                                bool gradient = false, float* d_grad = nullptr)
 {
     GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "interpolate: elements per point must be 3..16");
     GRACE_REQUIRE(n_points < (size_t(1) << 31), "interpolate: too many points");
@@ -385,23 +489,24 @@ grace_status interpolate_points(Args a, const float* d_points, size_t n_points, 
     GRACE_REQUIRE(d_points, "interpolate: null points");
     TraceState* ts = nullptr;
     GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
-                            d_out, d_counts, &ts));
+                            d_out, d_counts, &ts, gradient, d_grad));
     const hipStream_t stream_ = as_stream(stream);
     GRACE_TRY(interp_hook(a, stream_));
     return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
                       [&](Args w, size_t max_packets) -> grace_status {
         w.n_packets = int(max_packets);
-        return interp_walks(w, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_);
+        return interp_walks(w, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_, d_grad);
     });
 }
 
-// grace_interpolate_grid_f4 and its periodic form.
+// grace_interpolate_grid_f4, grace_interpolate_gradient_grid_f4 and their periodic forms.
 template <typename Args>
 grace_status interpolate_grid(Args a, const float* h_origin3, const float* h_uvw9, const int* h_dims3,
                               const float* d_spheres, size_t n_spheres, const int* d_nodes,
                               size_t n_nodes, const int* d_leaves, const int* d_root,
                               const float* d_weights, int n_channels,
-                              float* d_out, int* d_counts, grace_stream stream)
+                              float* d_out, int* d_counts, grace_stream stream,
+                              bool gradient = false, float* d_grad = nullptr)
 {
     GRACE_REQUIRE(h_origin3 && h_uvw9 && h_dims3, "interpolate_grid: null lattice argument");
     GRACE_REQUIRE(h_dims3[0] > 0 && h_dims3[1] > 0 && h_dims3[2] > 0, "interpolate_grid: dimensions must be positive");
@@ -409,7 +514,7 @@ grace_status interpolate_grid(Args a, const float* h_origin3, const float* h_uvw
     GRACE_REQUIRE(n < (size_t(1) << 31), "interpolate_grid: too many lattice points");
     TraceState* ts = nullptr;
     GRACE_TRY(interp_common(a, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root, d_weights, n_channels,
-                            d_out, d_counts, &ts));
+                            d_out, d_counts, &ts, gradient, d_grad));
     for (int d = 0; d < 3; ++d) {
         a.org[d] = h_origin3[d];
         a.eu[d] = h_uvw9[d]; a.ev[d] = h_uvw9[3 + d]; a.ew[d] = h_uvw9[6 + d];
@@ -425,7 +530,7 @@ grace_status interpolate_grid(Args a, const float* h_origin3, const float* h_uvw
     const hipStream_t stream_ = as_stream(stream);
     GRACE_TRY(interp_hook(a, stream_));
     return timed_walks(a, *ts, stream_, [&] {  // (a lattice has no packets to make)
-        return interp_walks(a, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_);
+        return interp_walks(a, ts->sph_kernel, d_weights, n_channels, d_out, d_counts, stream_, d_grad);
     });
 }
 
@@ -477,6 +582,71 @@ grace_status grace_interpolate_grid_periodic_f4(const float* h_origin3, const fl
     GRACE_TRY(walk_period(a.per, h_period3, nullptr));
     return interpolate_grid(a, h_origin3, h_uvw9, h_dims3, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves,
                             d_root, d_weights, n_channels, d_out, d_counts, stream);
+}
+
+grace_status grace_interpolate_gradient_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                  const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                  size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                  const float* d_weights, int n_channels, float* d_grad,
+                                                  float* d_value, int* d_counts, grace_stream stream)
+{
+    return interpolate_points(InterpArgs(), d_points, n_points, elems_per_point, d_spheres, n_spheres, d_nodes, n_nodes,
+                              d_leaves, d_root, d_weights, n_channels, d_value, d_counts, stream, true, d_grad);
+}
+
+grace_status grace_interpolate_gradient_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                const float* d_weights, int n_channels, float* d_grad,
+                                                float* d_value, int* d_counts, grace_stream stream)
+{
+    return interpolate_grid(InterpArgs(), h_origin3, h_uvw9, h_dims3, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves,
+                            d_root, d_weights, n_channels, d_value, d_counts, stream, true, d_grad);
+}
+
+grace_status grace_interpolate_gradient_points_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                           const float* d_spheres, size_t n_spheres,
+                                                           const int* d_nodes, size_t n_nodes, const int* d_leaves,
+                                                           const int* d_root, const float* d_weights, int n_channels,
+                                                           float* d_grad, float* d_value, int* d_counts,
+                                                           const float* h_period3, grace_stream stream)
+{
+    Periodic<InterpArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, nullptr));
+    return interpolate_points(a, d_points, n_points, elems_per_point, d_spheres, n_spheres, d_nodes, n_nodes,
+                              d_leaves, d_root, d_weights, n_channels, d_value, d_counts, stream, true, d_grad);
+}
+
+grace_status grace_interpolate_gradient_grid_periodic_f4(const float* h_origin3, const float* h_uvw9,
+                                                         const int* h_dims3, const float* d_spheres, size_t n_spheres,
+                                                         const int* d_nodes, size_t n_nodes, const int* d_leaves,
+                                                         const int* d_root, const float* d_weights, int n_channels,
+                                                         float* d_grad, float* d_value, int* d_counts,
+                                                         const float* h_period3, grace_stream stream)
+{
+    Periodic<InterpArgs> a = {};
+    GRACE_TRY(walk_period(a.per, h_period3, nullptr));
+    return interpolate_grid(a, h_origin3, h_uvw9, h_dims3, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves,
+                            d_root, d_weights, n_channels, d_value, d_counts, stream, true, d_grad);
+}
+
+grace_status grace_gradient_div_curl_f32(const float* d_grad, size_t n, float* d_div, float* d_curl,
+                                         grace_stream stream)
+{
+    GRACE_REQUIRE(d_div || d_curl, "gradient_div_curl: no output");
+    GRACE_REQUIRE(n < (size_t(1) << 31), "gradient_div_curl: too many rows");
+    if (n == 0) return GRACE_OK;
+    GRACE_REQUIRE(d_grad, "gradient_div_curl: null gradient");
+    div_curl_kernel<<<ceil_div(n, size_t(256)), 256, 0, as_stream(stream)>>>(d_grad, int(n), d_div, d_curl);
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+int grace_interpolate_gradient_channels_per_walk(int channels)
+{
+    if (channels == 0) g_grad_channels = GRAD_CHANNELS;
+    else if (channels >= 1 && channels <= GRAD_CHANNELS_MAX) g_grad_channels = channels;
+    return g_grad_channels;
 }
 
 grace_status grace_interpolate_enable_stats(int enabled)

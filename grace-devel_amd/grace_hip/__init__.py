@@ -876,6 +876,119 @@ def interpolate_last_stats():
     return v.value
 
 
+def _gradient_outputs(n_points, n_spheres, weights, grad, value, counts, device):
+    """Checks weights / grad / value / counts of a gradient call and allocates grad when it is missing."""
+    if weights is None:
+        raise ValueError("a gradient needs weights")
+    if weights.dtype != torch.float32 or weights.dim() not in (1, 2) or weights.shape[0] != n_spheres:
+        raise ValueError("weights must be float32 of shape [n_spheres] or [n_spheres, C]")
+    n_ch = 1 if weights.dim() == 1 else weights.shape[1]
+    if not 1 <= n_ch <= 64:
+        raise ValueError("weights must have 1..64 channels")
+    if value is not None:                                  # (checked like interpolate_sph's out; never allocated)
+        _, value, counts = _interp_outputs(n_points, n_spheres, weights, value, counts, device)
+    elif counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (n_points,)):
+        raise ValueError("counts must be int32 of shape [%d]" % n_points)
+    shape = (n_points, 3) if weights.dim() == 1 else (n_points, n_ch, 3)
+    if grad is None:
+        grad = torch.empty(shape, dtype=torch.float32, device=device)
+    if grad.dtype != torch.float32 or tuple(grad.shape) != shape:
+        raise ValueError("grad must be float32 of shape %s" % (shape,))
+    return n_ch, grad, value, counts
+
+
+def interpolate_gradient_sph(points, spheres, tree, weights, grad=None, value=None, counts=None, check=False,
+                             period=None):
+    """The gradient of the SPH field of interpolate_sph at points (an extension the reference lacks):
+    grad[p, c, k] = sum over spheres i containing point p of fl32(fl32(weights[i, c] * G) * n_k), with
+    G = H^-4 f'(q) of the context's SPH kernel and n the unit vector from the sphere's centre to the
+    point (at the centre itself the term is +0); containment, the wrap of a periodic box and the class
+    order of the sums are interpolate_sph's (include/grace_hip.h, "SPH gradients at points").
+    points, weights, period: as for interpolate_sph, but weights are required.  grad: float32 [n, 3] for
+    weights [n_spheres], [n, C, 3] for [n_spheres, C].  value (float32 [n] or [n, C]) and counts
+    (int32 [n]), when given, receive exactly interpolate_sph's out and counts from the same walk.
+    weights = m gives the density gradient; grad A - A grad 1 comes from a channel of m / rho * A and a
+    channel of m / rho.  Returns (grad, value, counts)."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    n_ch, grad, value, counts = _gradient_outputs(len(points), len(spheres), weights, grad, value, counts,
+                                                  points.device)
+    args = (_ptr(points), C.c_size_t(len(points)), C.c_int(points.shape[1]), *_interp_scene(spheres, tree),
+            _ptr(weights), C.c_int(n_ch), _ptr(grad), _ptr(value), _ptr(counts))
+    if period is None:
+        _check(_lib.grace_interpolate_gradient_points_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_interpolate_gradient_points_periodic_f4(*args, *_period_tail(period)))
+    if check:
+        trace_status()
+    return grad, value, counts
+
+
+def interpolate_gradient_grid_sph(origin, u, v, w, dims, spheres, tree, weights, grad=None, value=None,
+                                  counts=None, check=False, period=None):
+    """interpolate_gradient_sph over the lattice of interpolate_grid_sph.  grad: float32 [nz, ny, nx, 3]
+    or [nz, ny, nx, C, 3]; value: [nz, ny, nx] or [nz, ny, nx, C]; counts: int32 [nz, ny, nx]."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) <= 0:
+        raise ValueError("grid dimensions must be positive")
+    n = nx * ny * nz
+    flat = lambda t: None if t is None else t.view(n, *t.shape[3:])
+    n_ch, fgrad, fvalue, fcounts = _gradient_outputs(n, len(spheres), weights, flat(grad), flat(value),
+                                                     flat(counts), spheres.device)
+    o3 = (C.c_float * 3)(*[float(x) for x in origin])
+    uvw = (C.c_float * 9)(*[float(x) for x in (*u, *v, *w)])
+    d3 = (C.c_int * 3)(nx, ny, nz)
+    args = (o3, uvw, d3, *_interp_scene(spheres, tree), _ptr(weights), C.c_int(n_ch), _ptr(fgrad), _ptr(fvalue),
+            _ptr(fcounts))
+    if period is None:
+        _check(_lib.grace_interpolate_gradient_grid_f4(*args, _stream()))
+    else:
+        period = _period(period)
+        _check(_lib.grace_interpolate_gradient_grid_periodic_f4(*args, *_period_tail(period)))
+    if check:
+        trace_status()
+    grid = lambda t: None if t is None else t.view(nz, ny, nx, *t.shape[1:])
+    return grid(fgrad), grid(fvalue), grid(fcounts)
+
+
+def gradient_div_curl(grad, div=None, curl=None):
+    """Divergence and curl of a vector field from the gradient of its three channels, element-wise
+    (grace_gradient_div_curl_f32): grad float32 [n, 3, 3] with grad[p, c, k] = d_k A_c;
+    div[p] = fl(fl(g_xx + g_yy) + g_zz), curl[p] = (g_zy - g_yz, g_xz - g_zx, g_yx - g_xy).
+    Returns (div [n], curl [n, 3]), allocated when missing."""
+    if grad.dtype != torch.float32 or grad.dim() != 3 or tuple(grad.shape[1:]) != (3, 3):
+        raise ValueError("grad must be float32 of shape [n, 3, 3]")
+    grad = grad.contiguous()
+    n = len(grad)
+    if div is None:
+        div = torch.empty(n, dtype=torch.float32, device=grad.device)
+    if curl is None:
+        curl = torch.empty((n, 3), dtype=torch.float32, device=grad.device)
+    if div.dtype != torch.float32 or tuple(div.shape) != (n,) or curl.dtype != torch.float32 \
+            or tuple(curl.shape) != (n, 3):
+        raise ValueError("div must be float32 [n] and curl float32 [n, 3]")
+    _check(_lib.grace_gradient_div_curl_f32(_ptr(grad), C.c_size_t(n), _ptr(div), _ptr(curl), _stream()))
+    return div, curl
+
+
+def divergence_curl_sph(points, spheres, tree, vectors, period=None):
+    """Divergence and curl at points of the SPH vector field with the weights `vectors` (float32
+    [n_spheres, 3], e.g. m / rho * v): interpolate_gradient_sph of the three channels, then
+    gradient_div_curl.  Returns (div [n], curl [n, 3])."""
+    if vectors.dim() != 2 or vectors.shape[1] != 3:
+        raise ValueError("vectors must have shape [n_spheres, 3]")
+    grad = interpolate_gradient_sph(points, spheres, tree, vectors, period=period)[0]
+    return gradient_div_curl(grad)
+
+
+def interpolate_gradient_channels_per_walk(channels=0):
+    """Measurement hook (process-wide, results never depend on it): gradient channels per walk, 1 or 2;
+    0 restores the default.  Returns the value in effect."""
+    return int(_lib.grace_interpolate_gradient_channels_per_walk(C.c_int(channels)))
+
+
 def nearest_neighbours_sph(points, spheres, tree, k, indices=None, d2=None, check=False, period=None):
     """The k nearest sphere centres of each point (an extension the reference lacks): spheres are
     ranked by (d2, tree index), d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in fp32; row p holds

@@ -903,6 +903,65 @@ grace_status grace_interpolate_grid_f4(const float* h_origin3, const float* h_uv
 grace_status grace_interpolate_enable_stats(int enabled);
 grace_status grace_interpolate_last_stats(unsigned long long* h_survivor_tests);
 
+/* ---- SPH gradients at points (an extension the reference lacks) ---------------------------------
+ * The gradient of the field of "SPH interpolation at points" above, differentiated term by term:
+ * for point p, sphere i = {x, H} in tree order, channel c and component k in x, y, z
+ *   d_grad[(p * n_channels + c) * 3 + k] = sum over spheres i containing point p of term_ick
+ *   d_value[p * n_channels + c]          = exactly what grace_interpolate_points_f4 writes to d_out  (or NULL)
+ *   d_counts[p]                          = exactly what it writes to d_counts                        (or NULL)
+ * Containment, d, d2, ih and q are the interpolation's, bit for bit: d2 < fl(H * H), strict, and in
+ * a periodic box d wrapped once per component ("Periodic boxes" below).  NaN points and points
+ * outside every sphere get 0.
+ *
+ * New arithmetic (fp32, every operation rounded, none fused, IEEE divide and sqrt):
+ *   r = sqrt_rn(d2);  q = fl(r * ih);  E = f'(q), below;
+ *   G = fl(E * fl(fl(ih * ih) * fl(ih * ih)));                  H^-4 f'(q)
+ *   n_k = fl(d_k * fl(1 / r));                                  the unit vector, formed first
+ *   term_ick = fl(fl(w_ic * G) * n_k)        d2 > 0
+ *   term_ick = +0 for every k                d2 == 0 (a select, not 0 * inf): a point at a sphere's
+ *                                            centre gets no gradient from it; the sphere is counted.
+ * f'(q) with u = max(fl(1 - q), 0), p3(t) = fl(fl(t*t) * t), p4 as above, p5(t) = fl(p4(t) * t),
+ * p7(t) = fl(fl(p4(t) * fl(t*t)) * t), constants rounded to fp32, the normalisation of f last:
+ *   cubic:        q < 0.5 ? fl(fl(fl(18q) - 12) * q) : fl(-6 * fl(u*u))
+ *   quartic:      t2, t3 as in f;  fl(fl(fl(20 p3(t2)) - fl(4 p3(u))) - fl(40 p3(t3)))
+ *   quintic:      t2, t3 as in f;  fl(fl(fl(30 p4(t2)) - fl(5 p4(u))) - fl(75 p4(t3)))
+ *   Wendland C2:  fl(fl(-20 q) * p3(u))
+ *   Wendland C4:  fl(fl(fl(-56/3 q) * fl(fl(5q) + 1)) * p5(u))
+ *   Wendland C6:  fl(fl(fl(-22 q) * fl(fl(q * fl(fl(16q) + 7)) + 1)) * p7(u))
+ * (the fp32 f'(0) of the quartic and the quintic is a few 1e-6 of max |f'|, not 0: hence the select.)
+ * Every (c, k) is summed like a field channel: class (i >> 10) & 7, fp32 sums in ascending index
+ * within a class (a +0 term is added like any other), the 8 class sums added pairwise
+ * ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)).  The result is a function of the point and the scene only:
+ * not of the point order, elems_per_point, the entry point, the number of channels in the call or
+ * in a walk, the trace's cache knobs.
+ *
+ * weights = m gives the density gradient; the difference forms (grad A - A grad 1) combine a
+ * channel of m / rho * A with a channel of m / rho.  Points and the grid as for
+ * the interpolation.  The call needs weights, 1 <= n_channels <= 64 and a non-NULL d_grad.
+ * GRACE_INVALID_ARGUMENT, nothing written: as for the interpolation, a custom SPH kernel table
+ * included (there is no f'(q)).  Zero points: GRACE_OK.  Stack overflow, stream order, workspace and
+ * capture as for the interpolation. */
+grace_status grace_interpolate_gradient_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                  const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                  size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                  const float* d_weights, int n_channels, float* d_grad,
+                                                  float* d_value, int* d_counts, grace_stream stream);
+grace_status grace_interpolate_gradient_grid_f4(const float* h_origin3, const float* h_uvw9, const int* h_dims3,
+                                                const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                                size_t n_nodes, const int* d_leaves, const int* d_root,
+                                                const float* d_weights, int n_channels, float* d_grad,
+                                                float* d_value, int* d_counts, grace_stream stream);
+/* Divergence and curl of a vector field from the gradient of its three channels, element-wise:
+ * d_grad[(p * 3 + c) * 3 + k] = g_ck = d_k A_c (a 3-channel gradient call's output), n rows;
+ *   d_div[p]  = fl(fl(g_xx + g_yy) + g_zz)
+ *   d_curl[p * 3 + 0..2] = fl(g_zy - g_yz), fl(g_xz - g_zx), fl(g_yx - g_xy)
+ * Either output may be NULL, not both.  Stream-ordered, no allocation. */
+grace_status grace_gradient_div_curl_f32(const float* d_grad, size_t n, float* d_div, float* d_curl,
+                                         grace_stream stream);
+/* Measurement hook (process-wide, results never depend on it): gradient channels per walk, 1 or 2
+ * (DESIGN.md gives the default and why); 0 restores the default.  Returns the value in effect. */
+int grace_interpolate_gradient_channels_per_walk(int channels);
+
 /* ---- Nearest neighbours and smoothing lengths (an extension the reference lacks) ---------------
  * The k nearest sphere centres of each point, and smoothing lengths from the k-th neighbour of
  * every particle (for particles without H: dark matter, stars).
@@ -1242,6 +1301,21 @@ grace_status grace_interpolate_grid_periodic_f4(const float* h_origin3, const fl
                                                 const float* d_weights, int n_channels,
                                                 float* d_out, int* d_counts, const float* h_period3,
                                                 grace_stream stream);
+/* grace_interpolate_gradient_points_f4 / grace_interpolate_gradient_grid_f4 in a periodic box: the
+ * interpolation's wrapped d ("Interpolation" above) is the d of d2 and of the unit vector; a sphere
+ * whose H exceeds half a period contributes nothing. */
+grace_status grace_interpolate_gradient_points_periodic_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                                           const float* d_spheres, size_t n_spheres,
+                                                           const int* d_nodes, size_t n_nodes, const int* d_leaves,
+                                                           const int* d_root, const float* d_weights, int n_channels,
+                                                           float* d_grad, float* d_value, int* d_counts,
+                                                           const float* h_period3, grace_stream stream);
+grace_status grace_interpolate_gradient_grid_periodic_f4(const float* h_origin3, const float* h_uvw9,
+                                                         const int* h_dims3, const float* d_spheres, size_t n_spheres,
+                                                         const int* d_nodes, size_t n_nodes, const int* d_leaves,
+                                                         const int* d_root, const float* d_weights, int n_channels,
+                                                         float* d_grad, float* d_value, int* d_counts,
+                                                         const float* h_period3, grace_stream stream);
 
 /* ---- Periodic boxes for traces: sphere images, ray segments, folded results (an extension the
  * reference lacks)
