@@ -969,6 +969,8 @@ def gradient_div_curl(grad, div=None, curl=None):
     if div.dtype != torch.float32 or tuple(div.shape) != (n,) or curl.dtype != torch.float32 \
             or tuple(curl.shape) != (n, 3):
         raise ValueError("div must be float32 [n] and curl float32 [n, 3]")
+    if n == 0:                                             # (empty tensors have null pointers: "no output" to the library)
+        return div, curl
     _check(_lib.grace_gradient_div_curl_f32(_ptr(grad), C.c_size_t(n), _ptr(div), _ptr(curl), _stream()))
     return div, curl
 
