@@ -263,6 +263,7 @@ struct TraceBuffers {   // a call's buffers in its workspace frame (null: not ne
     // Packet plan (set by use_records): this call may use one -- both caches serve it --, under this key
     bool plan_eligible = false;
     PlanKey plan_key;
+    int plan_request = 0;   // what the call asks of the plan's layout: 0 format 3; -1 / 1 sub-tiles, automatic / forced
 };
 
 // Opens the call's frame and points `a` at its scene records and ray order, cached or derived here.
@@ -309,8 +310,18 @@ grace_status use_records(TraceState& ts, TraceArgs& a, TraceBuffers& b, FrameGua
     // (lat_split) keep it: their heaviest packets need its four waves.
     auto held = [](const CacheUse u) { return u == USE_CHECK || u == USE_TRUST; };
     b.plan_eligible = ts.plan_on && f4_sums(MODE) && held(scene_use) && held(rays_use) && p.lat_split == 0;
-    if (b.plan_eligible)
-        b.plan_key = PlanKey{ PLAN_FORMAT, p.fast_b, group_shift(n_prims), p.width, p.reorder, n_rays, n_prims, ts.scene.gen, ts.rays.gen };
+    if (b.plan_eligible) {
+        b.plan_key = PlanKey{ PLAN_FORMAT, false, p.fast_b, group_shift(n_prims), p.width, p.reorder, n_rays, n_prims, ts.scene.gen, ts.rays.gen };
+        // The sub-tile layout serves the unweighted fast kernel over full packets only; every other
+        // call asks for format 3.  A format-3 plan (or none) that this very request has already
+        // been answered with stands; otherwise the call asks for the sub-tile layout.
+        b.plan_request = !weighted(MODE) && p.fast_b && p.width == 64 ? ts.plan_subtiles : 0;
+        if (b.plan_request != 0) {
+            const PacketPlan& pp = ts.plan;
+            const bool answered = (pp.valid || pp.dead) && pp.key == b.plan_key && pp.asked == b.plan_request;
+            b.plan_key.subtiles = !answered;
+        }
+    }
     // (a recorded plan of this key: the device-side gate decides whether this call re-records it)
     PlanGate gate;
     const bool plan_steady = b.plan_eligible && ts.plan.valid && ts.plan.key == b.plan_key;
@@ -482,7 +493,7 @@ grace_status dispatch(const TraceState& ts, const TraceArgs& a, const TraceBuffe
                 // packet count -- a rule that looks at anything else must size this grid for its largest K)
                 const int grid_planned = a.plan_split_dev
                     ? ceil_div(size_t(p.n_packets) * planned_split(p.n_packets), TRACE_BLOCK / 64) : grid;
-                GRACE_TRY(launch_planned(MODE, ALT, grid_planned, a, stream));
+                GRACE_TRY(launch_planned(MODE, ALT, ts.plan.key.subtiles, grid_planned, a, stream));
                 if (p.split == 1) GRACE_TRY(combine(1, nullptr, reinterpret_cast<const int*>(a.plan_usable)));
             }
             if (p.split > 1) launch_walk<MODE, true, ALT>(grid, a, stream);
@@ -596,7 +607,9 @@ grace_status launch_trace(TraceArgs a, size_t n_rays, size_t n_spheres, size_t n
         // synchronisation, where the caches' own fills have theirs), used from then on.
         PacketPlan& pp = ts.plan;
         if (b.plan_eligible && !(pp.key == b.plan_key && (pp.valid || pp.dead)))
-            GRACE_TRY(plan_fill(ts, b.plan_key, a, stream));
+            GRACE_TRY(plan_fill(ts, b.plan_key, b.plan_request, a, stream));
+        // (a request for sub-tiles that the rule or the budget declined was answered with format 3)
+        if (b.plan_eligible && (pp.valid || pp.dead) && pp.asked == b.plan_request) b.plan_key.subtiles = pp.key.subtiles;
         ts.last_plan_ctl = nullptr;
         if (b.plan_eligible && pp.valid && pp.key == b.plan_key) {
             a.plan_idx = pp.idx; a.plan_hdr = pp.hdr; a.plan_spans = pp.spans; a.plan_counts = pp.counts;
@@ -1048,6 +1061,29 @@ grace_status grace_trace_set_plan_budget(size_t bytes)
     GRACE_TRACE_STATE();
     ts.plan_budget = bytes;
     GRACE_TRY(plan_release(ts));    // (sized again, under the new budget, by the next call it can serve)
+    return GRACE_OK;
+}
+
+grace_status grace_trace_set_plan_subtiles(int mode)
+{
+    GRACE_REQUIRE(mode >= -1 && mode <= 1, "plan sub-tiles: -1 (automatic), 0 (never) or 1 (whenever eligible)");
+    GRACE_TRACE_STATE();
+    if (ts.plan_subtiles != mode) GRACE_TRY(plan_release(ts));   // (sized again, in the layout the next call asks for)
+    ts.plan_subtiles = mode;
+    return GRACE_OK;
+}
+
+grace_status grace_trace_plan_subtiles(int* h_used, unsigned long long* h_steps, unsigned long long* h_slots)
+{
+    GRACE_REQUIRE(h_used && h_steps && h_slots, "null output");
+    *h_used = 0; *h_steps = 0; *h_slots = 0;
+    GRACE_TRACE_STATE();
+    if (ts.last_plan_ctl && ts.plan.valid && ts.plan.key.subtiles) {
+        PlanCtl h = {};
+        GRACE_TRY_HIP(hipStreamSynchronize(ts.last_plan_stream));
+        GRACE_TRY_HIP(hipMemcpy(&h, ts.last_plan_ctl, sizeof(h), hipMemcpyDeviceToHost));
+        if (h.usable != 0u) { *h_used = 1; *h_steps = h.sub_steps; *h_slots = h.sub_slots; }
+    }
     return GRACE_OK;
 }
 

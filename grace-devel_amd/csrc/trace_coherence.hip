@@ -245,6 +245,7 @@ __global__ void choose_variants_kernel(const uint32_t* __restrict__ ext12, int n
             for (int k = 0; k < 6; ++k) pc.stats[k] = 0ull;   // (the re-record tallies afresh)
             pc.largest_round = 0u;
             pc.loops = 0ull; pc.largest_loop = 0u;
+            pc.sub_steps = 0ull; pc.sub_slots = 0ull;
         }
     }
 }

@@ -346,7 +346,11 @@ struct WeightedB {
 // rounds of equal bits as ONE loop of up to 128 survivors (planned_fuses, trace_state.hpp), the
 // second 64 gathered from the next 64 index words.  It makes no group pass, no cluster test, no
 // cull, keeps no stack and has no LAT variant (the recorded indices hold the lattice cull's result).
-template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false, bool PLANNED = false>
+// SUBTILE (FUSE only): the plan is of the sub-tile layout (PLAN_FORMAT_SUBTILE, trace_state.hpp) --
+// a loop's index words are steps of four, one word per quadrant q = lane >> 4.  Gather and staging
+// are format 3's (a slot is a record); the survivor loops read slot 4 k + q at step k, through a
+// per-lane tile pointer and a stride of four records, and count steps (slots / 4).
+template <int MODE, bool SPLIT, bool ALT = false, bool LAT = false, bool PLANNED = false, bool SUBTILE = false>
 // The one-wave-per-packet hit-count / column-density kernels are held to 6 waves per SIMD (<= 80
 // VGPRs): left to itself the register allocator drifts between 77 and 102 VGPRs from one edit of
 // this file to the next, and at 5 waves per SIMD the frame kernel loses 20 % (2.9 -> 3.55 ms,
@@ -379,6 +383,9 @@ void trace_kernel(const TraceArgs a)
     // The planned kernel that fuses test-free rounds (the weighted ones do not: their occupancy is
     // set by LDS; the exact integral has no test-free loop)
     constexpr bool FUSE = PLANNED && !WEIGHTED && FAST;
+    static_assert(!SUBTILE || FUSE, "sub-tile plans: the unweighted fast planned kernel only");
+    // Records between a survivor loop's reads (a step of the sub-tile layout is four slots)
+    constexpr int STEP = SUBTILE ? 4 : 1;
     __shared__ double2 s_lut[FAST ? 1 : N_TABLE];
     // Fast integral: entry i = (y_i - i dy_i, dy_i), so that the lerp at table position b is ONE fma,
     // fma(dy_i, b, y_i - i dy_i) with i = int(b) -- no fractional part to extract.  Entries from
@@ -395,9 +402,11 @@ void trace_kernel(const TraceArgs a)
     // (66 slots: the survivor loop reads up to two slots past the round's last survivor)
     // Weighted sums add WP planes of staged weights (channels 2p, 2p + 1 in plane 3 + p).
     // FUSE: a fourth plane, so that the tile holds a fused loop's 128 + 2 sixteen-byte records
-    // (2080 of 2112 bytes).
-    __shared__ __align__(16) float2 s_tile[LDS_TILE ? TRACE_BLOCK / 64 : 1][LDS_TILE ? (FUSE ? 4 : 3 + WP) : 1][LDS_TILE ? 66 : 1];
-    static_assert(!FUSE || 4 * 66 * sizeof(float2) >= (PLAN_LOOP_MAX + 2) * sizeof(float4), "the fused loop's tile");
+    // (2080 of 2112 bytes).  SUBTILE: the two steps read past a loop's end are eight records: 68 slots
+    // per plane (2176 bytes for 128 + 8 records).
+    constexpr int TILE_SLOTS = SUBTILE ? 68 : 66;
+    __shared__ __align__(16) float2 s_tile[LDS_TILE ? TRACE_BLOCK / 64 : 1][LDS_TILE ? (FUSE ? 4 : 3 + WP) : 1][LDS_TILE ? TILE_SLOTS : 1];
+    static_assert(!FUSE || 4 * TILE_SLOTS * sizeof(float2) >= (PLAN_LOOP_MAX + 2 * STEP) * sizeof(float4), "the fused loop's tile");
     // *_D4 modes: the round's candidates as doubles, lane-indexed: {x, y, z, w w, 1/w, (1/w)^2}
     // (the division is done once per candidate by its lane, not once per survivor by the wave).
     __shared__ double s_tile_d[D4 ? TRACE_BLOCK / 64 : 1][D4 ? 64 : 1][D4 ? 6 : 1];
@@ -1090,7 +1099,8 @@ void trace_kernel(const TraceArgs a)
                         round_bits_next = uint32_t(loop_bits);
                         // (lanes past the loop's survivors hold the next round's words, slack or
                         // padding: clamped as unsigned like the rest, so in range whatever the plan holds)
-                        const int pj = int(min(plan_word, uint32_t(r_hi - 1)));
+                        // (SUBTILE: up to the null record, n_prims, which pads the shorter streams)
+                        const int pj = int(min(plan_word, uint32_t(SUBTILE ? r_hi : r_hi - 1)));
                         mine_next = a.A[pj];
                         if (NEED_B) mineb_next = a.B[pj];
                         if constexpr (WEIGHTED) {
@@ -1099,7 +1109,7 @@ void trace_kernel(const TraceArgs a)
                         }
                         if constexpr (FUSE) {
                             if (loop_n > 64) {
-                                const int pj2 = int(min(plan_word2, uint32_t(r_hi - 1)));
+                                const int pj2 = int(min(plan_word2, uint32_t(SUBTILE ? r_hi : r_hi - 1)));
                                 mine2_next = a.A[pj2];
                                 mine2b_next = a.B[pj2];
                             }
@@ -1486,6 +1496,7 @@ void trace_kernel(const TraceArgs a)
                     int at;
                     if (COMPACT) {
                         at = k++;
+                        if constexpr (SUBTILE) at = 4 * at + (lane >> 4);   // the lane's quadrant's slot of step k
                         jj = 0;
                     } else {
                         at = __builtin_ctzll(td);
@@ -1521,7 +1532,9 @@ void trace_kernel(const TraceArgs a)
                     float4 c0, c1, c2;
                     BRec b0 = make_float2(0.f, 0.f), b1 = b0, b2 = b0;
                     int j0, j1 = 0, j2 = 0;
+                    // (SUBTILE: steps; at least one whatever the header holds -- the loop counts down to 0)
                     int left = __builtin_popcountll(todo);
+                    if constexpr (SUBTILE) left = max(round_n >> 2, 1);
                     unsigned long long td = todo | 0x8000000000000000ull;
                     int k = 0;
                     fetch(td, k, c0, b0, j0);
@@ -1556,8 +1569,10 @@ void trace_kernel(const TraceArgs a)
                     constexpr bool FAT = decltype(fat_tag)::value;
                     float4 c0, c1, c2;
                     // (FUSE: a loop of up to 128 survivors -- todo names the first 64)
+                    // (SUBTILE: steps, at least one; the lane's quadrant's record of each step)
                     int left = FUSE ? round_n : __builtin_popcountll(todo);
                     const float4* t4 = tile4;
+                    if constexpr (SUBTILE) { left = max(round_n >> 2, 1); t4 = tile4 + (lane >> 4); }
                     if constexpr (WEIGHTED && NW > 1) {
                         // weighted, several channels: the second record ({w_1, w_2, w_3} / h^2)
                         // read beside the first, one survivor ahead
@@ -1593,18 +1608,18 @@ void trace_kernel(const TraceArgs a)
                         else sum = __builtin_fmaf(__builtin_fmaf(y.y, b, y.x), c.w, sum);
                     };
                     c0 = t4[0]; __builtin_amdgcn_sched_barrier(0);
-                    c1 = t4[1]; __builtin_amdgcn_sched_barrier(0);
+                    c1 = t4[STEP]; __builtin_amdgcn_sched_barrier(0);
                     for (;;) {
-                        c2 = t4[2]; __builtin_amdgcn_sched_barrier(0);
+                        c2 = t4[2 * STEP]; __builtin_amdgcn_sched_barrier(0);
                         proc(c0);
                         if (--left == 0) break;
-                        c0 = t4[3]; __builtin_amdgcn_sched_barrier(0);
+                        c0 = t4[3 * STEP]; __builtin_amdgcn_sched_barrier(0);
                         proc(c1);
                         if (--left == 0) break;
-                        c1 = t4[4]; __builtin_amdgcn_sched_barrier(0);
+                        c1 = t4[4 * STEP]; __builtin_amdgcn_sched_barrier(0);
                         proc(c2);
                         if (--left == 0) break;
-                        t4 += 3;
+                        t4 += 3 * STEP;
                     }
                 };
                 if constexpr (LEAN4) {

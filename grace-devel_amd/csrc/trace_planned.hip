@@ -16,6 +16,11 @@
 // dense rounds and tallies what it formed in PlanCtl::stats.  It stores the cull inverted: the
 // survivors' primitive indices, contiguous per list in list order, and one header per dense round
 // (plan_header) -- the planned kernel's lane l takes index word `round's first + l`.
+// SUB: the sub-tile layout (PLAN_FORMAT_SUBTILE, trace_state.hpp).  The packet set-up also forms the
+// origin rectangle of each quadrant (lanes 16 q .. 16 q + 15); every entry's packet-level mask is
+// cut into four sub-masks by the same bound against those rectangles, and each quadrant appends its
+// survivors to a stream of its own.  Rounds are runs of PLAN_SUB_ROUND_STEPS steps; the streams
+// drift apart, so an entry's bits are ANDed into every round its words fall in.
 #include "trace_kernel.hpp"
 
 #include <vector>
@@ -33,9 +38,10 @@ struct PlanRef {
     int force;           // record whatever ctl->record says (the first fill)
 };
 
-template <bool FUSED>
+template <bool FUSED, bool SUB = false>
 __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArgs a, const PlanRef pl)
 {
+    static_assert(!SUB || FUSED, "sub-tile plans: the fast integral only");
     __shared__ float s_lat[TRACE_BLOCK / 64][2][8];   // the packets' origin lattices
     if (pl.spans && !pl.force && pl.ctl->record == 0u) return;   // (workgroup-uniform)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -57,6 +63,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
     // ... and the survivor loop of the fused consumer that the class's closed rounds have opened
     // (planned_fuses; FUSED: the fast integral -- the exact one runs a loop per round)
     int loop_n = 0, loop_bits = 0, t_loops = 0, t_lmax = 0;
+    // SUB: lane 4 c + q holds the steps of class c's stream of quadrant q so far; lane c the rounds
+    // of class c whose header has been started
+    int sub_pos = 0, sub_touched = 0;
+    (void)sub_pos; (void)sub_touched;
     auto round_closed = [&](const int n, const int bits) {   // (on the class's own lane)
         if (FUSED && loop_n > 0 && planned_fuses(loop_n, loop_bits, plan_header(n, bits))) {
             loop_n += n;
@@ -80,6 +90,28 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
         float cell2;
         build_origin_lattice(ar.o1, ar.o2, lane, s_lat, lat_ok, cell2);
         const float lat_r2 = lat_ok ? cell2 : 0.f;
+        // SUB: the quadrants' origin rectangles, from their own valid lanes (each row of 16 lanes
+        // reduces its own); a quadrant without a valid ray keeps nothing
+        float qlo1[4] = {}, qhi1[4] = {}, qlo2[4] = {}, qhi2[4] = {};
+        unsigned long long q_lanes[4] = {};
+        if constexpr (SUB) {
+            float m1 = ray.valid ? ar.o1 : INFINITY, x1 = ray.valid ? ar.o1 : -INFINITY;
+            float m2 = ray.valid ? ar.o2 : INFINITY, x2 = ray.valid ? ar.o2 : -INFINITY;
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) {
+                m1 = fminf(m1, __shfl_xor(m1, off)); x1 = fmaxf(x1, __shfl_xor(x1, off));
+                m2 = fminf(m2, __shfl_xor(m2, off)); x2 = fmaxf(x2, __shfl_xor(x2, off));
+            }
+            const unsigned long long valid_lanes = __builtin_amdgcn_ballot_w64(ray.valid);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                qlo1[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m1), 16 * q));
+                qhi1[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x1), 16 * q));
+                qlo2[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m2), 16 * q));
+                qhi2[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x2), 16 * q));
+                q_lanes[q] = ((valid_lanes >> (16 * q)) & 0xffffull) != 0ull ? ~0ull : 0ull;
+            }
+        }
 
         // a box against the packet's origin rectangle (and, for groups, its extent along the axis)
         auto box_may_hit = [&](const float4 blo, const float4 bhi, const bool along) {
@@ -152,6 +184,46 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
                         // the class's open round takes this entry, or closes before it: (a) past 64
                         // survivors with it, (b) other lean / fat bits
                         const int n_surv = __builtin_popcountll(rest);
+                        if constexpr (SUB) {
+                            const int4 span = pl.spans ? pl.spans[packet * SUM_CLASSES + cls] : make_int4(0, 0, 0, 0);
+                            int touched = __builtin_amdgcn_readlane(sub_touched, cls);
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                // the same bound against the quadrant's rectangle (negated: a NaN
+                                // centre or bound stays in every quadrant)
+                                const float u1 = s1 - __builtin_amdgcn_fmed3f(s1, qlo1[q], qhi1[q]);
+                                const float u2 = s2 - __builtin_amdgcn_fmed3f(s2, qlo2[q], qhi2[q]);
+                                const unsigned long long rest_q =
+                                    __builtin_amdgcn_ballot_w64(!(__builtin_fmaf(u1, u1, u2 * u2) >= mine.w)) & rest & q_lanes[q];
+                                if (rest_q == 0ull) continue;
+                                const int n_q = __builtin_popcountll(rest_q);
+                                const int at = __builtin_amdgcn_readlane(sub_pos, 4 * cls + q);
+                                const int r_first = at / PLAN_SUB_ROUND_STEPS, r_last = (at + n_q - 1) / PLAN_SUB_ROUND_STEPS;
+                                if (pl.spans) {
+                                    // room for the quadrant's words and for the headers of the rounds they fall in
+                                    if (at + n_q <= span.z && r_last < span.w) {
+                                        if ((rest_q >> lane) & 1ull)
+                                            pl.idx[size_t(span.x) + 4 * size_t(at + int(__builtin_amdgcn_mbcnt_hi(uint32_t(rest_q >> 32),
+                                                                                           __builtin_amdgcn_mbcnt_lo(uint32_t(rest_q), 0u)))) + q] =
+                                                uint32_t(pbase + lane);
+                                        // (headers are read and written by lane 0 alone, in program order;
+                                        // counts are set when the list ends)
+                                        if (lane == 0) {
+                                            for (int r = r_first; r <= r_last; ++r) {
+                                                uint32_t* const h = pl.hdr + size_t(span.y) + r;
+                                                *h = plan_header(64, r < touched ? bits & plan_header_bits(*h) : bits);
+                                            }
+                                        }
+                                    } else {
+                                        failed = true;   // the list has outgrown its room
+                                    }
+                                }
+                                touched = max(touched, r_last + 1);
+                                if (lane == 4 * cls + q) sub_pos += n_q;
+                            }
+                            if (lane == cls) { sub_touched = touched; t_surv += n_surv; cnt += 1; }
+                            continue;
+                        }
                         const int open_n = __builtin_amdgcn_readlane(round_n, cls);
                         const int open_bits = __builtin_amdgcn_readlane(round_bits, cls);
                         const bool close_cap = n > 0 && open_n + n_surv > 64;
@@ -196,8 +268,53 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
         cnt = 0;
         if (lane == 0) { pl.ctl->unusable = 1u; pl.ctl->usable = 0u; }
     }
+    // SUB: the end of a list pads its shorter streams with the null record up to the longest, sets
+    // the round counts (every round PLAN_SUB_ROUND_STEPS steps, the last what is left) and tallies
+    // the list's rounds and loops
+    int sub_steps = 0, sub_real = 0;   // lane c: class c's steps, and its streams' real words
+    if constexpr (SUB) {
+        for (int c = 0; c < SUM_CLASSES; ++c) {
+            int steps = 0, real = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int n = failed ? 0 : __builtin_amdgcn_readlane(sub_pos, 4 * c + q);
+                steps = max(steps, n); real += n;
+            }
+            const int rounds = (steps + PLAN_SUB_ROUND_STEPS - 1) / PLAN_SUB_ROUND_STEPS;
+            int loops = 0, lmax = 0;
+            if (pl.spans && steps > 0) {
+                const int4 span = pl.spans[packet * SUM_CLASSES + c];   // (steps <= span.z, rounds <= span.w: the entries' tests)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    for (int t = __builtin_amdgcn_readlane(sub_pos, 4 * c + q) + lane; t < steps; t += 64)
+                        pl.idx[size_t(span.x) + 4 * size_t(t) + q] = uint32_t(a.n_prims);
+                if (lane == 0) {
+                    uint32_t* const h = pl.hdr + size_t(span.y);
+                    h[rounds - 1] = plan_header(4 * (steps - (rounds - 1) * PLAN_SUB_ROUND_STEPS), plan_header_bits(h[rounds - 1]));
+                    int ln = 0, lb = 0;
+                    for (int r = 0; r < rounds; ++r) {
+                        const uint32_t next = h[r];
+                        if (ln > 0 && planned_fuses(ln, lb, next)) {
+                            ln += plan_header_count(next);
+                        } else {
+                            if (ln > 0) { loops += 1; lmax = max(lmax, ln); }
+                            ln = plan_header_count(next); lb = plan_header_bits(next);
+                        }
+                    }
+                    loops += 1; lmax = max(lmax, ln);
+                }
+                loops = __builtin_amdgcn_readlane(loops, 0); lmax = __builtin_amdgcn_readlane(lmax, 0);
+            }
+            if (lane == c) {
+                t_rounds = rounds; t_full = steps / PLAN_SUB_ROUND_STEPS;
+                t_max = min(4 * steps, 4 * PLAN_SUB_ROUND_STEPS);
+                t_loops = loops; t_lmax = lmax;
+                sub_steps = steps; sub_real = real;
+            }
+        }
+    }
     // (c) the end of a list closes its round (its header had room: see the entries' test)
-    if (lane < SUM_CLASSES && cnt > 0) {
+    if (!SUB && lane < SUM_CLASSES && cnt > 0) {
         if (pl.spans && !failed)
             pl.hdr[size_t(pl.spans[packet * SUM_CLASSES + lane].y) + t_rounds] = plan_header(round_n, round_bits);
         t_rounds += 1; t_full += round_n == 64 ? 1 : 0;
@@ -205,7 +322,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
         round_closed(round_n, round_bits);
         t_loops += 1; t_lmax = max(t_lmax, loop_n);   // ... and its loop
     }
-    if (lane < SUM_CLASSES) pl.counts[packet * SUM_CLASSES + lane] = failed ? make_int4(0, 0, 0, 0) : make_int4(t_rounds, t_surv, cnt, 0);
+    if (lane < SUM_CLASSES) pl.counts[packet * SUM_CLASSES + lane] = failed ? make_int4(0, 0, 0, 0) : make_int4(t_rounds, t_surv, cnt, sub_steps);
     if (pl.spans && !failed) {
         // the packet's tallies (the recording pass only: not a hot path, and the planned kernel
         // never reads them)
@@ -217,23 +334,27 @@ __global__ __launch_bounds__(TRACE_BLOCK) void plan_record_kernel(const TraceArg
             for (int k = 0; k < 7; ++k) tally[k] += __shfl_xor(tally[k], off);
             t_max = max(t_max, __shfl_xor(t_max, off));
             t_lmax = max(t_lmax, __shfl_xor(t_lmax, off));
+            if constexpr (SUB) { sub_steps += __shfl_xor(sub_steps, off); sub_real += __shfl_xor(sub_real, off); }
         }
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 6; ++k)
                 if (tally[k]) atomicAdd(&pl.ctl->stats[k], (unsigned long long)tally[k]);
             if (tally[6]) atomicAdd(&pl.ctl->loops, (unsigned long long)tally[6]);
+            if (SUB && sub_steps) atomicAdd(&pl.ctl->sub_steps, (unsigned long long)sub_steps);
+            if (SUB && sub_real) atomicAdd(&pl.ctl->sub_slots, (unsigned long long)sub_real);
             atomicMax(&pl.ctl->largest_round, uint32_t(t_max));
             atomicMax(&pl.ctl->largest_loop, uint32_t(t_lmax));
         }
     }
 }
 
-grace_status launch_record(const bool fast, const TraceArgs& a, const PlanRef& pl, hipStream_t stream)
+grace_status launch_record(const bool fast, const bool subtiles, const TraceArgs& a, const PlanRef& pl, hipStream_t stream)
 {
     const int n_packets = (a.n_rays + a.width - 1) / a.width;
     const int grid = ceil_div(size_t(n_packets), size_t(TRACE_BLOCK / 64));
-    if (fast) plan_record_kernel<true><<<grid, TRACE_BLOCK, 0, stream>>>(a, pl);
+    if (subtiles) plan_record_kernel<true, true><<<grid, TRACE_BLOCK, 0, stream>>>(a, pl);
+    else if (fast) plan_record_kernel<true><<<grid, TRACE_BLOCK, 0, stream>>>(a, pl);
     else plan_record_kernel<false><<<grid, TRACE_BLOCK, 0, stream>>>(a, pl);
     GRACE_CHECK_LAUNCH();
     return GRACE_OK;
@@ -250,6 +371,7 @@ grace_status plan_free_buffers(PacketPlan& pp)
     pp.idx = nullptr; pp.hdr = nullptr; pp.spans = nullptr; pp.counts = nullptr; pp.ctl = nullptr;
     pp.valid = false;
     pp.n_lists = pp.n_words = pp.n_hdrs = pp.recorded = 0;
+    pp.key.subtiles = false;
     return GRACE_OK;
 }
 
@@ -265,12 +387,14 @@ grace_status plan_release(TraceState& ts)
     return GRACE_OK;
 }
 
-grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, hipStream_t stream)
+grace_status plan_fill(TraceState& ts, const PlanKey& key, const int request, const TraceArgs& a, hipStream_t stream)
 {
     PacketPlan& pp = ts.plan;
     GRACE_TRY(plan_free_buffers(pp));
     ts.last_plan_ctl = nullptr;
     pp.key = key;
+    pp.key.subtiles = false;
+    pp.asked = request;
     pp.dead = true;      // until the plan stands
     const int n_packets = (a.n_rays + a.width - 1) / a.width;
     const size_t n_lists = size_t(n_packets) * SUM_CLASSES;
@@ -285,56 +409,86 @@ grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, h
     if (!alloc(pp.counts, n_lists * sizeof(int4)) || !alloc(pp.spans, n_lists * sizeof(int4))
         || !alloc(pp.ctl, sizeof(PlanCtl)))
         return plan_free_buffers(pp);
-    // 1. sizing pass: rounds, survivors and entries per list, and whether every packet can be planned at all
-    GRACE_TRY_HIP(hipMemsetAsync(pp.ctl, 0, sizeof(PlanCtl), stream));
-    GRACE_TRY(launch_record(key.fast, a, PlanRef{ nullptr, nullptr, nullptr, pp.counts, pp.ctl, 1 }, stream));
-    std::vector<int4> counts(n_lists);
-    PlanCtl seen = {};
-    GRACE_TRY_HIP(hipMemcpyAsync(counts.data(), pp.counts, n_lists * sizeof(int4), hipMemcpyDeviceToHost, stream));
-    GRACE_TRY_HIP(hipMemcpyAsync(&seen, pp.ctl, sizeof(seen), hipMemcpyDeviceToHost, stream));
-    GRACE_TRY_HIP(hipStreamSynchronize(stream));
-    if (seen.unusable) return plan_free_buffers(pp);
-    // 2. room per list, in survivors and in rounds: what it holds now and an eighth more, so that
-    //    a re-record after a small change of the scene or the rays still fits.  The rounds' room is
-    //    counted from the ENTRIES (a round holds at least one): a change that only moves lean /
-    //    fat bits, or shrinks spheres, splits rounds without adding entries, and must still fit.
-    std::vector<int4> spans(n_lists);
-    size_t words = 0, hdrs = 0, used = 0;
-    for (size_t l = 0; l < n_lists; ++l) {
-        const size_t surv = size_t(counts[l].y), entries = size_t(counts[l].z);
-        const size_t room_s = surv + surv / 8 + 2, room_r = entries + entries / 8 + 2;
-        spans[l] = make_int4(int(words), int(hdrs), int(room_s), int(room_r));
-        words += room_s;
-        hdrs += room_r;
-        used += surv;
-        if (words >= (size_t(1) << 31) - PLAN_IDX_PAD) return plan_free_buffers(pp);
+    std::vector<int4> counts(n_lists), spans(n_lists);
+    // The sub-tile layout first, where the call asks for it (only fast, unweighted calls over full
+    // packets do: use_records), then format 3: whichever is sized, fits and -- automatic -- pays.
+    for (int sub = request != 0 && key.fast && a.width == 64 ? 1 : 0; sub >= 0; --sub) {
+        // 1. sizing pass: rounds, survivors and entries per list (sub-tile layout: and steps), and
+        //    whether every packet can be planned at all
+        GRACE_TRY_HIP(hipMemsetAsync(pp.ctl, 0, sizeof(PlanCtl), stream));
+        GRACE_TRY(launch_record(key.fast, sub != 0, a, PlanRef{ nullptr, nullptr, nullptr, pp.counts, pp.ctl, 1 }, stream));
+        PlanCtl seen = {};
+        GRACE_TRY_HIP(hipMemcpyAsync(counts.data(), pp.counts, n_lists * sizeof(int4), hipMemcpyDeviceToHost, stream));
+        GRACE_TRY_HIP(hipMemcpyAsync(&seen, pp.ctl, sizeof(seen), hipMemcpyDeviceToHost, stream));
+        GRACE_TRY_HIP(hipStreamSynchronize(stream));
+        if (seen.unusable) return plan_free_buffers(pp);
+        // 2. room per list, in survivors and in rounds: what it holds now and an eighth more, so that
+        //    a re-record after a small change of the scene or the rays still fits.  The rounds' room is
+        //    counted from the ENTRIES (a round holds at least one): a change that only moves lean /
+        //    fat bits, or shrinks spheres, splits rounds without adding entries, and must still fit.
+        //    Sub-tile layout: room in steps, the longest stream and an eighth more, four words each;
+        //    the rounds' room is what those steps can make.
+        size_t words = 0, hdrs = 0, used = 0, steps = 0;
+        bool fits = true;
+        for (size_t l = 0; l < n_lists && fits; ++l) {
+            const size_t surv = size_t(counts[l].y), entries = size_t(counts[l].z), len = size_t(counts[l].w);
+            const size_t room_s = sub ? len + len / 8 + 2 : surv + surv / 8 + 2;
+            const size_t room_r = sub ? (room_s + PLAN_SUB_ROUND_STEPS - 1) / PLAN_SUB_ROUND_STEPS : entries + entries / 8 + 2;
+            spans[l] = make_int4(int(words), int(hdrs), int(room_s), int(room_r));
+            words += sub ? 4 * room_s : room_s;
+            hdrs += room_r;
+            used += surv;
+            steps += len;
+            fits = words < (size_t(1) << 31) - PLAN_IDX_PAD;
+        }
+        pp.n_lists = n_lists; pp.n_words = words; pp.n_hdrs = hdrs; pp.recorded = used;
+        fits = fits && pp.bytes() <= ts.plan_budget;
+        if (sub) {
+            // the automatic rule: enough packets, and streams that drop enough of the survivors' steps
+            const bool pays = n_packets >= PLAN_SUB_MIN_PACKETS && double(steps) < PLAN_SUB_MAX_RATIO * double(used);
+            if (!fits || (request < 0 && !pays)) continue;
+        }
+        if (!fits || !alloc(pp.idx, (words + PLAN_IDX_PAD) * sizeof(uint32_t))
+            || !alloc(pp.hdr, (hdrs + PLAN_HDR_PAD) * sizeof(uint32_t))) {
+            if (sub) {   // (no memory for this layout: format 3 may still fit)
+                if (pp.idx) { GRACE_TRY_HIP(hipFree(pp.idx)); pp.idx = nullptr; }
+                continue;
+            }
+            return plan_free_buffers(pp);
+        }
+        GRACE_TRY_HIP(hipMemcpy(pp.spans, spans.data(), n_lists * sizeof(int4), hipMemcpyHostToDevice));
+        // (the padding the planned kernel may read past the last list)
+        GRACE_TRY_HIP(hipMemsetAsync(pp.idx + words, 0, PLAN_IDX_PAD * sizeof(uint32_t), stream));
+        GRACE_TRY_HIP(hipMemsetAsync(pp.hdr + hdrs, 0, PLAN_HDR_PAD * sizeof(uint32_t), stream));
+        // 3. record
+        pp.key.subtiles = sub != 0;
+        GRACE_TRY_HIP(hipMemsetAsync(pp.ctl, 0, sizeof(PlanCtl), stream));   // (the sizing pass's tallies)
+        GRACE_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&pp.ctl->usable), 1, 1, stream));
+        GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[0], ts.scene.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
+        GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[2], ts.rays.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
+        GRACE_TRY(launch_record(key.fast, sub != 0, a, PlanRef{ pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl, 1 }, stream));
+        pp.valid = true;
+        pp.dead = false;
+        return GRACE_OK;
     }
-    pp.n_lists = n_lists; pp.n_words = words; pp.n_hdrs = hdrs; pp.recorded = used;
-    if (pp.bytes() > ts.plan_budget || !alloc(pp.idx, (words + PLAN_IDX_PAD) * sizeof(uint32_t))
-        || !alloc(pp.hdr, (hdrs + PLAN_HDR_PAD) * sizeof(uint32_t)))
-        return plan_free_buffers(pp);
-    GRACE_TRY_HIP(hipMemcpy(pp.spans, spans.data(), n_lists * sizeof(int4), hipMemcpyHostToDevice));
-    // (the padding the planned kernel may read past the last list)
-    GRACE_TRY_HIP(hipMemsetAsync(pp.idx + words, 0, PLAN_IDX_PAD * sizeof(uint32_t), stream));
-    GRACE_TRY_HIP(hipMemsetAsync(pp.hdr + hdrs, 0, PLAN_HDR_PAD * sizeof(uint32_t), stream));
-    // 3. record
-    GRACE_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&pp.ctl->usable), 1, 1, stream));
-    GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[0], ts.scene.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
-    GRACE_TRY_HIP(hipMemcpyAsync(&pp.ctl->sig[2], ts.rays.ctl->sig, 16, hipMemcpyDeviceToDevice, stream));
-    GRACE_TRY(launch_record(key.fast, a, PlanRef{ pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl, 1 }, stream));
-    pp.valid = true;
-    pp.dead = false;
-    return GRACE_OK;
+    return GRACE_OK;   // (not reached: the format-3 pass returns)
 }
 
 grace_status plan_record(const TraceState& ts, const TraceArgs& a, hipStream_t stream)
 {
     const PacketPlan& pp = ts.plan;
-    return launch_record(pp.key.fast, a, PlanRef{ pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl, 0 }, stream);
+    return launch_record(pp.key.fast, pp.key.subtiles, a, PlanRef{ pp.idx, pp.hdr, pp.spans, pp.counts, pp.ctl, 0 }, stream);
 }
 
-grace_status launch_planned(const int mode, const bool fast, const int grid, const TraceArgs& a, hipStream_t stream)
+grace_status launch_planned(const int mode, const bool fast, const bool subtiles, const int grid, const TraceArgs& a, hipStream_t stream)
 {
+    if (subtiles) {
+        if (mode != MODE_CUMULATIVE || !fast)
+            return set_error(GRACE_INVALID_ARGUMENT, __FILE__, __LINE__, "no sub-tile planned kernel for this mode");
+        trace_kernel<MODE_CUMULATIVE, true, true, false, true, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);
+        GRACE_CHECK_LAUNCH();
+        return GRACE_OK;
+    }
     auto go = [&](auto mode_tag) {
         constexpr int MODE = decltype(mode_tag)::value;
         if (fast) trace_kernel<MODE, true, true, false, true><<<grid, TRACE_BLOCK, 0, stream>>>(a);

@@ -92,6 +92,10 @@ __global__ __launch_bounds__(256) void trace_prepass_kernel(const float4* __rest
             // candidate the ray misses: keep that product 0 when 1/h^2 overflows (h < 5e-20).
             b50 = make_float2(ir * float(N_TABLE - 1), fminf(ir * ir, 3.4028234664e38f));
         }
+        // Record n is the NULL RECORD that pads the streams of a sub-tile packet plan
+        // (PLAN_FORMAT_SUBTILE, trace_state.hpp): h^2 = +inf with 1/h terms of 0 -- whatever the
+        // ray, its term is (a finite table value) * 0.
+        if (i == n) a.w = INFINITY;
         if (i < n + 4) {
             A[i] = a;
             if (B1) B1[i] = b1;

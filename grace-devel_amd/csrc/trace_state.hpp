@@ -307,8 +307,28 @@ struct PlanCtl {                  // device memory
     // (grace_trace_plan_loops; tallied with stats)
     unsigned long long loops;
     uint32_t largest_loop, pad;
+    // Sub-tile layout only (grace_trace_plan_subtiles; tallied with stats): the lists' steps, and the
+    // index words of their four streams that name a survivor (the rest name the null record)
+    unsigned long long sub_steps, sub_slots;
 };
 constexpr int PLAN_FORMAT = 3;            // 1: one round per entry; 2: dense rounds; 3: index lists
+// Format 4, the SUB-TILE layout of format 3 (unweighted fast kernel only; PlanKey::subtiles): a
+// packet's 64 lanes are four quadrants of 16, q = lane >> 4, and each quadrant has a survivor
+// stream of its own per list -- the list's survivors that can reach the quadrant's own origin
+// rectangle, in the list's (ascending) order.  A list stores STEPS: step t is four index words,
+// quadrant q's at `list base + 4 t + q`; a stream shorter than the list's longest is padded at its
+// end with the index of the scene's NULL RECORD, n_prims (A = (0, 0, 0, +inf), B50 = (0, 0): its
+// term is fma(t, 0, sum) = sum, at table position 0).  Headers, dense rounds and planned_fuses work
+// on SLOTS (4 per step): a dense round is PLAN_SUB_ROUND_STEPS consecutive steps (the list's last:
+// what is left), its bits the AND over every real survivor in its slots.  The consumer gathers
+// and stages exactly as in format 3 -- lane l takes index word l, record l goes to tile slot l --
+// and its survivor loops read slot 4 k + q at step k.
+constexpr int PLAN_FORMAT_SUBTILE = 4;
+constexpr int PLAN_SUB_ROUND_STEPS = 16;
+// Below this many packets the automatic rule keeps format 3 (plan_fill; never under 1024) ...
+constexpr int PLAN_SUB_MIN_PACKETS = 1024;
+// ... and so it does when the steps are more than this fraction of the survivors.
+constexpr double PLAN_SUB_MAX_RATIO = 0.82;
 // A dense round's header: its survivors (1 .. 64) and its bits (1: lean, 2: fat).
 __host__ __device__ inline uint32_t plan_header(const int n_surv, const int bits)
 {
@@ -323,6 +343,7 @@ constexpr size_t PLAN_IDX_PAD = 128, PLAN_HDR_PAD = 8;
 
 struct PlanKey {
     int format = PLAN_FORMAT;     // what the entries mean: a plan of another format is never consumed
+    bool subtiles = false;        // the sub-tile layout (PLAN_FORMAT_SUBTILE)
     bool fast = false;            // axis_beam_may_hit<AX, FUSED> bounds the b^2 the survivors compute
     int group_shift = 0, width = 0;
     bool reorder = false;
@@ -330,7 +351,7 @@ struct PlanKey {
     unsigned long long scene_gen = 0, rays_gen = 0;
     bool operator==(const PlanKey& o) const
     {
-        return format == o.format && fast == o.fast && group_shift == o.group_shift && width == o.width && reorder == o.reorder
+        return format == o.format && subtiles == o.subtiles && fast == o.fast && group_shift == o.group_shift && width == o.width && reorder == o.reorder
             && n_rays == o.n_rays && n_prims == o.n_prims && scene_gen == o.scene_gen && rays_gen == o.rays_gen;
     }
 };
@@ -339,10 +360,15 @@ struct PacketPlan {
     bool valid = false;           // the buffers hold a plan recorded under `key`
     bool dead = false;            // `key`'s batch cannot be planned (known on the host): nothing is launched for it
     PlanKey key;
+    // What the call that sized it asked of the layout (plan_subtile_request): a format-3 plan sized
+    // under the same request is what that request gets (the rule, or the budget, declined the
+    // sub-tile layout), and serves every call that asks for none.
+    int asked = 0;
     uint32_t* idx = nullptr;      // n_words + PLAN_IDX_PAD: the lists' survivor indices
     uint32_t* hdr = nullptr;      // n_hdrs + PLAN_HDR_PAD: the lists' round headers
     int4* spans = nullptr;        // per list {first index word, first header, room in survivors, room in rounds}
-    int4* counts = nullptr;       // per list {dense rounds, survivors, entries, -}
+                                  // (sub-tile layout: room in steps)
+    int4* counts = nullptr;       // per list {dense rounds, survivors, entries, sub-tile layout: steps}
     PlanCtl* ctl = nullptr;
     size_t n_lists = 0, n_words = 0, n_hdrs = 0;
     size_t recorded = 0;          // survivors in use when the plan was sized
@@ -432,7 +458,10 @@ struct TraceState {
     double* custom_table = nullptr;          // N_TABLE doubles, allocated by the first custom table
     double custom_host[N_TABLE] = {};        // its host copy (grace_trace_get_sph_kernel)
     bool plan_on = true;                   // record and use packet plans (grace_trace_set_plan)
-    size_t plan_budget = size_t(512) << 20;  // bytes a plan may take (grace_trace_set_plan_budget)
+    // bytes a plan may take (grace_trace_set_plan_budget): the 1024^2 frame over 10^7 particles takes
+    // 1.475 GB in the sub-tile layout (530 MB in format 3)
+    size_t plan_budget = size_t(2) << 30;
+    int plan_subtiles = -1;                // sub-tile layout: -1 automatic, 0 never, 1 whenever eligible (grace_trace_set_plan_subtiles)
     Scene scene;
     RayOrder rays;
     HitsCache hits;
@@ -528,10 +557,14 @@ grace_status launch_choose_variants(const uint32_t* ext12, int n, const float4* 
 grace_status plan_release(TraceState& ts);
 // Sizes, allocates and records the plan of `key` for the batch `a` describes (its records and ray
 // order already queued on `stream`); synchronises the stream once.  On return ts.plan is valid, or dead.
-grace_status plan_fill(TraceState& ts, const PlanKey& key, const TraceArgs& a, hipStream_t stream);
+// request (plan_subtile_request): 0 records format 3; otherwise the sub-tile layout is recorded if
+// it fits the budget and, request < 0, the automatic rule takes it -- else format 3 as for 0.
+// ts.plan.key.subtiles says which it was.
+grace_status plan_fill(TraceState& ts, const PlanKey& key, int request, const TraceArgs& a, hipStream_t stream);
 // The gated re-record of a call with a valid plan.
 grace_status plan_record(const TraceState& ts, const TraceArgs& a, hipStream_t stream);
 // trace_kernel<mode, SPLIT, fast, false, PLANNED> over `grid` workgroups (mode: f4_sums).
-grace_status launch_planned(int mode, bool fast, int grid, const TraceArgs& a, hipStream_t stream);
+// subtiles: the plan is of the sub-tile layout (unweighted, fast only): the SUBTILE instantiation.
+grace_status launch_planned(int mode, bool fast, bool subtiles, int grid, const TraceArgs& a, hipStream_t stream);
 
 } // namespace grace_hip

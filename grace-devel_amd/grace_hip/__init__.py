@@ -444,6 +444,20 @@ def plan_loops():
     return int(v[0]), int(v[1])
 
 
+def set_plan_subtiles(mode):
+    """The plan's sub-tile layout (a survivor stream per quadrant of 16 rays): -1 automatic
+    (default), 0 never, 1 whenever the call is eligible and the plan fits the budget."""
+    _check(_lib.grace_trace_set_plan_subtiles(C.c_int(int(mode))))
+
+
+def plan_subtiles():
+    """(used, steps, slots): whether the last column-density trace ran from a plan of the sub-tile
+    layout, the steps of its lists and the index words of their streams that name a survivor."""
+    used, steps, slots = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
+    _check(_lib.grace_trace_plan_subtiles(C.byref(used), C.byref(steps), C.byref(slots)))
+    return used.value, int(steps.value), int(slots.value)
+
+
 def set_lattice_split(k):
     _check(_lib.grace_trace_set_lattice_split(C.c_int(k)))
 

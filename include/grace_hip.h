@@ -628,8 +628,9 @@ grace_status grace_trace_set_cache_auto(int enabled);
  * whose plan would exceed the byte budget, has no plan and runs as before.  Results are bit for bit
  * those without a plan.
  * grace_trace_set_plan(0 / 1): off / on (default: see DESIGN.md section 6).
- * grace_trace_set_plan_budget(bytes): the device memory a plan may take (default 512 MiB; the
- * 1024^2 frame over 10^7 particles takes 530.5 MB of those 536.9).
+ * grace_trace_set_plan_budget(bytes): the device memory a plan may take (default 2 GiB; the
+ * 1024^2 frame over 10^7 particles takes 1.475 GB in the sub-tile layout and 530.5 MB in the
+ * ordinary one).
  * grace_trace_plan_bytes: the device memory of the current plan (0: none).
  * grace_trace_last_plan_used (measurement hook, in the manner of grace_trace_last_lattice): 1 if
  * the last column-density trace ran the planned kernel, else 0.  Synchronises.
@@ -644,7 +645,18 @@ grace_status grace_trace_set_cache_auto(int enabled);
  * kernel runs over that plan -- h_loops[0] their number, [1] the survivors of the largest (zeros if
  * it ran from none).  The unweighted kernel with the fast integral runs consecutive test-free
  * rounds of equal bits as one loop of up to 128 survivors; every other planned kernel runs one
- * loop per dense round (at most 64).  Synchronises.
+ * loop per dense round (at most 64).  Synchronises.  With the sub-tile layout both figures are in
+ * slots (four per step).
+ * grace_trace_set_plan_subtiles(-1 / 0 / 1): the plan's sub-tile layout -- one survivor stream per
+ * quadrant of 16 rays instead of one per packet, for the unweighted column-density trace with the
+ * fast integral over packets of 64 rays; it takes about three times the memory of the ordinary
+ * layout.  -1 (default): taken when the batch has enough packets and the streams drop enough of
+ * the survivors' steps; 0: never; 1: whenever the call is eligible and the
+ * plan fits the budget.  A change releases the current plan.  Results are bit for bit the same.
+ * grace_trace_plan_subtiles (diagnostic): *h_used 1 if the last column-density trace ran from a
+ * plan of the sub-tile layout, with *h_steps the steps of its lists and *h_slots the index words
+ * of their streams that name a survivor (of 4 x steps; the rest name the null record); zeros
+ * otherwise.  Synchronises.
  * Not part of the reference API. */
 grace_status grace_trace_set_plan(int on);
 grace_status grace_trace_set_plan_budget(size_t bytes);
@@ -652,6 +664,8 @@ grace_status grace_trace_plan_bytes(size_t* h_bytes);
 grace_status grace_trace_last_plan_used(int* h_used);
 grace_status grace_trace_plan_stats(unsigned long long* h_stats /* [7] */);
 grace_status grace_trace_plan_loops(unsigned long long* h_loops /* [2] */);
+grace_status grace_trace_set_plan_subtiles(int mode);
+grace_status grace_trace_plan_subtiles(int* h_used, unsigned long long* h_steps, unsigned long long* h_slots);
 
 /* Reads (and clears) the traversal status word: GRACE_STACK_OVERFLOW if any packet ran out
  * of its 128-entry stack since the last check (the reference only asserts this in
