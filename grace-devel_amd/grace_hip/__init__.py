@@ -1301,6 +1301,72 @@ def radial_profiles_sph(points, edges, spheres, tree, weights=None, check=False,
     return counts, sums
 
 
+def _gravity_masses(masses, spheres):
+    if masses.dtype != torch.float32 or tuple(masses.shape) != (len(_spheres(spheres)),):
+        raise ValueError("masses must be float32 of shape [n_spheres]")
+    return masses.contiguous()
+
+
+def gravity_moments_sph(spheres, masses, tree, moments=None):
+    """The node moments of the tree gravity (an extension the reference lacks): per inner node the
+    monopole {c, M32}, the tight box of the centres below it and the span of primitives it covers,
+    moments[i] = {c_x, c_y, c_z, M32, lo_x, lo_y, lo_z, bits(span_lo), hi_x, hi_y, hi_z, bits(span_hi)}.
+    Masses and first moments are fp64 sums, per leaf over ascending tree index, per node left + right;
+    c = float(S / M), M32 = float(M), c = lo where M == 0 (include/grace_hip.h states every step).
+    masses: float32 [n_spheres] in the order of `spheres` (tree order: build_tree(want_perm=True)); the
+    spheres' w is ignored.  Computed once per tree and set of masses, then read by any number of
+    gravity_sph calls.  Returns moments float32 [n_nodes, 12] (no rows where the root is a leaf)."""
+    masses = _gravity_masses(masses, spheres)
+    n_nodes = tree.n_nodes
+    if moments is None:
+        moments = torch.empty((n_nodes, 12), dtype=torch.float32, device=spheres.device)
+    if moments.dtype != torch.float32 or tuple(moments.shape) != (n_nodes, 12):
+        raise ValueError("moments must be float32 of shape [%d, 12]" % n_nodes)
+    _check(_lib.grace_gravity_moments_f4(*_interp_scene(spheres, tree), _ptr(masses),
+                                         _ptr(moments) if n_nodes else C.c_void_p(0), _stream()))
+    return moments
+
+
+def gravity_sph(points, spheres, masses, tree, moments, theta=0.5, eps=0.0, out=None, counts=None, check=False):
+    """Potentials and accelerations at points from the BVH (an extension the reference lacks): the
+    Barnes-Hut walk with monopoles of the inner nodes, G = 1.  Per point the recursion from the root: an
+    inner node whose box has size2 < fl(theta^2 * d2min) -- size its longest edge, d2min the squared
+    distance from the point to the box, fp32 -- contributes one term {c, M32}; any other node is opened,
+    left child first; a leaf contributes one term per primitive.  A term is, in fp32, d = x - p,
+    d2 = |d|^2, nothing if d2 == 0 (the self pair), else ir = 1 / sqrt(d2 + eps^2), m ir^3 d into the
+    acceleration and m ir into the potential, both fp64 running sums in the order of the recursion
+    (include/grace_hip.h states every rounding).  theta = 0 is the direct sum over all spheres in
+    ascending tree index and does not depend on the tree; eps is a Plummer softening length for all
+    particles, 0 is Newtonian.
+    points: float32 [n, 3..16] (x y z first); masses: float32 [n_spheres] in tree order; moments:
+    gravity_moments_sph(spheres, masses, tree).  A point with a non-finite coordinate gets zeros.
+    Returns (out float64 [n, 4] = {a_x, a_y, a_z, phi}, counts int32 [n, 2] = {node terms, particle
+    terms} if counts is True or a tensor to fill, else None)."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    masses = _gravity_masses(masses, spheres)
+    n, n_nodes = len(points), tree.n_nodes
+    if n_nodes and (moments is None or moments.dtype != torch.float32 or tuple(moments.shape) != (n_nodes, 12)):
+        raise ValueError("moments must be float32 of shape [%d, 12]" % n_nodes)
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.float64, device=points.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (n, 4):
+        raise ValueError("out must be float64 of shape [%d, 4]" % n)
+    if counts is True:
+        counts = torch.empty((n, 2), dtype=torch.int32, device=points.device)
+    if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (n, 2)):
+        raise ValueError("counts must be True or int32 of shape [%d, 2]" % n)
+    _check(_lib.grace_gravity_points_f4(_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]),
+                                        *_interp_scene(spheres, tree), _ptr(masses),
+                                        _ptr(moments) if n_nodes else C.c_void_p(0),
+                                        C.c_float(float(theta)), C.c_float(float(eps)), _ptr(out), _ptr(counts),
+                                        _stream()))
+    if check:
+        trace_status()
+    return out, counts
+
+
 def _offsets_from_counts(offsets, extra=0):
     """Hit counts -> exclusive offsets in place; returns the total (64-bit).  int offsets cannot
     address more than INT32_MAX per-hit slots: ValueError (std::invalid_argument in the C++

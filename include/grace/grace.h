@@ -16,10 +16,11 @@
 // and this library's extensions: weighted, emission-absorption, deposit and spectra traces,
 // SphKernel, PreparedTrace (with trace_sph.cuh), interpolate_sph / interpolate_grid_sph,
 // nearest_neighbours_sph / smoothing_lengths_sph, range_counts_sph / range_neighbours_sph,
-// fof_labels_sph / fof_groups_sph, pair_counts_sph / radial_profiles_sph.
+// fof_labels_sph / fof_groups_sph, pair_counts_sph / radial_profiles_sph,
+// gravity_moments_sph / gravity_sph.
 //
 // The functions themselves are defined once, in grace/detail/{build_sph,trace_sph,scan,sort,
-// gen_rays,interpolate_sph,neighbours_sph,range_sph,fof_sph,pairs_sph}.h, for this mirror and for the drop-in grace/cuda/*.cuh
+// gen_rays,interpolate_sph,neighbours_sph,range_sph,fof_sph,pairs_sph,gravity_sph}.h, for this mirror and for the drop-in grace/cuda/*.cuh
 // set alike (grace/detail/front_end.h).  What is this header's own: the vector types, the
 // container, Tree, the error policy and the three helpers at its end.
 //
@@ -205,6 +206,7 @@ template <typename T> inline const T* raw(const device_vector<T>& v) { return v.
 #include "grace/detail/range_sph.h"
 #include "grace/detail/fof_sph.h"
 #include "grace/detail/pairs_sph.h"
+#include "grace/detail/gravity_sph.h"
 #include "grace/detail/periodic_trace.h"
 
 namespace grace {

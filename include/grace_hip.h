@@ -1205,6 +1205,80 @@ grace_status grace_pair_counts_f4(const float* d_points, size_t n_points, int el
                                   unsigned long long* d_totals, int* d_counts, float* d_sums,
                                   grace_stream stream);
 
+/* ---- Tree gravity: potentials and accelerations at points (an extension the reference lacks) ----
+ * The Barnes-Hut walk over the BVH with monopoles of the inner nodes, G = 1: whether a
+ * friends-of-friends group is bound, which member is the most bound, the acceleration on a tracer.
+ * Two calls: the node moments once per tree and set of masses, then any number of walks.  The
+ * contract is exact, no tolerance; two results depend on the tree (its max_per_leaf and H) by design:
+ * the node records, and the walk's outputs when theta > 0.
+ *
+ * grace_gravity_moments_f4.  d_masses: float[n_spheres] in tree order (as weights elsewhere); the
+ * spheres' w is ignored.  d_moments: 12 floats per inner node, n_nodes records.
+ *   Per leaf, over its primitives j in ascending index, sequentially in fp64: M = sum double(m_j);
+ *   S_k = sum double(m_j) * double(x_jk) (each product is exact, the running sum is not: hence the
+ *   order); the box lo_k = min x_jk, hi_k = max x_jk over the centres, fp32 -- tight, H plays no
+ *   part; the span [first, first + count).  Leaf values are intermediate (context workspace) and are
+ *   never written to d_moments.
+ *   Per inner node: M = M_left + M_right, S_k = S_left,k + S_right,k (one fp64 add each, the left
+ *   operand first); the box and the span are the unions of the children's.
+ *   Record i = {c_x, c_y, c_z, M32}, {lo_x, lo_y, lo_z, bits(span_lo)}, {hi_x, hi_y, hi_z,
+ *   bits(span_hi)}: c_k = float(S_k / M) (an fp64 divide, rounded once to fp32), M32 = float(M); where
+ *   M == 0, c = lo.  The spans are ints stored by their bit patterns.
+ *   Negative or non-finite masses are the caller's responsibility.  n_nodes == 0 (the root is a
+ *   leaf): GRACE_OK, nothing written, d_moments may be NULL.  GRACE_INVALID_ARGUMENT, nothing written:
+ *   a bad scene (including n_spheres == 0), null d_masses, null d_moments with n_nodes > 0.  The tree
+ *   must be one (every node but the root the child of exactly one node; leaves inside [0, n_spheres));
+ *   on arrays that are no tree some records stay unwritten, nothing is indexed out of bounds and
+ *   nothing waits.  Stream-ordered, no host synchronisation, no allocation (the context workspace):
+ *   capturable.  Bit-identical from run to run.
+ *
+ * grace_gravity_points_f4.  Points: n_points records of elems_per_point (3..16) floats, x y z first,
+ * as for every point query; outputs in the caller's point order.  theta (opening angle) and eps
+ * (Plummer softening length, one for all particles; 0: Newtonian) are host floats.
+ *   d_out[p * 4 + ..] (double) = {a_x, a_y, a_z, phi};  d_counts[p * 2 + ..] (int) = {node terms,
+ *   particle terms}.  Either may be NULL, not both.
+ * Per point p the recursion visit(root), theta2 = fl(theta * theta), eps2 = fl(eps * eps):
+ *   visit(inner node), from its record: e_k = max(max(fl(lo_k - p_k), fl(p_k - hi_k)), 0);
+ *     d2min = fl(fl(fl(e_x e_x) + fl(e_y e_y)) + fl(e_z e_z)); size = max_k fl(hi_k - lo_k);
+ *     size2 = fl(size * size).  The node is accepted iff size2 < fl(theta2 * d2min): then one term for
+ *     {c, M32} and one node term counted; otherwise visit(left child), then visit(right child).  A
+ *     point inside or on the box has d2min == 0 and never accepts it; with theta == 0 nothing is
+ *     accepted.
+ *   visit(leaf): one term per primitive {x_j, m_j} of the leaf, ascending j, a particle term counted
+ *     for each.  A leaf is never taken as a monopole.
+ *   Term for {x, m}, fp32, every operation rounded, none fused: d = fl(x - p) per component;
+ *     d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)).  A term with d2 == 0 contributes nothing, for
+ *     any eps (it is still counted): the self pair and coincident centres.  Otherwise
+ *     s = fl(d2 + eps2); ir = fl(1 / sqrt_rn(s)) (a correctly rounded square root, then a correctly
+ *     rounded divide); u = fl(m * ir); f = fl(m * fl(fl(ir * ir) * ir));
+ *     A_k += double(fl(f * d_k)); P += double(u): fp64 running sums from 0 in the order of the
+ *     recursion, which is ascending span start.
+ *   Output: a = A, phi = -P (so -0 for a point none of whose terms contributed).
+ * So with theta == 0 the result is the direct sum over all spheres in ascending tree index: a
+ * function of the point, the centres, the masses and eps only, not of the tree's shape, H or
+ * max_per_leaf.  For any theta the result does not depend on the point order, elems_per_point, the
+ * packets, the SPH kernel or the trace's knobs, and is bit-identical from run to run.
+ * Off points: a point with a non-finite coordinate gets zeros (+0, all four) and zero counts.
+ * GRACE_INVALID_ARGUMENT, nothing written: theta or eps negative or non-finite, elems_per_point
+ * outside 3..16, no output, null d_masses, null d_moments with n_nodes > 0, a bad scene.  Zero points:
+ * GRACE_OK (elems_per_point, n_points, theta and eps are checked first, the rest after).  The tree's
+ * leaves must cover exactly [0, n_spheres), and d_moments must be grace_gravity_moments_f4's records
+ * for this tree.  A packet that exhausts its 128-entry stack sets the status word of
+ * grace_trace_status (GRACE_STACK_OVERFLOW); nothing is written out of bounds.  Leaves are pushed as
+ * merged ranges as in the range queries, so a spine of coincident centres does not grow the stack.
+ * Stream-ordered, no host synchronisation, no allocation (the context workspace): capturable.
+ * grace_trace_enable_timing / grace_trace_last_kernel_ms time the walk of the last call.
+ * Not provided: periodic boxes (they need Ewald sums), quadrupoles, spline softening or per-particle
+ * softening, leaf monopoles, double4 spheres, G (multiply the outputs). */
+grace_status grace_gravity_moments_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                      size_t n_nodes, const int* d_leaves, const int* d_root,
+                                      const float* d_masses, float* d_moments, grace_stream stream);
+grace_status grace_gravity_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                     const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                     size_t n_nodes, const int* d_leaves, const int* d_root,
+                                     const float* d_masses, const float* d_moments, float theta, float eps,
+                                     double* d_out, int* d_counts, grace_stream stream);
+
 /* ---- Periodic boxes for the point queries: range queries, friends-of-friends, pair counts, nearest
  * neighbours, smoothing lengths and interpolation (an extension the reference lacks)
  * The five families above on a torus: a cosmological snapshot is a periodic box, and a halo that
