@@ -27,6 +27,16 @@
 // Arithmetic.  fp32, every operation rounded (-ffp-contract=off, correctly rounded divide and
 // sqrt): 1.0f / sqrtf(s) as written, no reciprocal-square-root instruction, so that a NumPy
 // restatement reproduces every bit.  LDS: 64 records of 16 bytes per wave, 4 KiB per block.
+//
+// Gravity within groups (grace_gravity_group_moments_f4, grace_gravity_group_points_f4): every point
+// feels the particles that carry its own label, in one walk of the whole-scene tree.  Both kernels
+// are compile-time variants of the ones above.  Moments: a leaf skips its unlabelled primitives
+// (label < 0), and the partial record carries the smallest and largest label below beside the sums;
+// spans still cover every primitive.  Walk: a lane is live at a node iff, in addition, its label
+// lies in the node's label range; a node is a monopole only where that range is one label; the leaf
+// sweep stages each candidate's label beside its record (64 more words of LDS per wave) and a lane
+// takes record j iff j >= skip_hi and the staged label is its own.  Label ranges nest, so a lane
+// a node's range keeps out is kept out of everything below it and needs no skip_hi of its own.
 #include "packet_walk.hpp"
 
 #include <cmath>
@@ -46,6 +56,12 @@ struct alignas(16) Partial {
     int span_hi;
 };
 static_assert(sizeof(Partial) == 64, "one 64-byte record per node or leaf");
+
+// ... and with labels: the smallest and largest label >= 0 below ({INT32_MAX, -1}: none).
+struct alignas(16) GroupPartial : Partial {
+    int lab_lo, lab_hi;
+};
+static_assert(sizeof(GroupPartial) == 80, "the partial record and two ints, padded to 16 bytes");
 
 // parent[child] = node, children indexed as the nodes do: inner nodes first, leaf l at n_nodes + l.
 __global__ __launch_bounds__(GM_BLOCK) void gravity_parents_kernel(const float4* __restrict__ nodes, int n_nodes,
@@ -74,25 +90,46 @@ __device__ __forceinline__ Partial combine(const Partial& l, const Partial& r)
     return p;
 }
 
+__device__ __forceinline__ GroupPartial combine(const GroupPartial& l, const GroupPartial& r)
+{
+    GroupPartial p;
+    static_cast<Partial&>(p) = combine(static_cast<const Partial&>(l), static_cast<const Partial&>(r));
+    p.lab_lo = min(l.lab_lo, r.lab_lo);
+    p.lab_hi = max(l.lab_hi, r.lab_hi);
+    return p;
+}
+
+// P: Partial (labels and label_ranges unused, null) or GroupPartial.
+template <typename P>
 __global__ __launch_bounds__(GM_BLOCK) void gravity_moments_kernel(const float4* __restrict__ spheres, int n_spheres,
                                                                    const float* __restrict__ masses,
+                                                                   const int* __restrict__ labels,
                                                                    const float4* __restrict__ nodes, int n_nodes,
                                                                    const int4* __restrict__ leaves,
                                                                    const int* __restrict__ parent, int* counters,
-                                                                   Partial* partials, float4* __restrict__ moments)
+                                                                   P* partials, float4* __restrict__ moments,
+                                                                   int2* __restrict__ label_ranges)
 {
+    constexpr bool GROUPS = std::is_same<P, GroupPartial>::value;
     const int leaf = blockIdx.x * GM_BLOCK + threadIdx.x;
     if (leaf > n_nodes) return;                                  // n_nodes + 1 leaves
     const int4 lf = leaves[leaf];
     const int first = min(max(lf.x, 0), n_spheres);
     const int end = first + min(max(lf.y, 0), n_spheres - first);   // inside [0, n_spheres] whatever the leaf holds
-    Partial mine;
+    P mine;
     mine.M = mine.Sx = mine.Sy = mine.Sz = 0.0;
     mine.lo_x = mine.lo_y = mine.lo_z = __int_as_float(0x7f800000);
     mine.hi_x = mine.hi_y = mine.hi_z = __int_as_float(0xff800000);
     mine.span_lo = first;
     mine.span_hi = end;
+    if constexpr (GROUPS) { mine.lab_lo = INT32_MAX; mine.lab_hi = -1; }
     for (int j = first; j < end; ++j) {
+        if constexpr (GROUPS) {
+            const int lab = labels[j];
+            if (lab < 0) continue;                               // in no group: absent, but it keeps its index
+            mine.lab_lo = min(mine.lab_lo, lab);
+            mine.lab_hi = max(mine.lab_hi, lab);
+        }
         const float4 s = spheres[j];
         const double m = double(masses[j]);
         mine.M += m;
@@ -115,7 +152,7 @@ __global__ __launch_bounds__(GM_BLOCK) void gravity_moments_kernel(const float4*
         const int l = __float_as_int(n0.x), r = __float_as_int(n0.y);
         const int other = l == at ? r : l;
         if (other < 0 || other > 2 * n_nodes || parent[other] != up) return;   // not a tree
-        const Partial theirs = partials[other];
+        const P theirs = partials[other];
         mine = l == at ? combine(mine, theirs) : combine(theirs, mine);
         float cx = mine.lo_x, cy = mine.lo_y, cz = mine.lo_z;
         if (mine.M != 0.0) {
@@ -127,6 +164,7 @@ __global__ __launch_bounds__(GM_BLOCK) void gravity_moments_kernel(const float4*
         rec[0] = make_float4(cx, cy, cz, float(mine.M));
         rec[1] = make_float4(mine.lo_x, mine.lo_y, mine.lo_z, __int_as_float(mine.span_lo));
         rec[2] = make_float4(mine.hi_x, mine.hi_y, mine.hi_z, __int_as_float(mine.span_hi));
+        if constexpr (GROUPS) label_ranges[up] = make_int2(mine.lab_lo, mine.lab_hi);
         at = up;
     }
 }
@@ -138,6 +176,13 @@ struct GravityArgs : PacketPoints, PacketScene {
     float theta2, eps2;
     double* out;                 // {a_x, a_y, a_z, phi} per point, or null
     int* counts;                 // {node terms, particle terms} per point, or null
+};
+
+// ... within groups: a label per primitive and per point, a label range per inner node.
+struct GroupGravityArgs : GravityArgs {
+    const int* labels;           // per primitive, tree order; < 0: in no group
+    const int2* label_ranges;    // {lab_lo, lab_hi} per inner node
+    const int* point_labels;     // per point, the caller's order
 };
 
 // The lane's four running sums and the pair term added to them.
@@ -161,9 +206,13 @@ struct GravitySums {
     }
 };
 
-__global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const GravityArgs a)
+// Args: GravityArgs, or GroupGravityArgs for the walk within groups.
+template <typename Args>
+__global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const Args a)
 {
+    constexpr bool GROUPS = std::is_same<Args, GroupGravityArgs>::value;
     __shared__ float4 s_rec_all[PW_WAVES][64];
+    __shared__ int s_lab_all[GROUPS ? PW_WAVES : 1][64];         // (the open walk never names it: no LDS there)
     const PacketWave w = packet_wave();
     const int lane = w.lane, packet = w.packet;
     if (packet >= int(*a.n_starts)) return;
@@ -171,7 +220,21 @@ __global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const GravityArgs a)
 
     const PacketPoint pt = load_point(a, packet, lane);
     const float px = pt.px, py = pt.py, pz = pt.pz;
-    const bool on = pt.in_range && isfinite(px) && isfinite(py) && isfinite(pz);
+    bool on = pt.in_range && isfinite(px) && isfinite(py) && isfinite(pz);
+    // the lane's label, and the range of the labels of the wave's on-lanes ({INT32_MAX, -1}: none is on)
+    int my_label = -1, wave_lab_lo = INT32_MAX, wave_lab_hi = -1;
+    int* s_lab = nullptr;
+    if constexpr (GROUPS) {
+        s_lab = s_lab_all[w.wv];
+        if (pt.in_range) my_label = a.point_labels[pt.src];
+        on = on && my_label >= 0;
+        wave_lab_lo = on ? my_label : INT32_MAX;
+        wave_lab_hi = on ? my_label : -1;
+        for (int off = 32; off > 0; off >>= 1) {
+            wave_lab_lo = min(wave_lab_lo, __shfl_xor(wave_lab_lo, off));
+            wave_lab_hi = max(wave_lab_hi, __shfl_xor(wave_lab_hi, off));
+        }
+    }
 
     GravitySums sum;
     int skip_hi = 0, n_node_terms = 0, n_particle_terms = 0;
@@ -215,7 +278,13 @@ __global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const GravityArgs a)
             const float4* rec = a.moments + 3 * size_t(idx);
             const float4 cm = rec[0], lo = rec[1], hi = rec[2];
             const int span_lo = __float_as_int(lo.w), span_hi = __float_as_int(hi.w);
-            const bool live = on && span_lo >= skip_hi;
+            bool live = on && span_lo >= skip_hi;
+            bool pure = true;
+            if constexpr (GROUPS) {
+                const int2 lr = a.label_ranges[idx];
+                live = live && lr.x <= my_label && my_label <= lr.y;
+                pure = lr.x == lr.y;                             // two or more labels: never a monopole
+            }
             if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
             const float ex = fmaxf(fmaxf(lo.x - px, px - hi.x), 0.0f);
             const float ey = fmaxf(fmaxf(lo.y - py, py - hi.y), 0.0f);
@@ -223,7 +292,7 @@ __global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const GravityArgs a)
             const float d2min = (ex * ex + ey * ey) + ez * ez;
             const float size = fmaxf(fmaxf(hi.x - lo.x, hi.y - lo.y), hi.z - lo.z);
             const float size2 = size * size;
-            const bool accept = live && size2 < a.theta2 * d2min;
+            const bool accept = live && pure && size2 < a.theta2 * d2min;
             if (accept) {
                 sum.add(px, py, pz, cm.x, cm.y, cm.z, cm.w, a.eps2);
                 ++n_node_terms;
@@ -240,17 +309,33 @@ __global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const GravityArgs a)
             const int j_lo = max(cl << 6, r_lo), j_hi = min((cl << 6) + 64, r_hi);
             if (__builtin_amdgcn_ballot_w64(on && j_hi > skip_hi) == 0ull) continue;
             const int pj = (cl << 6) + lane;
+            if constexpr (GROUPS) {
+                // the candidate's label (-1 outside the range); no on-lane carries a label outside the
+                // wave's range, so a cluster without a candidate inside it holds no lane's term
+                const int cand = pj >= j_lo && pj < j_hi ? a.labels[pj] : -1;
+                if (__builtin_amdgcn_ballot_w64(cand >= wave_lab_lo && cand <= wave_lab_hi) == 0ull) continue;
+                s_lab[lane] = cand;
+            }
             if (pj >= j_lo && pj < j_hi) {
                 const float4 s = a.spheres[pj];
                 s_rec[lane] = make_float4(s.x, s.y, s.z, a.masses[pj]);
             }
             wave_sync();
             if (on) {
-                for (int j = max(j_lo, skip_hi); j < j_hi; ++j) {
-                    const float4 r = s_rec[j & 63];
-                    sum.add(px, py, pz, r.x, r.y, r.z, r.w, a.eps2);
+                if constexpr (GROUPS) {
+                    for (int j = max(j_lo, skip_hi); j < j_hi; ++j) {
+                        if (s_lab[j & 63] != my_label) continue;
+                        const float4 r = s_rec[j & 63];
+                        sum.add(px, py, pz, r.x, r.y, r.z, r.w, a.eps2);
+                        ++n_particle_terms;
+                    }
+                } else {
+                    for (int j = max(j_lo, skip_hi); j < j_hi; ++j) {
+                        const float4 r = s_rec[j & 63];
+                        sum.add(px, py, pz, r.x, r.y, r.z, r.w, a.eps2);
+                    }
+                    n_particle_terms += max(j_hi - max(j_lo, skip_hi), 0);
                 }
-                n_particle_terms += max(j_hi - max(j_lo, skip_hi), 0);
             }
             wave_sync();
         }
@@ -268,6 +353,64 @@ __global__ __launch_bounds__(PW_BLOCK) void gravity_kernel(const GravityArgs a)
     }
 }
 
+// The parents, then the climb, in the context workspace (the scene and the pointers are checked by the caller).
+template <typename P>
+grace_status moments_run(const PacketScene& s, size_t n_spheres, size_t n_nodes, const float* d_masses,
+                         const int* d_labels, float* d_moments, int* d_label_ranges, hipStream_t stream_)
+{
+    const size_t n_all = 2 * n_nodes + 1;
+    FrameGuard frame;
+    GRACE_TRY(frame.begin(Workspace::aligned(n_all * sizeof(int)) + Workspace::aligned(n_nodes * sizeof(int))
+                          + Workspace::aligned(n_all * sizeof(P)), stream_));
+    int* parent = Workspace::take<int>(n_all);
+    int* counters = Workspace::take<int>(n_nodes);
+    P* partials = Workspace::take<P>(n_all);
+    GRACE_TRY_HIP(hipMemsetAsync(parent, 0xff, n_all * sizeof(int), stream_));
+    GRACE_TRY_HIP(hipMemsetAsync(counters, 0, n_nodes * sizeof(int), stream_));
+    gravity_parents_kernel<<<ceil_div(n_nodes, GM_BLOCK), GM_BLOCK, 0, stream_>>>(s.nodes, s.n_nodes, parent);
+    GRACE_CHECK_LAUNCH();
+    gravity_moments_kernel<P><<<ceil_div(n_nodes + 1, GM_BLOCK), GM_BLOCK, 0, stream_>>>(
+        s.spheres, int(n_spheres), d_masses, d_labels, s.nodes, s.n_nodes, s.leaves, parent, counters, partials,
+        reinterpret_cast<float4*>(d_moments), reinterpret_cast<int2*>(d_label_ranges));
+    GRACE_CHECK_LAUNCH();
+    return GRACE_OK;
+}
+
+// What both walks check and set, before anything is enqueued.
+#define GRAVITY_WALK_ARGS(a)                                                                                      \
+    do {                                                                                                          \
+        GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "gravity: elements per point must be 3..16"); \
+        GRACE_REQUIRE(n_points < (size_t(1) << 31), "gravity: too many points");                                  \
+        GRACE_REQUIRE(std::isfinite(theta) && theta >= 0.0f, "gravity: theta must be finite and not negative");    \
+        GRACE_REQUIRE(std::isfinite(eps) && eps >= 0.0f, "gravity: eps must be finite and not negative");         \
+        if (n_points == 0) return GRACE_OK;                      /* (a caller's empty arrays may be null) */      \
+        GRACE_REQUIRE(d_out || d_counts, "gravity: no output");                                                   \
+        GRACE_REQUIRE(d_points, "gravity: null points");                                                          \
+        PACKET_SCENE(a, "gravity", true, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);               \
+        GRACE_REQUIRE(d_masses, "gravity: null masses");                                                          \
+        GRACE_REQUIRE(d_moments || n_nodes == 0, "gravity: null moments");                                        \
+        (a).n_spheres = int(n_spheres);                                                                           \
+        (a).masses = d_masses;                                                                                    \
+        (a).moments = reinterpret_cast<const float4*>(d_moments);                                                 \
+        (a).theta2 = theta * theta;                                                                               \
+        (a).eps2 = eps * eps;                                                                                     \
+        (a).out = d_out;                                                                                          \
+        (a).counts = d_counts;                                                                                    \
+    } while (0)
+
+template <typename Args>
+grace_status walk_run(const Args& a, const float* d_points, size_t n_points, int elems_per_point, hipStream_t stream_)
+{
+    TraceState* ts = nullptr;
+    GRACE_TRY(trace_state(&ts));
+    return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
+                      [&](const Args& w, size_t waves) -> grace_status {
+        gravity_kernel<Args><<<ceil_div(waves, PW_WAVES), PW_BLOCK, 0, stream_>>>(w);
+        GRACE_CHECK_LAUNCH();
+        return GRACE_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -281,23 +424,23 @@ grace_status grace_gravity_moments_f4(const float* d_spheres, size_t n_spheres, 
     GRACE_REQUIRE(d_masses, "gravity_moments: null masses");
     if (n_nodes == 0) return GRACE_OK;                           // the root is a leaf: no records
     GRACE_REQUIRE(d_moments, "gravity_moments: null moments");
-    const hipStream_t stream_ = as_stream(stream);
-    const size_t n_all = 2 * n_nodes + 1;
-    FrameGuard frame;
-    GRACE_TRY(frame.begin(Workspace::aligned(n_all * sizeof(int)) + Workspace::aligned(n_nodes * sizeof(int))
-                          + Workspace::aligned(n_all * sizeof(Partial)), stream_));
-    int* parent = Workspace::take<int>(n_all);
-    int* counters = Workspace::take<int>(n_nodes);
-    Partial* partials = Workspace::take<Partial>(n_all);
-    GRACE_TRY_HIP(hipMemsetAsync(parent, 0xff, n_all * sizeof(int), stream_));
-    GRACE_TRY_HIP(hipMemsetAsync(counters, 0, n_nodes * sizeof(int), stream_));
-    gravity_parents_kernel<<<ceil_div(n_nodes, GM_BLOCK), GM_BLOCK, 0, stream_>>>(s.nodes, s.n_nodes, parent);
-    GRACE_CHECK_LAUNCH();
-    gravity_moments_kernel<<<ceil_div(n_nodes + 1, GM_BLOCK), GM_BLOCK, 0, stream_>>>(
-        s.spheres, int(n_spheres), d_masses, s.nodes, s.n_nodes, s.leaves, parent, counters, partials,
-        reinterpret_cast<float4*>(d_moments));
-    GRACE_CHECK_LAUNCH();
-    return GRACE_OK;
+    return moments_run<Partial>(s, n_spheres, n_nodes, d_masses, nullptr, d_moments, nullptr, as_stream(stream));
+}
+
+grace_status grace_gravity_group_moments_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                            size_t n_nodes, const int* d_leaves, const int* d_root,
+                                            const float* d_masses, const int* d_labels, float* d_moments,
+                                            int* d_label_ranges, grace_stream stream)
+{
+    PacketScene s = {};
+    PACKET_SCENE(s, "gravity", true, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
+    GRACE_REQUIRE(d_masses, "gravity_group_moments: null masses");
+    GRACE_REQUIRE(d_labels, "gravity_group_moments: null labels");
+    if (n_nodes == 0) return GRACE_OK;                           // the root is a leaf: no records
+    GRACE_REQUIRE(d_moments, "gravity_group_moments: null moments");
+    GRACE_REQUIRE(d_label_ranges, "gravity_group_moments: null label ranges");
+    return moments_run<GroupPartial>(s, n_spheres, n_nodes, d_masses, d_labels, d_moments, d_label_ranges,
+                                     as_stream(stream));
 }
 
 grace_status grace_gravity_points_f4(const float* d_points, size_t n_points, int elems_per_point,
@@ -306,33 +449,27 @@ grace_status grace_gravity_points_f4(const float* d_points, size_t n_points, int
                                      const float* d_moments, float theta, float eps, double* d_out, int* d_counts,
                                      grace_stream stream)
 {
-    GRACE_REQUIRE(elems_per_point >= 3 && elems_per_point <= 16, "gravity: elements per point must be 3..16");
-    GRACE_REQUIRE(n_points < (size_t(1) << 31), "gravity: too many points");
-    GRACE_REQUIRE(std::isfinite(theta) && theta >= 0.0f, "gravity: theta must be finite and not negative");
-    GRACE_REQUIRE(std::isfinite(eps) && eps >= 0.0f, "gravity: eps must be finite and not negative");
-    if (n_points == 0) return GRACE_OK;                          // (a caller's empty arrays may be null)
-    GRACE_REQUIRE(d_out || d_counts, "gravity: no output");
-    GRACE_REQUIRE(d_points, "gravity: null points");
     GravityArgs a = {};
-    PACKET_SCENE(a, "gravity", true, d_spheres, n_spheres, d_nodes, n_nodes, d_leaves, d_root);
-    GRACE_REQUIRE(d_masses, "gravity: null masses");
-    GRACE_REQUIRE(d_moments || n_nodes == 0, "gravity: null moments");
-    TraceState* ts = nullptr;
-    GRACE_TRY(trace_state(&ts));
-    a.n_spheres = int(n_spheres);
-    a.masses = d_masses;
-    a.moments = reinterpret_cast<const float4*>(d_moments);
-    a.theta2 = theta * theta;
-    a.eps2 = eps * eps;
-    a.out = d_out;
-    a.counts = d_counts;
-    const hipStream_t stream_ = as_stream(stream);
-    return packet_run(a, *ts, d_points, n_points, elems_per_point, stream_,
-                      [&](const GravityArgs& w, size_t waves) -> grace_status {
-        gravity_kernel<<<ceil_div(waves, PW_WAVES), PW_BLOCK, 0, stream_>>>(w);
-        GRACE_CHECK_LAUNCH();
-        return GRACE_OK;
-    });
+    GRAVITY_WALK_ARGS(a);
+    return walk_run(a, d_points, n_points, elems_per_point, as_stream(stream));
+}
+
+grace_status grace_gravity_group_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                           const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                           size_t n_nodes, const int* d_leaves, const int* d_root,
+                                           const float* d_masses, const int* d_labels, const float* d_moments,
+                                           const int* d_label_ranges, const int* d_point_labels, float theta,
+                                           float eps, double* d_out, int* d_counts, grace_stream stream)
+{
+    GroupGravityArgs a = {};
+    GRAVITY_WALK_ARGS(a);
+    GRACE_REQUIRE(d_labels, "gravity_groups: null labels");
+    GRACE_REQUIRE(d_point_labels, "gravity_groups: null point labels");
+    GRACE_REQUIRE(d_label_ranges || n_nodes == 0, "gravity_groups: null label ranges");
+    a.labels = d_labels;
+    a.label_ranges = reinterpret_cast<const int2*>(d_label_ranges);
+    a.point_labels = d_point_labels;
+    return walk_run(a, d_points, n_points, elems_per_point, as_stream(stream));
 }
 
 } // extern "C"

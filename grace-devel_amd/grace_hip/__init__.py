@@ -1367,6 +1367,91 @@ def gravity_sph(points, spheres, masses, tree, moments, theta=0.5, eps=0.0, out=
     return out, counts
 
 
+def _gravity_labels(labels, n, what, of):
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise ValueError("%s must be int32 of shape [%s]" % (what, of))
+    return labels.contiguous()
+
+
+def gravity_group_moments_sph(spheres, masses, labels, tree, moments=None, label_ranges=None):
+    """The node moments of the gravity within groups (an extension the reference lacks): gravity_moments_sph's
+    records taken over the labelled spheres only, and per inner node the range of the labels below it.
+    labels: int32 [n_spheres] in the order of `spheres` (tree order), such as fof_labels_sph's labels or
+    fof_groups_sph's group_of; a label >= 0 names a group, a label < 0 means "in no group": such a particle
+    attracts nobody, as if it were absent, but keeps its index.  M, S and the tight box lo / hi are over
+    the labelled spheres below the node (fp64 sums per leaf in ascending tree index, per node left +
+    right; +inf / -inf where there are none); the spans cover every sphere; c = float(S / M), lo where
+    M == 0.  label_ranges[i] = {smallest, largest label >= 0 below node i}, {INT32_MAX, -1} where there
+    is none.  Where no label is negative the moments equal gravity_moments_sph's bit for bit.
+    Returns (moments float32 [n_nodes, 12], label_ranges int32 [n_nodes, 2])."""
+    masses = _gravity_masses(masses, spheres)
+    labels = _gravity_labels(labels, len(masses), "labels", "n_spheres")
+    n_nodes = tree.n_nodes
+    if moments is None:
+        moments = torch.empty((n_nodes, 12), dtype=torch.float32, device=spheres.device)
+    if moments.dtype != torch.float32 or tuple(moments.shape) != (n_nodes, 12):
+        raise ValueError("moments must be float32 of shape [%d, 12]" % n_nodes)
+    if label_ranges is None:
+        label_ranges = torch.empty((n_nodes, 2), dtype=torch.int32, device=spheres.device)
+    if label_ranges.dtype != torch.int32 or tuple(label_ranges.shape) != (n_nodes, 2):
+        raise ValueError("label_ranges must be int32 of shape [%d, 2]" % n_nodes)
+    _check(_lib.grace_gravity_group_moments_f4(*_interp_scene(spheres, tree), _ptr(masses), _ptr(labels),
+                                               _ptr(moments) if n_nodes else C.c_void_p(0),
+                                               _ptr(label_ranges) if n_nodes else C.c_void_p(0), _stream()))
+    return moments, label_ranges
+
+
+def gravity_groups_sph(points, point_labels, spheres, masses, labels, tree, moments, label_ranges, theta=0.5,
+                       eps=0.0, out=None, counts=None, check=False):
+    """Gravity within groups (an extension the reference lacks): at every point the potential and the
+    acceleration due to the spheres that carry the point's own label, in one walk of the whole-scene
+    tree -- the binding energy of every member of every friends-of-friends group in one call.  The
+    recursion of gravity_sph with labels: a point of label L >= 0 passes by an inner node whose label
+    range does not hold L (no term, no count); a node whose range is the one label L and whose box has
+    size2 < fl(theta^2 * d2min) contributes one term {c, M32}; any other node is opened, left child
+    first -- a node that holds two or more labels is never a monopole; a leaf contributes one term per
+    sphere j with labels[j] == L, ascending j.  Terms, rounding, the fp64 sums and their order are
+    gravity_sph's (include/grace_hip.h states every step).  theta = 0 is the direct sum over the
+    label's members in ascending tree index and does not depend on the tree; with one label >= 0 on
+    every sphere and point the result equals gravity_sph's bit for bit.
+    points: float32 [n, 3..16]; point_labels: int32 [n]; masses: float32 [n_spheres] and labels: int32
+    [n_spheres] in tree order; moments, label_ranges: gravity_group_moments_sph(spheres, masses, labels,
+    tree).  A point with a negative label or a non-finite coordinate gets zeros; a point whose label no
+    sphere carries gets no term.  An unbinding pass: labels[unbound] = -1, the moments again, this call
+    again.
+    Returns (out float64 [n, 4] = {a_x, a_y, a_z, phi}, counts int32 [n, 2] = {node terms, particle
+    terms} if counts is True or a tensor to fill, else None)."""
+    if points.dtype != torch.float32 or points.dim() != 2 or not 3 <= points.shape[1] <= 16:
+        raise ValueError("points must be float32 of shape [n, 3..16]")
+    points = points.contiguous()
+    masses = _gravity_masses(masses, spheres)
+    n, n_nodes = len(points), tree.n_nodes
+    labels = _gravity_labels(labels, len(masses), "labels", "n_spheres")
+    point_labels = _gravity_labels(point_labels, n, "point_labels", "n_points")
+    if n_nodes and (moments is None or moments.dtype != torch.float32 or tuple(moments.shape) != (n_nodes, 12)):
+        raise ValueError("moments must be float32 of shape [%d, 12]" % n_nodes)
+    if n_nodes and (label_ranges is None or label_ranges.dtype != torch.int32
+                    or tuple(label_ranges.shape) != (n_nodes, 2)):
+        raise ValueError("label_ranges must be int32 of shape [%d, 2]" % n_nodes)
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.float64, device=points.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (n, 4):
+        raise ValueError("out must be float64 of shape [%d, 4]" % n)
+    if counts is True:
+        counts = torch.empty((n, 2), dtype=torch.int32, device=points.device)
+    if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (n, 2)):
+        raise ValueError("counts must be True or int32 of shape [%d, 2]" % n)
+    _check(_lib.grace_gravity_group_points_f4(_ptr(points), C.c_size_t(n), C.c_int(points.shape[1]),
+                                              *_interp_scene(spheres, tree), _ptr(masses), _ptr(labels),
+                                              _ptr(moments) if n_nodes else C.c_void_p(0),
+                                              _ptr(label_ranges) if n_nodes else C.c_void_p(0), _ptr(point_labels),
+                                              C.c_float(float(theta)), C.c_float(float(eps)), _ptr(out),
+                                              _ptr(counts), _stream()))
+    if check:
+        trace_status()
+    return out, counts
+
+
 def _offsets_from_counts(offsets, extra=0):
     """Hit counts -> exclusive offsets in place; returns the total (64-bit).  int offsets cannot
     address more than INT32_MAX per-hit slots: ValueError (std::invalid_argument in the C++

@@ -8,4 +8,4 @@
 
 #include "grace/cuda/trace_sph.cuh"
 
-#include "grace/detail/gravity_sph.h"   // gravity_moments_sph, gravity_sph
+#include "grace/detail/gravity_sph.h"   // gravity_moments_sph, gravity_sph, gravity_group_moments_sph, gravity_groups_sph

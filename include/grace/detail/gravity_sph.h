@@ -84,4 +84,93 @@ GRACE_HOST void gravity_sph(const detail::dvec<PointType>& d_points, const detai
                          detail::raw(d_counts));
 }
 
+// ---- Gravity within groups (grace_gravity_group_moments_f4, grace_gravity_group_points_f4): every
+// point feels the particles that carry its own label.  d_labels: one int per sphere in tree order
+// (fof_labels_sph's labels, fof_groups_sph's group_of), < 0: in no group, attracts nobody;
+// d_point_labels: one int per point.  gravity_group_moments_sph once per tree, masses and labels,
+// then any number of gravity_groups_sph calls; an unbinding pass sets labels to -1 and calls both
+// again.  Not provided: a theta or eps per group, particles in more than one group, the unbinding
+// loop itself, periodic boxes, and everything gravity_sph leaves out.
+
+namespace detail {
+
+// The one call of grace_gravity_group_points_f4; out or counts may be NULL.
+template <typename PointType, typename Real4>
+inline void gravity_groups_call(const dvec<PointType>& d_points, const dvec<int>& d_point_labels,
+                                const dvec<Real4>& d_spheres, const dvec<float>& d_masses, const dvec<int>& d_labels,
+                                const Tree& d_tree, const dvec<float>& d_moments, const dvec<int>& d_label_ranges,
+                                const float theta, const float eps, double* out, int* counts)
+{
+    static_assert(std::is_same<Real4, float4>::value, "gravity: float4 spheres only (float distances, double sums)");
+    static_assert(sizeof(PointType) % sizeof(float) == 0 && sizeof(PointType) >= 3 * sizeof(float)
+                      && sizeof(PointType) <= 16 * sizeof(float),
+                  "gravity: points are 3..16 floats, x y z first");
+    const SceneArgs<Real4> a = scene_args(d_spheres, d_tree);
+    if (d_masses.size() != d_spheres.size())
+        throw std::invalid_argument("gravity_groups_sph: d_masses must hold one mass per sphere");
+    if (d_labels.size() != d_spheres.size())
+        throw std::invalid_argument("gravity_groups_sph: d_labels must hold one label per sphere");
+    if (d_point_labels.size() != d_points.size())
+        throw std::invalid_argument("gravity_groups_sph: d_point_labels must hold one label per point");
+    if (d_moments.size() != a.n_nodes * 12)
+        throw std::invalid_argument("gravity_groups_sph: d_moments must hold 12 floats per node (gravity_group_moments_sph)");
+    if (d_label_ranges.size() != a.n_nodes * 2)
+        throw std::invalid_argument("gravity_groups_sph: d_label_ranges must hold 2 ints per node (gravity_group_moments_sph)");
+    GRACE_STATUS_CHECK(grace_gravity_group_points_f4(
+        reinterpret_cast<const float*>(raw(d_points)), d_points.size(), int(sizeof(PointType) / sizeof(float)),
+        GRACE_SCENE(a), raw(d_masses), raw(d_labels), a.n_nodes ? raw(d_moments) : NULL,
+        a.n_nodes ? raw(d_label_ranges) : NULL, raw(d_point_labels), theta, eps, out, counts, NULL));
+    check_trace_status();
+}
+
+} // namespace detail
+
+// d_moments as gravity_moments_sph's, over the labelled spheres only; d_label_ranges[i * 2 + ..] =
+// {smallest, largest label >= 0 below node i} ({INT32_MAX, -1}: none).  Both resized.
+template <typename Real4>
+GRACE_HOST void gravity_group_moments_sph(const detail::dvec<Real4>& d_spheres, const detail::dvec<float>& d_masses,
+                                          const detail::dvec<int>& d_labels, const Tree& d_tree,
+                                          detail::dvec<float>& d_moments, detail::dvec<int>& d_label_ranges)
+{
+    static_assert(std::is_same<Real4, float4>::value, "gravity: float4 spheres only (float distances, double sums)");
+    const detail::SceneArgs<Real4> a = detail::scene_args(d_spheres, d_tree);
+    if (d_masses.size() != d_spheres.size())
+        throw std::invalid_argument("gravity_group_moments_sph: d_masses must hold one mass per sphere");
+    if (d_labels.size() != d_spheres.size())
+        throw std::invalid_argument("gravity_group_moments_sph: d_labels must hold one label per sphere");
+    d_moments.resize(a.n_nodes * 12);
+    d_label_ranges.resize(a.n_nodes * 2);
+    GRACE_STATUS_CHECK(grace_gravity_group_moments_f4(GRACE_SCENE(a), detail::raw(d_masses), detail::raw(d_labels),
+                                                      a.n_nodes ? detail::raw(d_moments) : NULL,
+                                                      a.n_nodes ? detail::raw(d_label_ranges) : NULL, NULL));
+}
+
+// d_out[p * 4 + ..] = {a_x, a_y, a_z, phi} at d_points[p] due to the spheres labelled d_point_labels[p]; resized.
+template <typename PointType, typename Real4>
+GRACE_HOST void gravity_groups_sph(const detail::dvec<PointType>& d_points, const detail::dvec<int>& d_point_labels,
+                                   const detail::dvec<Real4>& d_spheres, const detail::dvec<float>& d_masses,
+                                   const detail::dvec<int>& d_labels, const Tree& d_tree,
+                                   const detail::dvec<float>& d_moments, const detail::dvec<int>& d_label_ranges,
+                                   const float theta, const float eps, detail::dvec<double>& d_out)
+{
+    d_out.resize(d_points.size() * 4);
+    detail::gravity_groups_call(d_points, d_point_labels, d_spheres, d_masses, d_labels, d_tree, d_moments,
+                                d_label_ranges, theta, eps, detail::raw(d_out), (int*)NULL);
+}
+
+// ... and d_counts[p * 2 + ..] = {node terms, particle terms} of the point's walk; resized.
+template <typename PointType, typename Real4>
+GRACE_HOST void gravity_groups_sph(const detail::dvec<PointType>& d_points, const detail::dvec<int>& d_point_labels,
+                                   const detail::dvec<Real4>& d_spheres, const detail::dvec<float>& d_masses,
+                                   const detail::dvec<int>& d_labels, const Tree& d_tree,
+                                   const detail::dvec<float>& d_moments, const detail::dvec<int>& d_label_ranges,
+                                   const float theta, const float eps, detail::dvec<double>& d_out,
+                                   detail::dvec<int>& d_counts)
+{
+    d_out.resize(d_points.size() * 4);
+    d_counts.resize(d_points.size() * 2);
+    detail::gravity_groups_call(d_points, d_point_labels, d_spheres, d_masses, d_labels, d_tree, d_moments,
+                                d_label_ranges, theta, eps, detail::raw(d_out), detail::raw(d_counts));
+}
+
 } // namespace grace

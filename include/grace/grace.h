@@ -17,7 +17,7 @@
 // SphKernel, PreparedTrace (with trace_sph.cuh), interpolate_sph / interpolate_grid_sph,
 // nearest_neighbours_sph / smoothing_lengths_sph, range_counts_sph / range_neighbours_sph,
 // fof_labels_sph / fof_groups_sph, pair_counts_sph / radial_profiles_sph,
-// gravity_moments_sph / gravity_sph.
+// gravity_moments_sph / gravity_sph, gravity_group_moments_sph / gravity_groups_sph.
 //
 // The functions themselves are defined once, in grace/detail/{build_sph,trace_sph,scan,sort,
 // gen_rays,interpolate_sph,neighbours_sph,range_sph,fof_sph,pairs_sph,gravity_sph}.h, for this mirror and for the drop-in grace/cuda/*.cuh

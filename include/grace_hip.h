@@ -1279,6 +1279,71 @@ grace_status grace_gravity_points_f4(const float* d_points, size_t n_points, int
                                      const float* d_masses, const float* d_moments, float theta, float eps,
                                      double* d_out, int* d_counts, grace_stream stream);
 
+/* ---- Gravity within groups: every point feels the particles of its own label (an extension the
+ * reference lacks)
+ * The potential of every member of every friends-of-friends group due to its own group alone, in
+ * one walk of the whole-scene tree: which haloes of a catalogue are bound, without a tree, a gather
+ * and a launch per group.  The two calls are grace_gravity_moments_f4 and grace_gravity_points_f4 in
+ * everything this block does not restate: arguments, layouts, rounding, the order of the sums,
+ * status word, stream ordering, timing, capturability.  The contract is exact, no tolerance.
+ *
+ * Labels.  d_labels: int[n_spheres] in tree order.  A label >= 0 names a group; a label < 0 means
+ * "in no group": such a particle attracts nobody -- it is as if it were absent, except that it keeps
+ * its index.  d_point_labels: int[n_points] in the caller's point order.  Label values matter only
+ * through equality and order.
+ *
+ * grace_gravity_group_moments_f4.  d_moments: 12 floats per inner node in the layout of
+ * grace_gravity_moments_f4; d_label_ranges: 2 ints per inner node.
+ *   M, S, lo and hi are taken over the labelled primitives (label >= 0) below the node only: the
+ *   fp64 sums per leaf in ascending tree index, skipping unlabelled primitives, and per node as
+ *   left + right; lo / hi the tight box of the labelled centres, +inf / -inf where there are none.
+ *   span_lo / span_hi are unchanged: they cover every primitive, because the walk skips by spans.
+ *   c = float(S / M), or lo where M == 0 (so +inf under a node without a labelled primitive, which the
+ *   walk never reads).  d_label_ranges[i * 2 + ..] = {lab_lo, lab_hi}: the smallest and largest label
+ *   >= 0 below node i, {INT32_MAX, -1} where there is none.
+ *   When no label is negative, the 12-float records equal grace_gravity_moments_f4's bit for bit.
+ *   n_nodes == 0: GRACE_OK, nothing written.  GRACE_INVALID_ARGUMENT, nothing written: as
+ *   grace_gravity_moments_f4, and null d_labels, null d_label_ranges with n_nodes > 0.
+ *
+ * grace_gravity_group_points_f4.  For a point p with finite coordinates and label L >= 0 the
+ * recursion visit(root):
+ *   visit(inner node i):
+ *     lab_lo[i] > L or lab_hi[i] < L: nothing, no term and no count;
+ *     lab_lo[i] == lab_hi[i] and size2 < fl(theta2 * d2min) (the fp32 test of
+ *       grace_gravity_points_f4 on the record's box): one term {c, M32}, one node term counted;
+ *     otherwise visit(left child), then visit(right child).
+ *     A node that holds two or more labels is never a monopole.
+ *   visit(leaf): one term per primitive j with labels[j] == L, in ascending index, a particle term
+ *     counted for each.
+ *   Terms, rounding, the d2 == 0 rule, the fp64 running sums in the order of the recursion,
+ *   out = {a, phi = -P} and counts = {node terms, particle terms} are exactly those of
+ *   grace_gravity_points_f4.
+ * A point with a negative label or a non-finite coordinate gets +0 throughout and zero counts.  A
+ * point whose label no particle carries gets no term (phi = -0).
+ * So: theta == 0 is the direct sum over the label's members in ascending tree index, independent of
+ * the tree.  With all labels and point labels equal to one value >= 0, out and counts equal
+ * grace_gravity_points_f4's bit for bit.  For theta > 0 the result depends on the tree and on which
+ * particles carry which labels, and on nothing else: not on the point order, the packets,
+ * elems_per_point, the knobs or the stream; it is bit-identical from run to run.
+ * GRACE_INVALID_ARGUMENT, nothing written: as grace_gravity_points_f4, and null d_labels, null
+ * d_point_labels, null d_label_ranges with n_nodes > 0.  d_moments and d_label_ranges must be
+ * grace_gravity_group_moments_f4's for this tree, these masses and these labels.  The walk pushes
+ * both children of every node it opens, as the open walk does, so the stack bound is the same; an
+ * overflow is reported through the status word.
+ * An unbinding pass is: set the labels of the unbound members to -1, the moments again, the walk again.
+ * Not provided: a theta or eps per group, particles in more than one group, the unbinding loop itself
+ * (INTEGRATION.md shows it), periodic boxes, and everything grace_gravity_points_f4 leaves out. */
+grace_status grace_gravity_group_moments_f4(const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                            size_t n_nodes, const int* d_leaves, const int* d_root,
+                                            const float* d_masses, const int* d_labels, float* d_moments,
+                                            int* d_label_ranges, grace_stream stream);
+grace_status grace_gravity_group_points_f4(const float* d_points, size_t n_points, int elems_per_point,
+                                           const float* d_spheres, size_t n_spheres, const int* d_nodes,
+                                           size_t n_nodes, const int* d_leaves, const int* d_root,
+                                           const float* d_masses, const int* d_labels, const float* d_moments,
+                                           const int* d_label_ranges, const int* d_point_labels, float theta,
+                                           float eps, double* d_out, int* d_counts, grace_stream stream);
+
 /* ---- Periodic boxes for the point queries: range queries, friends-of-friends, pair counts, nearest
  * neighbours, smoothing lengths and interpolation (an extension the reference lacks)
  * The five families above on a torus: a cosmological snapshot is a periodic box, and a halo that
